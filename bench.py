@@ -1,7 +1,11 @@
 # coding: utf-8
 """Headline benchmark: src+tgt tokens/sec of the Transformer-base training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`value`, `ms_per_step` = milliseconds
+of one timed step, ...); --dump-outputs DIR also writes what the last timed step computed (dump_outputs()).  The extra
+objects below are measured only with --full.
 
 One "step" = what a user's training loop runs per batch (zero_amd.main.Trainer.step, the call of zero_amd.main.train):
 the batch's ids go host -> HBM through pinned staging slots, ONE launch derives what depends on the ids alone (masks,
@@ -12,8 +16,8 @@ N>1) + global-norm + Adam.  The timed loop feeds a ROTATION of 8 distinct synthe
 accumulate / fp32 master weights, dropouts 0.1 and label smoothing 0.1 as in the canonical recipe.  Weak scaling: every
 rank draws its own batches.  `static_batch_ms_per_step` in the same line is the old measurement (one pre-uploaded batch
 replayed: the device work alone); --static-batch makes it the headline of a SIDE measurement.  With --gpus N and no launcher (WORLD_SIZE unset) bench.py starts its N ranks itself
-(torch.distributed.run on 127.0.0.1); under torchrun it goes straight on.  Rank 0 prints ONE JSON line
-(contract in the task statement) with these extra objects:
+(torch.distributed.run on 127.0.0.1); under torchrun it goes straight on.  Rank 0 prints ONE JSON line; with N > 1
+it always carries `rccl` with the timed legs (the headline is chosen among them), and with --full these extra objects:
 
   roofline     -- the dominant kernel CLASS (the class with the largest time per step: splitting or merging template
                   instances cannot move it), achieved = algorithmic FLOPs of its launches / their HIP-event time,
@@ -775,6 +779,28 @@ def cpu_decode_baseline(hp, model, batches):
                       "torch-CPU fp32 restatement of search.py + transformer_aan.py" % r["steps"]}
 
 
+DUMP_SAMPLE = 1 << 22     # weights in the --dump-outputs sample (16 MB of fp32)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(tr, loss, out_dir):
+    """--dump-outputs: what the last timed step computed, as <out_dir>/<name>.npy -- the loss the step returned
+    (float32 [1]), the global gradient norm of its update (float64 [1]) and a fixed, seeded sample of the updated fp32
+    master weights (float32 [DUMP_SAMPLE]), taken in the logical layout of the variables in sorted-name order so that
+    two builds of the project compare element for element whatever their padding."""
+    st = tr.store
+    if st.device.type == "cuda":
+        torch.cuda.synchronize()
+    flat = torch.cat([st.w(n)[tuple(slice(0, s) for s in st.lshape[n])].reshape(-1) for n in sorted(st.names())])
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=min(DUMP_SAMPLE, flat.numel())))
+    sample = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy().astype(np.float32)
+    gnorm = tr.train_op.stats()[0]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().reshape(-1)[:1].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "grad_norm.npy"), np.array([gnorm], dtype=np.float64))
+    np.save(os.path.join(out_dir, "weights_sample.npy"), sample)
+
+
 def choose_headline(legs):
     """The leg whose time is the line's `value`: the fastest REFERENCE-EXACT leg (fp32 gradient buckets -- what
     utils/parallel.py:184-196 averages) unless a bf16-bucket leg beats it by more than 3 %.  legs: dicts with `ms_per_step`
@@ -821,7 +847,7 @@ def main():
     ap.add_argument("--sentences-per-gpu", type=int, default=B,
                     help="training batch in sentences per GPU (default 64 = the metric's 4096+4096 tokens; other "
                          "values are SIDE measurements that separate kernel quality from 'problem too small for 256 CUs')")
-    ap.add_argument("--no-decode", action="store_true", help="skip the decode leg of the default line")
+    ap.add_argument("--no-decode", action="store_true", help="skip the decode leg of the --full line")
     ap.add_argument("--static-batch", action="store_true",
                     help="SIDE measurement: time the replay of ONE pre-uploaded batch (rounds 1-3's loop) instead of "
                          "Trainer.step on rotating batches; the default line carries both")
@@ -832,7 +858,16 @@ def main():
                          "legs): what a rocprofv3 --kernel-trace of the CAPTURED step should see (scripts/gpu_round5.sh profstep)")
     ap.add_argument("--decode-streams", type=int, default=0,
                     help="decode batches in flight at once (0 = ZERO_HIP_DECODE_STREAMS or its default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: the other timed loop (static batch), "
+                         "the step without the exchange (N > 1), the roofline pass, the decode leg and the CPU baseline. "
+                         "Without it the run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, gradient norm, a fixed sample of the updated "
+                         "weights) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "train":
+        ap.error("--dump-outputs writes the outputs of the training step (--mode train)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: spawn the N ranks ourselves (one process per GPU, torchrun's
@@ -869,6 +904,8 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    last_loss = [None]        # what the last timed step returned (--dump-outputs)
+
     def timed(step_fn, steps, warm):
         """warm untimed steps, then EXACTLY `steps` steps between barrier + synchronize; max over ranks (seconds)."""
         loss = None
@@ -884,6 +921,7 @@ def main():
                 loss = step_fn(warm + i)
             barrier()
             dt = time.perf_counter() - t0
+        last_loss[0] = loss
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         if world > 1:
             torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -997,12 +1035,31 @@ def main():
             run_leg("bf16", True, True, guard_s=guard)
         # headline = the fastest reference-exact (fp32) leg unless bf16 buckets win by more than 3 %
         chosen = choose_headline(legs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, last_loss[0], args.dump_outputs)
+    if world > 1 and args.full:
         # leave the reducer in the chosen mode for what follows
         parallel.select_transport(chosen["transport"] == "zk_comm")
         tr.reducer.configure(bucket_dtype=chosen["bucket_dtype"], sparse=bool(chosen["sparse_rows_exchange"]))
         for _ in range(2):
             rotating(0)
     dt, loss = chosen["_dt"], chosen["_loss"]
+    if not args.full and not args.timed_only:
+        # the plain run: the headline line and nothing else
+        if rank == 0:
+            line = bench_line(chosen, legs)
+            if world > 1:
+                line["rccl"]["ranks_seen"] = ranks_seen_box[0]
+            # the in-launch LayerNorm exchange bounds every wait and records a give-up on the device: a line measured
+            # with one is void
+            line["sync_ln_errors"] = int(tr.core.eng.sync_ln_errors())
+            if line["sync_ln_errors"]:
+                raise RuntimeError("bench.py: a workgroup of an in-launch LayerNorm exchange gave up waiting for its "
+                                   "peers; the measurement is void (ZERO_HIP_SYNC_LN=0 runs the launch structure without it)")
+            print(json.dumps(line))
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     if args.timed_only:
         if rank == 0:
             line = bench_line(chosen, legs)

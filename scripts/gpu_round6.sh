@@ -11,29 +11,30 @@
 #   mfma / traffic / trafficd   PMC passes (scripts/pmc_*.sh), each in runs of its own
 set -u
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+OUT=${OUT:-out}      # where the stages write their logs, relative to the repository root
+mkdir -p "$OUT"
 export PYTHONPATH=$PWD TMPDIR=/tmp
 STAGES=${1:-"all smoke benchq"}
 prof_decode() {   # $1 dtype, $2 tag
-  (cd /tmp && ZERO_HIP_DECODE_STREAMS=1 timeout 600 rocprofv3 --kernel-trace --stats -d $OLDPWD/gpurun_out/profd_$2 -o r1 -- python $OLDPWD/scripts/decode_bench.py --sentences 128 --dtype $1 > $OLDPWD/gpurun_out/profd_$2.log 2>&1); echo "rc=$?"
-  python scripts/prof_summary.py $(find gpurun_out/profd_$2 -name "*.db" | head -1) 1 > gpurun_out/rocprof_decode_$2.txt 2>&1; rm -rf gpurun_out/profd_$2
-  tail -1 gpurun_out/profd_$2.log; head -${PROF_HEAD:-40} gpurun_out/rocprof_decode_$2.txt
+  (cd /tmp && ZERO_HIP_DECODE_STREAMS=1 timeout 600 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/profd_$2 -o r1 -- python $OLDPWD/scripts/decode_bench.py --sentences 128 --dtype $1 > $OLDPWD/$OUT/profd_$2.log 2>&1); echo "rc=$?"
+  python scripts/prof_summary.py $(find $OUT/profd_$2 -name "*.db" | head -1) 1 > $OUT/rocprof_decode_$2.txt 2>&1; rm -rf $OUT/profd_$2
+  tail -1 $OUT/profd_$2.log; head -${PROF_HEAD:-40} $OUT/rocprof_decode_$2.txt
 }
 for st in $STAGES; do
   echo "=== stage $st $(date +%T)"
   case $st in
-    all)    timeout 1800 python -m pytest tests -m gpu -q -p no:cacheprovider > gpurun_out/all_gpu.log 2>&1; echo "rc=$?"; grep -E "^FAILED|^ERROR" gpurun_out/all_gpu.log | head -40; tail -3 gpurun_out/all_gpu.log ;;
-    beam)   timeout 1200 python -m pytest tests/test_gpu_fullsize.py -m gpu -q -p no:cacheprovider -k "beam or fixture" > gpurun_out/beam.log 2>&1; echo "rc=$?"; grep -E "^FAILED|^ERROR" gpurun_out/beam.log | head; tail -4 gpurun_out/beam.log ;;
-    smoke)  timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; echo "rc=$?"; tail -3 gpurun_out/smoke.log ;;
-    bench)  timeout 900 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; echo "rc=$?"; tail -c 1500 gpurun_out/bench.json; tail -3 gpurun_out/bench.err ;;
-    benchq) timeout 600 python bench.py --no-cpu-baseline --no-decode > gpurun_out/benchq.json 2> gpurun_out/benchq.err; echo "rc=$?"; grep -o '"ms_per_step": [0-9.]*\|"static_batch_ms_per_step": [0-9.]*\|"launches_per_step": [0-9]*' gpurun_out/benchq.json; tail -3 gpurun_out/benchq.err ;;
-    profstep) (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OLDPWD/gpurun_out/profs -o r1 -- python $OLDPWD/bench.py --steps 40 --warmup 2 --timed-only > $OLDPWD/gpurun_out/profstep.log 2>&1); echo "rc=$?"
-            python scripts/prof_summary.py $(find gpurun_out/profs -name "*.db" | head -1) 42 > gpurun_out/rocprof_captured_step.txt 2>&1
-            python scripts/prof_gaps.py $(find gpurun_out/profs -name "*.db" | head -1) > gpurun_out/rocprof_captured_step_gaps.txt 2>&1
-            rm -rf gpurun_out/profs; head -${PROF_HEAD:-50} gpurun_out/rocprof_captured_step.txt; tail -2 gpurun_out/profstep.log; head -${GAP_HEAD:-12} gpurun_out/rocprof_captured_step_gaps.txt ;;
-    prof)   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OLDPWD/gpurun_out/prof -o r1 -- python $OLDPWD/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-decode > $OLDPWD/gpurun_out/prof.log 2>&1); echo "rc=$?"
-            python scripts/prof_summary.py $(find gpurun_out/prof -name "*.db" | head -1) > gpurun_out/rocprof_kernel_stats.txt 2>&1
-            rm -rf gpurun_out/prof; head -${PROF_HEAD:-45} gpurun_out/rocprof_kernel_stats.txt ;;
+    all)    timeout 1800 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/all_gpu.log 2>&1; echo "rc=$?"; grep -E "^FAILED|^ERROR" $OUT/all_gpu.log | head -40; tail -3 $OUT/all_gpu.log ;;
+    beam)   timeout 1200 python -m pytest tests/test_gpu_fullsize.py -m gpu -q -p no:cacheprovider -k "beam or fixture" > $OUT/beam.log 2>&1; echo "rc=$?"; grep -E "^FAILED|^ERROR" $OUT/beam.log | head; tail -4 $OUT/beam.log ;;
+    smoke)  timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "rc=$?"; tail -3 $OUT/smoke.log ;;
+    bench)  timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"; tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err ;;
+    benchq) timeout 600 python bench.py --full --no-cpu-baseline --no-decode > $OUT/benchq.json 2> $OUT/benchq.err; echo "rc=$?"; grep -o '"ms_per_step": [0-9.]*\|"static_batch_ms_per_step": [0-9.]*\|"launches_per_step": [0-9]*' $OUT/benchq.json; tail -3 $OUT/benchq.err ;;
+    profstep) (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/profs -o r1 -- python $OLDPWD/bench.py --steps 40 --warmup 2 --timed-only > $OLDPWD/$OUT/profstep.log 2>&1); echo "rc=$?"
+            python scripts/prof_summary.py $(find $OUT/profs -name "*.db" | head -1) 42 > $OUT/rocprof_captured_step.txt 2>&1
+            python scripts/prof_gaps.py $(find $OUT/profs -name "*.db" | head -1) > $OUT/rocprof_captured_step_gaps.txt 2>&1
+            rm -rf $OUT/profs; head -${PROF_HEAD:-50} $OUT/rocprof_captured_step.txt; tail -2 $OUT/profstep.log; head -${GAP_HEAD:-12} $OUT/rocprof_captured_step_gaps.txt ;;
+    prof)   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OLDPWD/$OUT/prof -o r1 -- python $OLDPWD/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-decode > $OLDPWD/$OUT/prof.log 2>&1); echo "rc=$?"
+            python scripts/prof_summary.py $(find $OUT/prof -name "*.db" | head -1) > $OUT/rocprof_kernel_stats.txt 2>&1
+            rm -rf $OUT/prof; head -${PROF_HEAD:-45} $OUT/rocprof_kernel_stats.txt ;;
     mfma)   bash scripts/pmc_mfma.sh ;;
     traffic) bash scripts/pmc_traffic.sh ;;
     trafficd) bash scripts/pmc_traffic_decode.sh ;;
@@ -41,7 +42,7 @@ for st in $STAGES; do
     profd16) prof_decode bfloat16 bf16_1lane ;;
     dec32)  ZERO_HIP_DECODE_STREAMS=1 timeout 600 python scripts/decode_bench.py --sentences 256 --dtype float32 2>&1 | tail -1 ;;
     dec16)  ZERO_HIP_DECODE_STREAMS=1 timeout 600 python scripts/decode_bench.py --sentences 256 --dtype bfloat16 2>&1 | tail -1 ;;
-    decode) timeout 600 python bench.py --mode decode > gpurun_out/bench_decode.json 2> gpurun_out/bench_decode.err; echo "rc=$?"; tail -c 1200 gpurun_out/bench_decode.json ;;
+    decode) timeout 600 python bench.py --mode decode > $OUT/bench_decode.json 2> $OUT/bench_decode.err; echo "rc=$?"; tail -c 1200 $OUT/bench_decode.json ;;
     *)      echo "unknown stage $st" ;;
   esac
 done

@@ -190,7 +190,7 @@ def test_bench_contract_with_two_ranks_on_one_gpu():
     env = dict(os.environ, PYTHONPATH=root, ZERO_DIST_BACKEND="gloo", ZERO_SINGLE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "2"]
+           "--warmup", "2", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -239,6 +239,33 @@ def test_bench_spawns_its_own_ranks_when_not_under_a_launcher():
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["rccl"]["ranks"] == 2 and out["value"] > 0
+
+
+def test_plain_bench_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline line of exactly K timed steps and
+    none of the objects that --full measures; DIR holds the loss, gradient norm and weight sample of the last step."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["n_gpus"] == 1 and out["unit"] == "src+tgt tokens/s" and out["dtype"] == "bf16"
+    assert out["higher_is_better"] is True and out["ms_per_step"] > 0 and out["sync_ln_errors"] == 0
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 64 * 128) < 1e-6 * 64 * 128     # tokens of one step
+    assert not {"roofline", "decode", "cpu_baseline", "static_batch_ms_per_step", "rccl"} & set(out)
+    loss = np.load(str(out_dir / "loss.npy"))
+    gnorm = np.load(str(out_dir / "grad_norm.npy"))
+    w = np.load(str(out_dir / "weights_sample.npy"))
+    assert loss.dtype == np.float32 and loss.shape == (1,) and 5.0 < float(loss[0]) < 15.0   # ~ln(32000) at the start
+    assert gnorm.dtype == np.float64 and np.isfinite(gnorm).all() and gnorm[0] > 0
+    assert w.dtype == np.float32 and 0.9 * (1 << 22) < w.size <= (1 << 22) and np.isfinite(w).all()
+    assert sum(os.path.getsize(str(p)) for p in out_dir.iterdir()) <= 64 << 20
 
 
 def test_rccl_communicator_through_the_c_abi_single_rank():

@@ -298,3 +298,39 @@ def test_counter_files_of_an_earlier_round_or_a_dirty_tree_are_flagged_stale(mon
     assert bench.counter_status("pmc.json", "abc")["stale"] is True and bench.counter_status(None, None) is None
     monkeypatch.undo()
     assert bench.current_round() >= 1
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_of_the_logical_weights(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs DIR): loss, gradient norm and a seeded sample of the updated weights taken in
+    the LOGICAL layout (padding rows never sampled), identical from call to call, float32 / float64, within 64 MB."""
+    import types
+    import torch
+    import bench
+    hp = make_hp("transformer", Vs=13, Vt=11)
+    st = VariableStore(hp, "transformer", "cpu")
+    vals = initial_values(hp, "transformer", 3)
+    st.load(vals)
+    tr = types.SimpleNamespace(store=st, train_op=types.SimpleNamespace(stats=lambda: (1.5, 2.0, False)))
+    assert bench.DUMP_SAMPLE * 4 <= 64 << 20                      # the whole dump stays within 64 MB
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 5000)
+    for d in ("a", "b"):
+        bench.dump_outputs(tr, torch.tensor([3.25]), str(tmp_path / d))
+    a = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("loss", "grad_norm", "weights_sample")}
+    b = {n: np.load(str(tmp_path / "b" / (n + ".npy"))) for n in a}
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    assert a["loss"].dtype == np.float32 and a["loss"].tolist() == [3.25]
+    assert a["grad_norm"].dtype == np.float64 and a["grad_norm"].tolist() == [1.5]
+    flat = np.concatenate([vals[n].reshape(-1) for n in sorted(vals)])
+    idx = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, flat.size, size=5000))
+    assert a["weights_sample"].dtype == np.float32 and np.array_equal(a["weights_sample"], flat[idx])
+
+
+def test_bench_options_of_a_plain_and_a_full_run():
+    """bench.py --help (no GPU needed): --full moves the extra measurements behind an option, --dump-outputs DIR exists."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=300, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout and "--steps" in r.stdout
