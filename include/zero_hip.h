@@ -98,34 +98,11 @@ int zk_proj_attn_out_ln(const void* x, int ldx, const void* Wp, int ldwp, const 
                    const float* beta, float eps, void* s_out, void* y, float* mean, float* rstd, void* slots,
                    size_t slots_bytes, void* flags, size_t flags_bytes, const uint32_t* epoch, uint32_t site, int* err,
                    zk_stream_t stream);
-#ifdef ZK_EXPERIMENTS   /* measured, no gain over the two launches (profiles/r04_negative_results.txt item 8) */
-/* Attention backward (single-tile path of zk_attn_bwd with the o_map dgrad folded in: d = 64, Lq, Lk <= 64, no relative
- * positions) + the dgrad dx = dA W^T + residual that consumes its dq / dk / dv (dA [B*Lq, K]: the matrix they are columns of)
- * + the LayerNorm backward of the sub-layer below (as zk_gemm_ln_bwd), one launch: workgroup (sentence, head) computes its
- * head's gradients, waits for the sentence's heads, runs its 64-column dgrad tile.  partials: [B][3][nh*64] (one row per
- * sentence).  flags: zk_attn_out_ln_flags bytes, zero-filled once.  Returns 2 (nothing launched) when not covered. */
-int zk_attn_bwd_ln(const void* q, const void* k, const void* v, const void* out, const float* lse, void* dq, void* dk, void* dv,
-                   int B, int nh, int Lq, int Lk, int d, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
-                   const float* kmask, int causal, float scale, float mask_inf, float attn_drop_p, const uint64_t* seed,
-                   uint32_t attn_sid, const void* oproj_dy, int oproj_lddy, const void* oproj_w, int oproj_ldw, int oproj_n,
-                   const void* dA, int lda, const void* W, int ldw, int K, const void* residual, int ldr, const void* s,
-                   const float* mean, const float* rstd, const float* gamma, float drop_p, uint32_t sid, void* dsum,
-                   void* dy_out, float* partials, void* slots, size_t slots_bytes, void* flags, size_t flags_bytes,
-                   const uint32_t* epoch, uint32_t site, int* err, zk_stream_t stream);
-#endif
 size_t zk_gemm_ln_bwd_partials(int rows, int N);
 int zk_gemm_ln_bwd(const void* dY, const void* W, int M, int N, int K, int lda, int ldb, const void* residual, int ldr,
                    const void* s, const float* mean, const float* rstd, const float* gamma, float drop_p,
                    const uint64_t* seed, uint32_t sid, void* dsum, void* dy_out, float* partials, void* slots,
                    size_t slots_bytes, const uint32_t* epoch, uint32_t site, int* err, zk_stream_t stream);
-#ifdef ZK_EXPERIMENTS   /* measured: slower than the two launches (profiles/r04_negative_results.txt item 9) */
-/* The two products of a feed-forward sub-layer on few rows (the decode step: func.py:327-338 at batch x beam rows) in one
- * launch: h = relu(x W1 + b1) (bf16 [M, F]), then -- behind a barrier among the launch's workgroups -- parts[z] = h[:, K_z]
- * W2[K_z, :] as zk_gemm_parts leaves them (fp32 [M, H] at parts + z M H; *nparts_out parts).  counter: a zeroed device
- * uint64 shared only by calls with the same (ceil(M/64), F).  Returns 2 (nothing launched) when the shape is not covered. */
-int zk_ffn_pair(const void* x, const void* W1, const float* b1, void* h, const void* W2, float* parts, int M, int F, int H, int K1,
-                int ldx, int ldw1, int ldw2, int splits, int* nparts_out, void* counter, int* err, zk_stream_t stream);
-#endif
 int zk_gemm_plan(int M, int N, int K, int out_f32, int plain);  /* gen | (bm/8)<<8 | (bn/8)<<16 | splits<<24 | producer waves<<28 chosen by impl=0 */
 int zk_gemm_set_generation(int gen);   /* 1 = register-staged kernel, 2 = LDS-DMA ring kernel (default) */
 /* K-segmented GEMM: C bf16 [M, ldc] = sum_s A_s [M, kseg] x B_s (+ bf16 residual, may alias C) in ONE launch --
@@ -150,21 +127,6 @@ int zk_gemm(const void* A, const void* B, void* C, int M, int N, int K, int lda,
  * tile_start = running sum of ceil(M/T)*ceil(N/T) with T = 128 (tile=1) or 64 (tile=4). */
 int zk_gemm_grouped(const void* descs, int nprob, int total_tiles, int ta, int tb, int tile,
                     zk_stream_t stream);
-
-#ifdef ZK_EXPERIMENTS   /* measured slower than GEMM + zk_ce_fused (profiles/r02_fused_ce_256_tile.txt): make EXPERIMENTS=1 */
-/* ---- transformer.py:182-216 + util.py:88-103 fused for training: logits = feat . E^T and the label-smoothed
- * cross entropy WITHOUT materialising the [T, V] logits.  fwd: ce fp32 [T] (may be NULL), lse fp32 [T]
- * (log-sum-exp of every row, kept for the backward); bwd: recomputes the logits tile by tile and writes
- * dlogits bf16 [T, ldd] = w_row * (softmax - soft labels) (columns >= V zero), the operand of the two
- * logits-gradient GEMMs.  feat bf16 [T, K] (ldf); E bf16 [>= V rows, K] (lde).  label smoothing as util.py:88-103
- * (p = 1 - eps on the gold id, q = eps / (V - 1) elsewhere, normaliser subtracted). */
-size_t zk_logits_ce_workspace(int T, int V);
-int zk_logits_ce_fwd(const void* feat, const void* E, const int* ids, float* ce, float* lse, int T, int V, int K,
-                     int ldf, int lde, float label_smooth, void* workspace, size_t ws_bytes, zk_stream_t stream);
-int zk_logits_ce_bwd(const void* feat, const void* E, const int* ids, const float* w, const float* lse,
-                     void* dlogits, int T, int V, int K, int ldf, int lde, int ldd, float label_smooth,
-                     zk_stream_t stream);
-#endif /* ZK_EXPERIMENTS */
 
 /* ---- func.py:218-256 dot_attention core (+ modules/rpr.py:10-75 relative positions).
  * q/k/v/out: [B*L, ld] bf16, head h at columns [h*d,(h+1)*d) (split/combine_heads,
@@ -265,33 +227,6 @@ int zk_embed_bwd(const int* ids, const void* dout, float* dtable, float* dbias, 
 int zk_embed_bwd_sorted(const int* rows_sorted, const int* seg, const int* uid, const int* n_uniq_dev,
                         int max_uniq, const void* dout, float* dtable, int H, float scale, int accumulate,
                         float drop_p, const uint64_t* seed, uint32_t sid, zk_stream_t stream);
-
-#ifdef ZK_EXPERIMENTS   /* measured: no gain over the LayerNorm launches (profiles/r04_negative_results.txt): make EXPERIMENTS=1 */
-/* ---- round 4: residual + LayerNorm WITHOUT a launch of its own (func.py:289-303, 321-324 in the post-LN order of
- * transformer.py:57-58; the forward half of the 30 LayerNorm launches of a Transformer-base step).
- *   zk_gemm_ln   forward linear (func.py:14-65; A [M,K] x B [K,N], bf16 out) with the LayerNorm around it folded into
- *                the epilogue.  PRODUCER (stat_out != NULL): C = residual + dropout(A B + bias), the sub-layer's
- *                un-normalised sum, and stat_out [M][N/64][2] = {sum, M2} of every (row, 64-column group) of the
- *                stored values.  res_part != NULL: the residual operand is the previous sub-layer's un-normalised sum
- *                and is normalised on the fly (res_part [M][np][2], res_gamma / res_beta [N]).  CONSUMER
- *                (in_c != NULL): A is an un-normalised sum (statistics in_part [M][np][2], np = K/64), B the weight
- *                with gamma folded in, in_c / bias the vectors of zk_ln_fold:
- *                C = act(rstd (A B - mu in_c) + bias), then dropout.  act: 0 none, 1 ReLU.
- *   zk_ln_fold   per step, from the fp32 masters: Wf = bf16(gamma_k W_kn), c_n = sum_k Wf_kn, d_n = sum_k beta_k W_kn
- *                + b_n for every consumer weight; descs = DEVICE array of {W, gamma, beta, b, Wf, c, d pointers; int K, N,
- *                block_start (running sum of N/64), pad} (64 bytes), total_blocks = that sum.
- *   zk_add_ln_bwd_lazy   the backward of such a LayerNorm: statistics from `part`; y_out (optional) receives
- *                LN(sum) as zk_add_ln_fwd would have written it -- the X operand of the consumer's weight gradient. */
-int zk_gemm_ln(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, const float* bias,
-               const void* residual, int ldr, int act, float drop_p, const uint64_t* seed, uint32_t sid, float* stat_out,
-               const float* in_part, const float* in_c, const float* res_part, const float* res_gamma,
-               const float* res_beta, int np, float eps, zk_stream_t stream);
-int zk_ln_fold(const void* descs, int nprob, int total_blocks, zk_stream_t stream);
-int zk_add_ln_bwd_lazy(const void* dout, const void* sum, const float* part, const float* gamma, const float* beta,
-                       void* y_out, void* dsum, void* dy, float* dgamma, float* dbeta, float* dbias_prev, int rows, int H,
-                       float eps, float drop_p, const uint64_t* seed, uint32_t sid, void* workspace, size_t ws_bytes,
-                       int defer_reduce, zk_stream_t stream);
-#endif /* ZK_EXPERIMENTS */
 
 /* ---- func.py:321-324 residual_fn + func.py:289-303 layer_norm (post-LN, eps inside
  * rsqrt): out = LN(x + dropout(y)).  sum_out/mean/rstd are saved for the backward.    */
@@ -402,33 +337,6 @@ size_t zk_adam_step_workspace(void);
 int zk_adam_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, size_t n, float* hyper,
                  float* pnorm_out, uint64_t* seed, int norm_free, const int* skip_word, void* workspace, size_t ws_bytes,
                  zk_stream_t stream);
-#ifdef ZK_EXPERIMENTS   /* measured slower than gradient launch + Adam pass (profiles/r04_negative_results.txt): make EXPERIMENTS=1 */
-/* ---- round 4: the optimiser update of the weight matrices INSIDE the launch that makes their gradients
- * (utils/cycle.py:94-101 norm-free form + main.py:178-181 TF1 Adam, fused into the autodiff mirror of func.py:14-65).
- *   zk_gemm_grouped_update   the grouped weight-gradient launch of 256 x 256 tiles (as zk_gemm_grouped with ta = 1,
- *       tb = 0, tile 8 | 256: bias column sums ride along); a descriptor with pad & 1 marks a problem whose output C is a
- *       whole variable inside the flat gradient buffer `grad_base`: its tiles do not store the gradient but run Adam on
- *       the accumulators against master / m / v / shadow at the same offset (hyper as zk_adam_step) and leave the wave's
- *       {sum g^2, sum theta^2} in sq [total_tiles][8][2] (zeros from the other tiles).
- *   zk_adam_step_segments    the norm-free update of everything else: segments [seg_lo[s], +len) of the flat buffers
- *       (DEVICE int64 arrays, elements, multiples of 4, ascending; prefix = running lengths, prefix[0] = 0, total =
- *       prefix[nseg]), then gradient / parameter norms over both parts (extra = sq above, n_extra = total_tiles * 8). */
-int zk_gemm_grouped_update(const void* descs, int nprob, int total_tiles, float* master, float* m, float* v, void* shadow,
-                           const float* grad_base, const float* hyper, float* sq, zk_stream_t stream);
-int zk_adam_step_segments(float* p, const float* g, float* m, float* v, void* shadow, const long* seg_lo, const long* prefix,
-                          int nseg, long total, float* hyper, float* pnorm_out, uint64_t* seed, const float* extra,
-                          int n_extra, void* workspace, size_t ws_bytes, zk_stream_t stream);
-#endif /* ZK_EXPERIMENTS */
-#ifdef ZK_EXPERIMENTS   /* Adam beside the encoder backward: 5.01 vs 4.94 ms: make EXPERIMENTS=1 */
-/* the norm-free update in pieces: TF1 Adam on n elements writing its partial sums of squares into workspace slot
- * `slot` (< 16); zk_adam_finish sums nslots slots -> hyper[6] (+ flags), pnorm_out, seed += 1.  Lets the update of
- * the parameters whose gradients are final run beside the rest of the backward (and behind per-bucket all-reduces). */
-size_t zk_adam_range_workspace(void);
-int zk_adam_range(float* p, const float* g, float* m, float* v, void* shadow_bf16, size_t n, float* hyper, int slot,
-                  void* workspace, size_t ws_bytes, zk_stream_t stream);
-int zk_adam_finish(float* hyper, float* pnorm_out, uint64_t* seed, int nslots, const void* workspace, size_t ws_bytes,
-                   zk_stream_t stream);
-#endif /* ZK_EXPERIMENTS */
 int zk_norm_flag(float* hyper, zk_stream_t stream);
 int zk_cast_f32_bf16(const float* x, void* y, size_t n, zk_stream_t stream);
 int zk_cast_bf16_f32(const void* x, float* y, size_t n, zk_stream_t stream);
@@ -484,28 +392,6 @@ int zk_comm_allgather(void* comm, const void* send, void* recv, size_t count, in
  * NULL).  zero_amd/utils/parallel.py RcclComm uses the pair per gradient bucket under ZERO_HIP_COMM_HANDOFF=flag. */
 int zk_flag_add(void* flag, zk_stream_t stream);
 int zk_flag_wait(const void* flag, unsigned long long target, int* err, zk_stream_t stream);
-
-#ifdef ZK_EXPERIMENTS   /* measured 1.25x slower than launch-per-op (profiles/r02_layer_program_experiment.txt) */
-/* ---- Layer program (zk_layer.hip): a run of dependent, sentence-local ops -- the linear / attention / residual +
- * LayerNorm chain of the encoder and decoder stacks (transformer.py:35-69, 121-181; func.py:194-338) -- executed by ONE
- * persistent launch instead of one launch per op.  The B sentences are dealt to the 8 XCDs; every XCD walks the op list
- * on its own sentences with a barrier among ITS workgroups between ops, activations staying in its L2.  The ops run
- * the same tile functions as the launch-per-op kernels: bit-identical results.
- * Recording: between zk_prog_begin(B) and zk_prog_end on one host thread, zk_gemm (untransposed A), zk_attn_fwd,
- * zk_attn_bwd (one 64x64 tile per sentence and head) and zk_add_ln_fwd append an op instead of launching; any other
- * variant makes the recording fail (zk_prog_end returns -2 and the caller issues ordinary launches).  Entry points
- * that are not listed here must not be called while recording.  A program is either a forward chain (gemm, attention
- * forward, residual + LayerNorm) or a backward chain (gemm, attention backward): zk_prog_end reports which in
- * *is_backward, to be passed to zk_prog_launch.  zk_prog_end copies the ops to a HOST buffer; the
- * caller uploads them and owns the device copy and the state buffer (zk_prog_state_bytes(), any content).
- * state after a launch (ints): [576] workgroups found on another XCD than their group's (handled: that group runs
- * placement-independent barriers), [577] != 0: a barrier timed out and the launch drained (results invalid). */
-size_t zk_prog_op_bytes(void);
-size_t zk_prog_state_bytes(void);
-int zk_prog_begin(int sentences);
-int zk_prog_end(void* ops_out, size_t cap_bytes, int* nops, int* is_backward);
-int zk_prog_launch(const void* ops_dev, int nops, int sentences, int backward, void* state_dev, zk_stream_t stream);
-#endif /* ZK_EXPERIMENTS */
 
 /* dropout plumbing */
 int zk_dropout_mask(float* out, size_t n, float drop_p, const uint64_t* seed, uint32_t sid, zk_stream_t stream);

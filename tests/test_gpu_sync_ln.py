@@ -222,85 +222,6 @@ def test_projection_inside_the_attention_launch(B, Lq, Lk, pro, causal, masked, 
         assert torch.equal(r, t), name
 
 
-@pytest.mark.parametrize("B,Lq,Lk,K3,causal,drop", [(64, 64, 64, True, True, 0.1), (64, 64, 64, False, False, 0.0),
-                                                    (16, 37, 37, True, True, 0.1), (8, 13, 50, False, False, 0.1),
-                                                    (5, 64, 64, True, False, 0.0)])
-def test_attention_backward_inside_the_dgrad_launch(B, Lq, Lk, K3, causal, drop):
-    """zk_attn_bwd_ln against zk_attn_bwd (o_map dgrad folded in) followed by zk_gemm_ln_bwd: dQ / dK / dV are the
-    attention kernel's bit for bit (same tile function), ds / dy are the dgrad launch's bit for bit (same tile function,
-    same K order), the column sums agree after their reductions (one partial row per sentence instead of per 64 rows).
-    K3: the merged q/k/v projection of self-attention (K = 3 H) / the query projection of cross-attention (K = H)."""
-    e = eng()
-    if not e.lib.experiments:
-        pytest.skip("the attention backward inside the dgrad launch is an EXPERIMENTS=1 build (measured, no gain)")
-    e.set_seed(31)
-    nh, d = 8, 64
-    H = nh * d
-    Tq, Tk = B * Lq, B * Lk
-    if K3:
-        qkv = rand_bf(Tq, 3 * H, seed=1)
-        q, k, v = mat(qkv, Tq, H, 3 * H, 0), mat(qkv, Tq, H, 3 * H, H), mat(qkv, Tq, H, 3 * H, 2 * H)
-    else:
-        qt, kvt = rand_bf(Tq, H, seed=1), rand_bf(Tk, 2 * H, seed=2)
-        q, k, v = mat(qt), mat(kvt, Tk, H, 2 * H, 0), mat(kvt, Tk, H, 2 * H, H)
-    kmask = None
-    if not causal:
-        kmask = torch.ones(B, Lk, device="cuda")
-        for i in range(B):
-            kmask[i, Lk - (i % max(1, Lk // 2)):] = 0.0
-    att = torch.empty(Tq, H, dtype=torch.bfloat16, device="cuda")
-    lse = torch.zeros(B * nh * Lq, device="cuda")
-    e.attn_fwd(q, k, v, mat(att), lse, B, nh, Lq, Lk, d, kmask=kmask, causal=causal, drop_p=drop, sid=7)
-    dY, Wo = rand_bf(Tq, H, seed=4, scale=0.2), rand_bf(H, H, seed=5, scale=0.05)
-    Kd = 3 * H if K3 else H
-    Wd = rand_bf(H, Kd, seed=6, scale=0.05)                 # the forward weight [in = H, out = Kd] of the projection
-    R, S = rand_bf(Tq, H, seed=8, scale=0.3), rand_bf(Tq, H, seed=9)
-    gam = (1.0 + 0.2 * torch.randn(H, generator=torch.Generator().manual_seed(4))).cuda()
-    mean = S.float().mean(1).contiguous()
-    rstd = (1.0 / torch.sqrt(S.float().var(1, unbiased=False) + 1e-8)).contiguous()
-
-    def run(fused):
-        if K3:
-            dA = torch.full((Tq, 3 * H), 5.0, dtype=torch.bfloat16, device="cuda")
-            dq, dk, dv = mat(dA, Tq, H, 3 * H, 0), mat(dA, Tq, H, 3 * H, H), mat(dA, Tq, H, 3 * H, 2 * H)
-            dAm = mat(dA)
-        else:
-            dqt = torch.full((Tq, H), 5.0, dtype=torch.bfloat16, device="cuda")
-            dkv = torch.full((Tk, 2 * H), 5.0, dtype=torch.bfloat16, device="cuda")
-            dq, dk, dv = mat(dqt), mat(dkv, Tk, H, 2 * H, 0), mat(dkv, Tk, H, 2 * H, H)
-            dA, dAm = (dqt, dkv), mat(dqt)
-        ds, dyo = torch.full((Tq, H), 7.0, dtype=torch.bfloat16, device="cuda"), torch.full((Tq, H), 7.0, dtype=torch.bfloat16, device="cuda")
-        part = torch.full((max(B * 3 * H, e.lib.query("zk_gemm_ln_bwd_partials", Tq, H) // 4),), 1e9, device="cuda")
-        outs = [torch.zeros(H, device="cuda") for _ in range(3)]
-        e.ln_epoch_bump()
-        if fused:
-            ok = e.attn_bwd_ln(q, k, v, mat(att), lse, dq, dk, dv, B, nh, Lq, Lk, d, kmask, causal, drop, 7, (mat(dY), mat(Wo)),
-                               dAm, mat(Wd), mat(R), mat(S), mean, rstd, gam, mat(ds), mat(dyo) if drop else None, part, drop, 17)
-            assert ok
-            e.reductions_grouped([], [(part, Tq, H, outs[0], outs[1], outs[2], B)])
-        else:
-            datt = torch.empty(Tq, H, dtype=torch.bfloat16, device="cuda")
-            e.attn_bwd(q, k, v, mat(att), mat(datt), lse, dq, dk, dv, B, nh, Lq, Lk, d, kmask=kmask, causal=causal, drop_p=drop,
-                       sid=7, oproj=(mat(dY), mat(Wo)))
-            e.gemm_ln_bwd(dAm, mat(Wd), Tq, H, Kd, mat(R), mat(S), mean, rstd, gam, mat(ds), mat(dyo) if drop else None, part,
-                          drop, 17)
-            e.reductions_grouped([], [(part, Tq, H, outs[0], outs[1], outs[2], True)])
-        torch.cuda.synchronize()
-        return dA, ds, dyo, outs
-
-    ref, got = run(False), run(True)
-    assert e.sync_ln_errors() == 0
-    if K3:
-        assert torch.equal(got[0], ref[0])
-    else:
-        assert torch.equal(got[0][0], ref[0][0]) and torch.equal(got[0][1], ref[0][1])
-    assert torch.equal(got[1], ref[1])
-    if drop:
-        assert torch.equal(got[2], ref[2])
-    for a, b in zip(got[3], ref[3]):
-        assert rel_err(a, b) < 1e-4
-
-
 def test_repeated_launches_reuse_the_slots():
     """Several hundred launches back to back on the same slots, different inputs and sites, the epoch advancing every 30
     launches as it does in a training step (30 sub-layers): every one of them must see this launch's partials, never an

@@ -1,7 +1,6 @@
 // zk_attn_dev.h -- device side of the MFMA attention kernels (d = 64): argument block, relative-position helpers,
 // LDS staging, and the tile functions `attn_fwd_tile` / `attn_bwd_fused64_tile` over a caller-provided LDS buffer.
-// Included by zk_attn.hip (one tile per workgroup launch) and zk_layer.hip (the per-XCD layer program calls the same
-// functions phase after phase: bit-identical results).  See zk_attn.hip for the design notes.
+// Included by zk_attn.hip (one tile per workgroup launch).  See zk_attn.hip for the design notes.
 #pragma once
 #include "zk_common.h"
 

@@ -60,8 +60,8 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
 }
 
 // ---------------------------------------------------------------- loads of data another CU wrote during THIS launch
-// A CU's vector L1 is never refreshed by another CU's stores (MI355X_MICROARCH.md, inter-workgroup visibility).  Inside
-// the persistent layer program (zk_layer.hip) an op reads what other workgroups of its XCD stored one barrier earlier:
+// A CU's vector L1 is never refreshed by another CU's stores (MI355X_MICROARCH.md, inter-workgroup visibility).  When a
+// workgroup reads what other workgroups of the same launch stored behind an in-launch barrier,
 // FRESH = true issues the load with the nt policy, which bypasses the L1 and is served by the XCD's (coherent) L2, so
 // the barrier needs no L1 invalidate (~5 us per barrier at two workgroups per CU).  FRESH = false: ordinary load.
 typedef unsigned int zk_u32x4 __attribute__((ext_vector_type(4)));
@@ -153,29 +153,8 @@ __device__ __forceinline__ void wave_argbest(float& s, int& i, int& t, B better)
 }
 
 // ---------------------------------------------------------------- LayerNorm statistics as per-64-column partials (round 4)
-// (mu, rstd) of row `row` from its per-64-column partials {sum, M2}: Chan's combination, robust for |mean| >> sigma
-#define ZK_LN_MAXP 16
-__device__ __forceinline__ void zk_ln_row_stats(const float* __restrict__ part, int np, float invh, float eps, size_t row,
-                                                float& mu, float& rs) {
-  const float4* p = reinterpret_cast<const float4*>(part + row * (size_t)np * 2);
-  float4 v[ZK_LN_MAXP / 2];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < ZK_LN_MAXP / 2; ++i) {
-    if (2 * i < np) { v[i] = p[i]; s += v[i].x + v[i].z; }
-  }
-  mu = s * invh;
-  float m2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < ZK_LN_MAXP / 2; ++i) {
-    if (2 * i < np) {
-      const float d0 = v[i].x * (1.f / 64.f) - mu, d1 = v[i].z * (1.f / 64.f) - mu;
-      m2 += v[i].y + v[i].w + 64.f * (d0 * d0 + d1 * d1);
-    }
-  }
-  rs = rsqrtf(m2 * invh + eps);
-}
-// the same for a row the whole WAVE works on: lane i < np loads partial i (one coalesced load instead of np/2 wave-wide
+// (mu, rstd) of row `row` from its per-64-column partials {sum, M2} (Chan's combination, robust for |mean| >> sigma) for a
+// row the whole WAVE works on: lane i < np loads partial i (one coalesced load instead of np/2 wave-wide
 // broadcast loads, each of which costs the address path as much as a full row), two 16-lane DPP reductions
 __device__ __forceinline__ void zk_ln_row_stats_wave(const float* __restrict__ part, int np, float invh, float eps, size_t row,
                                                      int lane, float& mu, float& rs) {

@@ -21,7 +21,6 @@
 #include "zk_common.h"
 
 #include "zk_gemm.h"
-#include "zk_prog.h"
 
 // ------------------------------------------------------------------ reference kernel
 // one thread per output element; any shape / alignment.  Used for parity checks of the
@@ -298,11 +297,6 @@ int zk_gemm_dlds_sync_ln_dispatch(const bf16_t* A, const bf16_t* B, int M, int N
                                   const GemmEpi& e, hipStream_t stream);
 int zk_gemm_dlds_sync_ln_bwd_dispatch(const bf16_t* A, const bf16_t* B, int M, int N, int K, int lda, int ldb,
                                       const GemmEpi& e, hipStream_t stream);
-#ifdef ZK_EXPERIMENTS
-int zk_ffn_pair_launch(const bf16_t* x, const bf16_t* W1, bf16_t* h, const bf16_t* W2, float* parts, int M, int F, int H, int K1,
-                       int ldx, int ldw1, int ldw2, int kchunk, int nparts, const GemmEpi& e1, const GemmEpi& e2,
-                       unsigned long long* cnt, int* err, hipStream_t stream);
-#endif
 int zk_gemm_dlds_dispatch(const bf16_t* A, const bf16_t* B, int M, int N, int K, int lda, int ldb, int ta, int tb,
                           int bm, int bn, int splits, int kchunk, float* slabs, const GemmEpi& e, int sched_flags,
                           hipStream_t stream);
@@ -369,8 +363,6 @@ int zk_gemm(const void* A, const void* B, void* C, int M, int N, int K, int lda,
   const bool ok = mfma_ok(A, B, M, N, K, lda, ldb, ta, tb);
   ZK_CHECK_ARG(impl != 2 || ok, "zk_gemm: shape/alignment not supported by the MFMA kernel "
                "(M=%d N=%d K=%d lda=%d ldb=%d ta=%d tb=%d)", M, N, K, lda, ldb, ta, tb);
-  if (zk_prog_active() && (impl == 1 || (impl == 0 && !ok)))
-    return zk_prog_reject("gemm on the reference kernel");
   if (impl == 1 || (impl == 0 && !ok)) {
     const size_t n = (size_t)M * N;
     hipLaunchKernelGGL(k_gemm_naive, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)A,
@@ -389,10 +381,6 @@ int zk_gemm(const void* A, const void* B, void* C, int M, int N, int K, int lda,
   }
   if (split_ovr && plain) splits = split_ovr;
   if (splits > 1 && ws_bytes < (size_t)splits * M * N * sizeof(float)) splits = 1;
-  if (zk_prog_active()) {
-    if (gen != 2 || splits > 1 || wide) return zk_prog_reject("gemm variant (generation / split-K / wide tile) not available in the layer program");
-    return zk_prog_record_gemm((const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, ta, tb, bm, bn, e);
-  }
   int kchunk = K;
   float* slabs = nullptr;
   if (splits > 1) {
@@ -418,57 +406,6 @@ int zk_gemm(const void* A, const void* B, void* C, int M, int N, int K, int lda,
   }
   return 0;
 }
-
-#ifdef ZK_EXPERIMENTS   // measured: no gain over the LayerNorm launches (profiles/r04_negative_results.txt): make EXPERIMENTS=1
-// Forward linear with the residual + LayerNorm of the sub-layer folded into GEMM epilogues (GemmEpi, round 4): no
-// LayerNorm launch.  C bf16 [M, ldc] = epilogue(A [M, K] x B [K, N]), ta = tb = 0, gen-2 tile kernels only.
-//   stat_out  != NULL  PRODUCER: C is the un-normalised sum  residual + dropout(A B + bias)  and stat_out [M][N/64][2]
-//                      receives {sum, M2} of each (row, 64-column group) of the stored bf16 values;
-//   res_part  != NULL  the residual operand is itself an un-normalised sum: residual <- bf16(LN(residual)) with the
-//                      statistics res_part [M][np][2] and res_gamma / res_beta [N];
-//   in_c      != NULL  CONSUMER: A is an un-normalised sum with statistics in_part [M][np][2] (np = K / 64), B the weight
-//                      with gamma folded in and in_c / bias the vectors zk_ln_fold made:
-//                      C = act(rstd (A B - mu in_c) + bias), then dropout.
-int zk_gemm_ln(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, const float* bias,
-               const void* residual, int ldr, int act, float drop_p, const uint64_t* seed, uint32_t sid, float* stat_out,
-               const float* in_part, const float* in_c, const float* res_part, const float* res_gamma,
-               const float* res_beta, int np, float eps, hipStream_t stream) {
-  ZK_CHECK_ARG(M >= 0 && N >= 1 && K >= 1, "zk_gemm_ln: bad dims");
-  ZK_CHECK_ARG(act == 0 || act == 1, "zk_gemm_ln: act=%d (0 none, 1 ReLU)", act);
-  ZK_CHECK_ARG(drop_p == 0.f || seed != nullptr, "zk_gemm_ln: dropout needs a seed pointer");
-  ZK_CHECK_ARG(N % 64 == 0 && ldc % 8 == 0 && (residual == nullptr || ldr % 8 == 0), "zk_gemm_ln: N=%d must be a multiple of 64, ldc / ldr of 8", N);
-  ZK_CHECK_ARG(np >= 2 && np <= ZK_LN_MAXP && np % 2 == 0, "zk_gemm_ln: np=%d partials per row (even, 2..%d)", np, ZK_LN_MAXP);
-  ZK_CHECK_ARG(stat_out == nullptr || N == np * 64, "zk_gemm_ln: a producer writes N/64 = np partials per row");
-  ZK_CHECK_ARG((in_c == nullptr) == (in_part == nullptr), "zk_gemm_ln: in_part and in_c come together");
-  ZK_CHECK_ARG(in_c == nullptr || (stat_out == nullptr && res_part == nullptr && residual == nullptr),
-               "zk_gemm_ln: a GEMM is a consumer or a producer, not both");
-  ZK_CHECK_ARG(in_c == nullptr || (K == np * 64 && bias != nullptr), "zk_gemm_ln: a consumer needs K = 64 np and the folded bias");
-  ZK_CHECK_ARG(res_part == nullptr || (residual != nullptr && res_gamma != nullptr && res_beta != nullptr && N == np * 64),
-               "zk_gemm_ln: a lazy residual needs the sum, gamma, beta and N = 64 np");
-  const uintptr_t al = (uintptr_t)C | (uintptr_t)bias | (uintptr_t)residual | (uintptr_t)stat_out | (uintptr_t)in_part |
-                       (uintptr_t)in_c | (uintptr_t)res_part | (uintptr_t)res_gamma | (uintptr_t)res_beta;
-  ZK_CHECK_ARG((al & 15) == 0, "zk_gemm_ln: operands must be 16-byte aligned");
-  ZK_CHECK_ARG(mfma_ok(A, B, M, N, K, lda, ldb, 0, 0), "zk_gemm_ln: shape/alignment not supported by the MFMA kernel "
-               "(M=%d N=%d K=%d lda=%d ldb=%d)", M, N, K, lda, ldb);
-  ZK_CHECK_ARG(!zk_prog_active(), "zk_gemm_ln cannot be part of a layer program");
-  if (M == 0) return 0;
-  GemmEpi e;
-  e.C = C; e.ldc = ldc; e.out_f32 = 0; e.alpha = 1.f; e.bias = bias;
-  e.res = (const bf16_t*)residual; e.ldr = ldr; e.act = act; e.aux = nullptr; e.ldaux = 0; e.aux_scale = 1.f;
-  e.thr = drop_p > 0.f ? zk_drop_threshold(drop_p) : 0;
-  e.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-  e.seed = seed; e.sid = sid;
-  e.ln_stat_out = stat_out; e.ln_in_part = in_part; e.ln_c = in_c;
-  e.res_part = res_part; e.res_gamma = res_gamma; e.res_beta = res_beta;
-  e.ln_np = np; e.res_after_drop = 1; e.ln_eps = eps; e.ln_invh = 1.f / (float)(np * 64);
-  int bm, bn, splits;
-  pick_config(M, N, K, 0, &bm, &bn, &splits);
-  (void)splits;                 // never split: the epilogue needs the whole sum
-  if (bm > 128 || bn > 128) { bm = 128; bn = 128; }
-  return zk_gemm_dlds_ln_dispatch((const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, bm, bn, e, stream);
-}
-
-#endif  // ZK_EXPERIMENTS
 
 // The tail of a post-LN sub-layer in ONE launch (func.py:321-324 residual_fn, func.py:289-303 layer_norm, the order of
 // transformer.py:57-58):   s = residual + dropout(bf16(A B + bias));   y = LN(s) = gamma (s - mu) rstd + beta.
@@ -507,7 +444,6 @@ int zk_gemm_add_ln(const void* A, const void* B, int M, int N, int K, int lda, i
   ZK_CHECK_ARG((al & 15) == 0, "zk_gemm_add_ln: operands must be 16-byte aligned");
   ZK_CHECK_ARG(mfma_ok(A, B, M, N, K, lda, ldb, 0, 0), "zk_gemm_add_ln: shape/alignment not supported by the MFMA kernel "
                "(M=%d N=%d K=%d lda=%d ldb=%d)", M, N, K, lda, ldb);
-  ZK_CHECK_ARG(!zk_prog_active(), "zk_gemm_add_ln cannot be part of a layer program");
   if (M == 0) return 0;
   GemmEpi e;
   e.C = s_out; e.ldc = N; e.out_f32 = 0; e.alpha = 1.f; e.bias = bias;
@@ -552,7 +488,6 @@ int zk_gemm_ln_bwd(const void* dY, const void* W, int M, int N, int K, int lda, 
   ZK_CHECK_ARG((al & 15) == 0, "zk_gemm_ln_bwd: operands must be 16-byte aligned");
   ZK_CHECK_ARG(mfma_ok(dY, W, M, N, K, lda, ldb, 0, 1), "zk_gemm_ln_bwd: shape/alignment not supported by the MFMA kernel "
                "(M=%d N=%d K=%d lda=%d ldb=%d)", M, N, K, lda, ldb);
-  ZK_CHECK_ARG(!zk_prog_active(), "zk_gemm_ln_bwd cannot be part of a layer program");
   if (M == 0) return 0;
   GemmEpi e;
   e.C = nullptr; e.ldc = N; e.out_f32 = 0; e.alpha = 1.f; e.bias = nullptr;
@@ -580,7 +515,6 @@ int zk_gemm_parts(const void* A, const void* B, float* parts, int M, int N, int 
   ZK_CHECK_ARG(parts != nullptr && nparts_out != nullptr, "zk_gemm_parts: parts and nparts_out are required");
   ZK_CHECK_ARG(mfma_ok(A, B, M, N, K, lda, ldb, ta, tb), "zk_gemm_parts: shape/alignment not supported by the MFMA kernel "
                "(M=%d N=%d K=%d lda=%d ldb=%d ta=%d tb=%d)", M, N, K, lda, ldb, ta, tb);
-  ZK_CHECK_ARG(!zk_prog_active(), "zk_gemm_parts cannot be part of a layer program");
   int kchunk = ((K + splits - 1) / splits + BK - 1) / BK * BK;
   const int n = (K + kchunk - 1) / kchunk;
   *nparts_out = n;
@@ -597,38 +531,5 @@ int zk_gemm_parts(const void* A, const void* B, float* parts, int M, int N, int 
   return zk_gemm_dlds_dispatch((const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, ta, tb, 64, 64, n, kchunk, parts, e, 0,
                                stream);
 }
-
-#ifdef ZK_EXPERIMENTS   // measured: slower than the two launches (profiles/r04_negative_results.txt item 9)
-// The two products of a feed-forward sub-layer on few rows in one launch (see k_ffn_pair, zk_gemm2.hip):
-//   h = relu(x W1 + b1)  (bf16 [M, F], written: ldh = F),   parts[z] = h[:, K_z] W2[K_z, :]  (fp32 [M, H] at parts + z M H)
-// for the z-th of *nparts_out <= splits K ranges (multiples of 64) -- exactly what zk_gemm(act = 1) followed by zk_gemm_parts
-// leaves (same tile function, same K order).  x [M, ldx] (K1 = the model width contiguous), W1 [K1, ldw1], W2 [F, ldw2].
-// counter: a zeroed device uint64 that only calls with the same (ceil(M/64), F) may share (the barrier's arrival count);
-// *err (device int, may be null) is set if a workgroup gave up waiting.  Returns 2 without launching when the shape is not
-// covered (more workgroups than are resident at once, or fewer phase-1 than phase-2 tiles): call the two entry points.
-int zk_ffn_pair(const void* x, const void* W1, const float* b1, void* h, const void* W2, float* parts, int M, int F, int H, int K1,
-                int ldx, int ldw1, int ldw2, int splits, int* nparts_out, void* counter, int* err, hipStream_t stream) {
-  ZK_CHECK_ARG(M >= 1 && F >= 64 && H >= 64 && K1 >= 64 && splits >= 2 && splits <= 64, "zk_ffn_pair: bad sizes");
-  ZK_CHECK_ARG(h != nullptr && parts != nullptr && nparts_out != nullptr && counter != nullptr, "zk_ffn_pair: h, parts, nparts_out and counter are required");
-  if (F % 64 != 0 || H % 64 != 0 || K1 % 64 != 0) return 2;
-  if (!mfma_ok(x, W1, M, F, K1, ldx, ldw1, 0, 0) || !mfma_ok(h, W2, M, H, F, F, ldw2, 0, 0) || zk_prog_active()) return 2;
-  if ((((uintptr_t)b1 | (uintptr_t)h | (uintptr_t)parts | (uintptr_t)counter) & 15) != 0) return 2;
-  const int kchunk = ((F + splits - 1) / splits + BK - 1) / BK * BK;
-  const int n = (F + kchunk - 1) / kchunk;
-  const int tiles_m = (M + 63) / 64, T1 = tiles_m * (F / 64), T2 = tiles_m * (H / 64) * n;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 2;
-  if (n < 2 || T2 > T1 || T1 > 2 * cus) return 2;               // every workgroup must be resident while it waits
-  *nparts_out = n;
-  GemmEpi e1, e2;
-  e1.C = h; e1.ldc = F; e1.out_f32 = 0; e1.alpha = 1.f; e1.bias = b1; e1.res = nullptr; e1.ldr = 0; e1.act = 1;
-  e1.aux = nullptr; e1.ldaux = 0; e1.aux_scale = 1.f; e1.thr = 0; e1.inv_keep = 1.f; e1.seed = nullptr; e1.sid = 0;
-  e2.C = nullptr; e2.ldc = H; e2.out_f32 = 1; e2.alpha = 1.f; e2.bias = nullptr; e2.res = nullptr; e2.ldr = 0; e2.act = 0;
-  e2.aux = nullptr; e2.ldaux = 0; e2.aux_scale = 1.f; e2.thr = 0; e2.inv_keep = 1.f; e2.seed = nullptr; e2.sid = 0;
-  return zk_ffn_pair_launch((const bf16_t*)x, (const bf16_t*)W1, (bf16_t*)h, (const bf16_t*)W2, parts, M, F, H, K1, ldx, ldw1, ldw2,
-                            kchunk, n, e1, e2, (unsigned long long*)counter, err, stream);
-}
-
-#endif  // ZK_EXPERIMENTS
 
 }  // extern "C"

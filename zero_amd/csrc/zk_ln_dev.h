@@ -1,5 +1,5 @@
-// zk_ln_dev.h -- residual add + LayerNorm forward of ONE row by one wave (func.py:289-303, 321-324); shared by
-// k_add_ln_fwd (zk_elem.hip) and the layer program (zk_layer.hip).
+// zk_ln_dev.h -- residual add + LayerNorm forward of ONE row by one wave (func.py:289-303, 321-324), used by
+// k_add_ln_fwd (zk_elem.hip).
 #pragma once
 #include "zk_common.h"
 

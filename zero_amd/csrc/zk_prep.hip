@@ -259,67 +259,6 @@ __global__ void __launch_bounds__(NT) k_batch_prep(PrepArgs a) {
   }
 }
 
-#ifdef ZK_EXPERIMENTS
-// =====================================================================================
-// zk_ln_fold -- what the step derives from the PARAMETERS alone for the LayerNorm-free forward (GemmEpi, zk_gemm_ln):
-// for every linear layer whose input is LN(s) (qkv_map, q_map, ffn enlarge; func.py:289-303 feeding func.py:14-65)
-//     LN(s) W + b = rstd (s (gamma o W) - mu colsum(gamma o W)) + (beta W + b)
-// so the consumer GEMM reads the un-normalised sum s against  Wf = bf16(gamma_k W_kn)  and finishes in its epilogue
-// with  c_n = sum_k Wf_kn  (of the ROUNDED values: it must cancel the mean of exactly what the MFMAs multiplied) and
-// d_n = sum_k beta_k W_kn + b_n.  W is the fp32 master.  One launch for all layers at the head of the step; a block =
-// 64 columns of one weight, 32 row lanes x 8 column groups, K / 32 rows per lane.  HBM: 6 B per weight element.
-// =====================================================================================
-struct FoldDesc {
-  const float* W; const float* gamma; const float* beta; const float* b;
-  bf16_t* Wf; float* c; float* d;
-  int K, N, block_start, pad;
-};
-
-__global__ void __launch_bounds__(256) k_ln_fold(const FoldDesc* __restrict__ descs, int nprob) {
-  __shared__ float red[2][32][64 + 1];
-  const int bid = blockIdx.x;
-  int p = 0;
-  {
-    int hi = nprob - 1;
-    while (p < hi) {
-      const int mid = (p + hi + 1) >> 1;
-      if (descs[mid].block_start <= bid) p = mid; else hi = mid - 1;
-    }
-  }
-  const FoldDesc d = descs[p];
-  const int n0 = (bid - d.block_start) * 64;
-  const int tid = threadIdx.x, cg = tid & 7, rl = tid >> 3;
-  const int col = n0 + cg * 8;
-  float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, ds[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int k = rl; k < d.K; k += 32) {
-    const float4 a = *reinterpret_cast<const float4*>(d.W + (size_t)k * d.N + col);
-    const float4 b = *reinterpret_cast<const float4*>(d.W + (size_t)k * d.N + col + 4);
-    const float w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    const float g = d.gamma[k], bt = d.beta[k];
-    float wf[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) wf[j] = g * w[j];
-    const uint4 pk = pack8(wf);
-    *reinterpret_cast<uint4*>(d.Wf + (size_t)k * d.N + col) = pk;
-    unpack8(pk, wf);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { cs[j] += wf[j]; ds[j] += bt * w[j]; }
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { red[0][rl][cg * 8 + j] = cs[j]; red[1][rl][cg * 8 + j] = ds[j]; }
-  __syncthreads();
-  if (tid < 128) {
-    const int q = tid >> 6, n = tid & 63;
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) t += red[q][i][n];
-    if (q == 0) d.c[n0 + n] = t;
-    else d.d[n0 + n] = t + (d.b != nullptr ? d.b[n0 + n] : 0.f);
-  }
-}
-
-#endif  // ZK_EXPERIMENTS
-
 // =====================================================================================
 // zk_copy_many -- up to 16 small device-to-device copies in ONE launch: the id-dependent arrays of the NEXT batch, which
 // a side stream uploaded and prepared (zk_batch_prep) into staging buffers while the previous step was still running,
@@ -494,15 +433,4 @@ int zk_graph_set_copy_many(void* exec, void* const* dsts, const void* const* src
   return 0;
 }
 
-#ifdef ZK_EXPERIMENTS   // the LayerNorm-free forward: measured, no gain (profiles/r04_negative_results.txt)
-// descs: DEVICE array of nprob FoldDesc (64 bytes: W, gamma, beta, b, Wf, c, d pointers; K, N, block_start = running sum
-// of N / 64, pad); total_blocks = that sum.  N % 64 == 0, 16-byte aligned rows.
-int zk_ln_fold(const void* descs, int nprob, int total_blocks, hipStream_t stream) {
-  if (nprob == 0 || total_blocks == 0) return 0;
-  ZK_CHECK_ARG(descs != nullptr && nprob > 0 && total_blocks > 0, "zk_ln_fold: bad arguments");
-  hipLaunchKernelGGL(k_ln_fold, dim3(total_blocks), dim3(256), 0, stream, (const FoldDesc*)descs, nprob);
-  ZK_LAUNCH_CHECK();
-  return 0;
-}
-#endif  // ZK_EXPERIMENTS
 }  // extern "C"

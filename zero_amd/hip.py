@@ -42,13 +42,10 @@ def _ctype_of(decl):
     raise ValueError("unknown C type in %r" % decl)
 
 
-def parse_header(path=HEADER_PATH, experiments=True):
-    """-> {name: (restype, [argtypes], [argnames])} for every prototype.  experiments=False leaves out the
-    ``#ifdef ZK_EXPERIMENTS`` sections (entry points only a ``make EXPERIMENTS=1`` library exports)."""
+def parse_header(path=HEADER_PATH):
+    """-> {name: (restype, [argtypes], [argnames])} for every prototype."""
     text = open(path).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    if not experiments:
-        text = re.sub(r"#ifdef ZK_EXPERIMENTS.*?#endif", " ", text, flags=re.S)
     protos = {}
     for m in re.finditer(r"(const char\*|size_t|uint32_t|int)\s+(zk_\w+)\s*\(([^)]*)\)\s*;", text):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
@@ -71,6 +68,10 @@ def parse_header(path=HEADER_PATH, experiments=True):
 
 
 class _Lib(object):
+    # No build of the library has experiment entry points any more.  The flag stays, always False, so that callers
+    # written against versions that had them (tests that skip themselves without them) still skip instead of failing.
+    experiments = False
+
     def __init__(self):
         if not os.path.exists(LIB_PATH):
             raise ZeroHipError(
@@ -78,12 +79,7 @@ class _Lib(object):
                 "or `make -C zero_amd/csrc`). There is no CPU fallback." % LIB_PATH)
         self._dll = ctypes.CDLL(LIB_PATH)
         self.ncalls = 0
-        self.recording = False        # a layer program is being recorded (func.Engine.run_program)
-        core = parse_header(experiments=False)
-        every = parse_header(experiments=True)
-        # the experiment entry points (negative results kept as evidence, `make EXPERIMENTS=1`) come as a set
-        self.experiments = all(hasattr(self._dll, n) for n in every if n not in core)
-        self.protos = every if self.experiments else core
+        self.protos = parse_header()
         for name, (restype, argtypes, _) in self.protos.items():
             try:
                 fn = getattr(self._dll, name)
@@ -97,14 +93,8 @@ class _Lib(object):
     def raw(self, name):
         return getattr(self._dll, name)
 
-    # entry points that append an op while a layer program is being recorded (include/zero_hip.h, zk_prog_*)
-    RECORDABLE = frozenset(["zk_gemm", "zk_attn_fwd", "zk_attn_bwd", "zk_add_ln_fwd", "zk_prog_begin", "zk_prog_end"])
-
     def call(self, name, *args):
         """Call an int-returning entry point; raise on a non-zero status."""
-        if self.recording and name not in self.RECORDABLE:
-            # it would launch immediately, ahead of the ops recorded before it
-            raise ZeroHipError("%s cannot be part of a layer program" % name)
         self.ncalls += 1          # lets callers tell whether anything was enqueued between two points
         rc = getattr(self._dll, name)(*args)
         if rc != 0:

@@ -78,20 +78,7 @@ class Trainer(object):
         self.overlap_update = _os.environ.get("ZERO_HIP_OVERLAP_UPDATE", "1") != "0"
         # pad both sides of a batch to a multiple of this many positions (1 = the reference's exact shapes); see prepare_static
         self.pad_len = max(1, int(_os.environ.get("ZERO_HIP_PAD_LEN", "1")))
-        # one rank: update the decoder-side parameters on a side stream while the encoder backward still runs
-        # (the Adam pass is HBM-bound, the backward chain latency-bound: they overlap well); needs the norm-free
-        # update (no clipping / safe_nan), see _train_and_update
-        # measured on MI355X (bench.py, same box): 5.01 ms with the overlap, 4.94 ms without -- the streaming Adam
-        # blocks take HBM bandwidth and wave slots from the latency-bound chain they run beside, and the fork / join
-        # edges of the graph cost the rest -- so it is opt-in
-        # (an experiment: needs a `make EXPERIMENTS=1` library for zk_adam_range / zk_adam_finish)
-        self.overlap_adam = _os.environ.get("ZERO_HIP_OVERLAP_ADAM", "0") != "0" and self.core.eng.lib.experiments
-        self._adam_stream = None
         self._empty_ids = None
-        # the update of the weight matrices inside the weight-gradient launch (zk_gemm_grouped_update; _can_fuse_update):
-        # MEASURED SLOWER (profiles/r04_negative_results.txt: the launch 500 -> 794 us for 255 us less in the Adam pass)
-        # -> an experiment: `make EXPERIMENTS=1` library + ZERO_HIP_FUSED_UPDATE=1
-        self.fuse_update = _os.environ.get("ZERO_HIP_FUSED_UPDATE", "0") == "1" and self.core.eng.lib.experiments
         self.reseed()
 
     # -- row-sparse exchange of lookup-table gradients (utils/parallel.py:142-181) -----------------
@@ -137,13 +124,6 @@ class Trainer(object):
         micro = (self.global_step * max(1, int(hp.update_cycle)) + self.cycle_counter) & 0xFFFFFFFF
         self.core.eng.set_seed((hi << 32) | micro)
 
-    def _can_fuse_update(self):
-        """One rank, no accumulation, an update that does not look at the global norm (cycle.py:98-101 with the recipe's
-        clip_grad_norm = 0.0 and no safe_nan), all weight gradients in the backward's single deferred launch."""
-        return self.fuse_update and parallel.world_size() == 1 and not self.force_segmented and \
-            self.params.update_cycle == 1 and self.train_op.can_update_by_range() and self.core.group_all and \
-            not self.overlap_adam and not self.core.use_side
-
     def rollback_skipped_update(self):
         """main.py:320-332 (safe_nan): a skipped update does not run train_op, so global_step, Adam's t and the
         learning-rate schedule do not advance."""
@@ -167,23 +147,7 @@ class Trainer(object):
             if "B" not in features and features["source"].shape[0] > 0:
                 features = self.core.upload(features["source"], features["target"])
             self._declare_sparse(features if "B" in features else None)
-        fuse = last and hp.update_cycle == 1 and self._can_fuse_update()
-        if fuse:
-            # the weight-gradient launch runs the update of the weights itself: the scalars of this update first
-            self.train_op.count = 0
-            scale = self.train_op.set_hyper(self.lr.get_lr(), world)
-            self.core.fused_update = self.train_op.fused_ctx()
-        self.core.fused_info = None
-        try:
-            loss, _ = tower_train_graph(features, self.graph, hp, self.reducer if overlap else None)
-        finally:
-            self.core.fused_update = None
-        if fuse:
-            self.train_op.launch_update(scale, fused=self.core.fused_info)
-            self.store.step += 1
-            self.cycle_counter = 0
-            self.global_step += 1
-            return loss
+        loss, _ = tower_train_graph(features, self.graph, hp, self.reducer if overlap else None)
         if not last:
             self.train_op.collect()
             self.cycle_counter += 1
@@ -215,7 +179,7 @@ class Trainer(object):
         """One micro step on ``features`` (update on the last one of a cycle), replaying a captured
         hipGraph per batch shape.  Same arithmetic and bookkeeping as :meth:`micro_step`."""
         hp = self.params
-        if not use_graph or features["source"].shape[0] == 0 or self.core.use_side:
+        if not use_graph or features["source"].shape[0] == 0:
             return self.micro_step(features)
         if hp.update_cycle == 1 and self.pad_len == 1:
             # The batch is uploaded (asynchronous copies through pinned slots) and prepared (zk_batch_prep: masks, loss
@@ -300,11 +264,11 @@ class Trainer(object):
         FIRST NODE of the step's graph -- one submission per step, as for a static replay -- and its arguments are
         rewritten in the instantiated graph before every launch (zk_graph_set_copy_many; the graphs with that node are
         keyed ("stg", B, Ls, Lt), apart from the ones step_static() captures for the same shape).  Everything else (first
-        sight of a shape, several ranks, the side-stream variants): the commit launch in front, then _step_static().
+        sight of a shape, several ranks): the commit launch in front, then _step_static().
         Either way the commit also copies the step's sequence number into the pinned word step() polls."""
         eng = self.core.eng
         extra = self.train_op.hyper_pairs(hstage) + [(self._commit_reached.view(torch.float32), hstage[11:12])]
-        fast = parallel.world_size() == 1 and not self.force_segmented and not self.core.use_side and \
+        fast = parallel.world_size() == 1 and not self.force_segmented and \
             os.environ.get("ZERO_HIP_COMMIT_IN_GRAPH", "1") != "0"
         key = ("stg", staged["B"], staged["Ls"], staged.get("Lt", 0))
         self._check_graph_cache()
@@ -493,71 +457,9 @@ class Trainer(object):
             return plan
 
     def _train_and_update(self, scale):
-        """Single rank, update_cycle == 1: forward + backward + update.  With a norm-free update (cycle.py:98-101,
-        clip_grad_norm 0.0, no safe_nan) the parameters whose gradients are final -- the whole decoder side and the
-        target / softmax embedding once the decoder backward is through -- are updated on a side stream beside the
-        encoder backward; the rest follows on the main stream; the norms come out of the same passes
-        (zk_adam_range slots -> zk_adam_finish).  Same arithmetic per element as the single launch."""
-        hp, top, core = self.params, self.train_op, self.core
-        if not (self.overlap_adam and top.can_update_by_range() and not core.use_side):
-            core.fused_update = top.fused_ctx() if self._can_fuse_update() else None
-            core.fused_info = None
-            try:
-                self.graph.train_fn(self.batch, hp)
-            finally:
-                core.fused_update = None
-            top.launch_update(scale, fused=core.fused_info)
-            return
-        eng = core.eng
-        main = torch.cuda.current_stream(eng.device)
-        if self._adam_stream is None:
-            self._adam_stream = torch.cuda.Stream(eng.device)
-        side = self._adam_stream
-        ranges = self.reducer.ranges
-        early = set(k for k in ranges if k.startswith("decoder/"))
-        if core.soft_emb != core.src_emb:
-            early.add(core.soft_emb)
-            if core.tgt_emb != core.src_emb:
-                early.add(core.tgt_emb)
-        state = {"slots": 0, "forked": False, "seen": set(), "pend": []}
-
-        def launch(rs):
-            rs = sorted(rs)
-            merged = []
-            for lo, hi in rs:
-                if merged and merged[-1][1] == lo:
-                    merged[-1][1] = hi
-                else:
-                    merged.append([lo, hi])
-            for lo, hi in merged:
-                top.launch_update_slot(lo, hi, state["slots"])
-                state["slots"] += 1
-            return sum(hi - lo for lo, hi in merged)
-
-        covered = [0]
-
-        def ready(key):
-            if key in state["seen"]:
-                return
-            state["seen"].add(key)
-            state["pend"].append(ranges[key])
-            if not state["forked"] and early and early <= state["seen"]:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                side.wait_event(ev)
-                with torch.cuda.stream(side):
-                    covered[0] += launch(state["pend"])
-                state["pend"] = []
-                state["forked"] = True
-        self.graph.train_fn(self.batch, hp, on_ready=ready)
-        covered[0] += launch(state["pend"])
-        if covered[0] != self.store.numel:          # a variable group nobody reported: never leave it stale
-            raise RuntimeError("parameter ranges covered %d of %d elements" % (covered[0], self.store.numel))
-        if state["forked"]:
-            ev = torch.cuda.Event()
-            ev.record(side)
-            main.wait_event(ev)
-        top.finish_update_slots(state["slots"])
+        """Single rank, update_cycle == 1: forward + backward + update."""
+        self.graph.train_fn(self.batch, self.params)
+        self.train_op.launch_update(scale)
 
     # -- captured path (static shapes, update_cycle == 1) ---------------------------
     def prepare_static(self, features):
@@ -643,7 +545,7 @@ class Trainer(object):
                 g = eng.graph_capture(body)
                 self._graphs[key] = g
             eng.graph_launch(g)
-        elif use_graph and not self.core.use_side and (world > 1 or self.force_segmented):
+        elif use_graph and (world > 1 or self.force_segmented):
             self._step_segmented(scale)
         elif world > 1:
             self.graph.train_fn(self.batch, hp, on_ready=self.reducer.ready)

@@ -19,7 +19,6 @@ import os
 import numpy as np
 import torch
 
-from zero_amd import hip
 from zero_amd.func import Engine, Mat
 from zero_amd.variables import get_store
 
@@ -35,16 +34,6 @@ def trim_columns(ids):
     if keep.size:
         keep[0] = True
     return np.ascontiguousarray(ids[:, keep])
-
-
-class LazyLN(object):
-    """LN(s) that no kernel has written (round 4): the un-normalised sum ``s`` a producer GEMM left (zk_gemm_ln), its
-    per-64-column row statistics ``part`` and the LayerNorm scope whose gamma / beta apply.  Readers normalise where they
-    read: the consumer GEMM algebraically, the next residual on the fly, the backward from the same statistics."""
-    __slots__ = ("s", "part", "scope", "tag", "rows")
-
-    def __init__(self, s, part, scope, tag):
-        self.s, self.part, self.scope, self.tag, self.rows = s, part, scope, tag, s.rows
 
 
 class TransformerCore(object):
@@ -76,11 +65,6 @@ class TransformerCore(object):
             self.soft_emb = "tgt_embedding" if params.shared_target_softmax_embedding else "softmax_embedding"
         self.V = params.tgt_vocab.size()
         self.Vpad = self.store.pshape[self.soft_emb][0]
-        # weight-gradient GEMMs and bias column sums leave the critical path: they run on a second
-        # HIP stream, concurrently with the dgrad chain (both are latency-bound at this size)
-        # (measured in round 1: with one rank the second stream LOSES ~3 % -- cross-stream graph
-        # edges cost more than the overlap buys once the small GEMMs are grouped -- so it is opt-in)
-        self.use_side = os.environ.get("ZERO_HIP_SIDE_STREAM", "0") != "0" and self.eng.lib.experiments
         # weight-gradient GEMMs are deferred and launched as ONE grouped grid per `group_layers`
         # layers (each is far too small to fill 256 CUs on its own)
         self.group_wgrad = True
@@ -100,10 +84,8 @@ class TransformerCore(object):
         # ("256x256n": the LDS-DMA pieces of a K step issued right behind the barrier instead of spread between the MFMA
         # groups -- same-box A/B of the whole step: 4.708 ms spread, 4.673 ms not, 4.80 ms for the round-2 grouping)
         # (round 4: the measured-and-lost alternatives -- per-side groups, the spread DMA issue, 128x128 -- lost their
-        # switches; the 32-deep ring of the EXPERIMENTS build is selected with ZERO_HIP_WGRAD_TILE=256x256k32 there)
+        # switches)
         self.wgrad_tile = (256, 256, 0) if self.group_all else (128, 256)
-        if self.eng.lib.experiments and os.environ.get("ZERO_HIP_WGRAD_TILE", "").lower() == "256x256k32":
-            self.wgrad_tile = (256, 256, "k32")
         self._pending_wgrads = []
         self._pending_colsums = []     # (dY Mat, bias-gradient view, private partial buffer)
         self._pending_lnred = []       # (partials, rows, H, dgamma, dbeta, dbias_prev)
@@ -114,11 +96,6 @@ class TransformerCore(object):
         self._mem_segs = []            # (dK or dV, W) pairs of the cross-attention memory side (see _finish_mem_grad)
         # encoder-output gradient by one K-segmented GEMM (needs the MFMA path: H a multiple of 64, aligned rows)
         self.kseg_mem = True
-        # fused logits + cross entropy (no [T, V] fp32 logits in HBM, recompute in the backward): measured
-        # 224 + 8 us forward and 287 us backward against 291 + 208 us for GEMM + k_ce_fused -- the second
-        # pass over the 137-GFLOP GEMM costs what the saved 1 GB of traffic buys, so it is opt-in (it frees
-        # T*V*4 bytes, which matters for larger batches / vocabularies)
-        self.fused_ce = os.environ.get("ZERO_HIP_FUSED_CE", "0") != "0" and self.eng.lib.experiments
         self.logits_tile256 = True
         # the dgrad of the attention output projection inside the attention backward launch (zk_attn_bwd oproj_*): 18
         # launches and 18 [T, H] matrices less per step, same-box A/B -0.02 to -0.05 ms (the 64 x 64 x H product per
@@ -129,18 +106,6 @@ class TransformerCore(object):
         # of that kernel runs one workgroup per CU and the longer prologue is not hidden (5.21 -> 5.24 ms).
         self.attn_oproj = os.environ.get("ZERO_HIP_ATTN_OPROJ", "auto").lower()
         self._red_id = 0
-        self._side_stream = None      # created on first use: every stream of the process takes a share of the hardware queues
-        # Residual + LayerNorm without a launch of its own in the TRAINING forward (round 4): the
-        # o_map / ffn-output GEMM adds the residual and leaves the un-normalised sum + row statistics (zk_gemm_ln), the
-        # next linear reads the sum against gamma-folded weights (zk_ln_fold, one launch per step), the next residual
-        # normalises on the fly, and the LayerNorm backward -- which runs anyway -- writes the normalised rows for the
-        # deferred weight gradients.  28 of the 30 LayerNorm-forward launches of a Transformer-base step go (the two that
-        # end the encoder / decoder stacks keep their launch: their outputs feed grouped / 256-tile GEMMs).
-        # MEASURED (profiles/r04_negative_results.txt): parity holds at the BASELINE sizes, the step does NOT get
-        # faster (+0.03 to +0.09 ms) -- what the 28 launches did has to be done somewhere: the producer epilogues cost
-        # +2 us each, the LayerNorm backward +5..7 us for the normalised rows it now writes, the fold launch 42 us.  So it
-        # is an experiment: only in a `make EXPERIMENTS=1` library, only with ZERO_HIP_LAZY_LN=1.
-        self.lazy_ln_mode = os.environ.get("ZERO_HIP_LAZY_LN", "0").lower() if self.eng.lib.experiments else "0"
         self.sync_ln_mode = os.environ.get("ZERO_HIP_SYNC_LN", "1") != "0"
         # round 6: small launches of the step merged pairwise (both input embeddings; their two gradient scatters; the two
         # bias column sums; per-sentence loss + mean): ZERO_HIP_MERGE_SMALL=0 restores the round-5 launches (A/B, tests)
@@ -153,100 +118,28 @@ class TransformerCore(object):
         # round 6: the projection in front of the attention (merged qkv_map / q_map) as the prologue of that launch
         # (zk_proj_attn_out_ln); ZERO_HIP_PROJ_ATTN=0 keeps it a launch of its own (A/B, bit-identity tests)
         self.proj_attn = os.environ.get("ZERO_HIP_PROJ_ATTN", "1") != "0"
-        # the attention BACKWARD inside the dgrad launch: measured, no gain (EXPERIMENTS=1 library, ZERO_HIP_SYNC_LN=attnbwd)
-        self.sync_attn_bwd = os.environ.get("ZERO_HIP_SYNC_LN", "1") == "attnbwd" and self.eng.lib.experiments
         self._sync_ln = False
-        # The update of the weight matrices inside the weight-gradient launch (round 4; zk_gemm_grouped_update): set by the
-        # Trainer for a step whose update is norm-free, single-rank and unaccumulated; the backward's one grouped launch
-        # then runs TF1 Adam on its accumulators for every weight it can (see _flush_wgrads) and `fused_info` tells the
-        # optimiser what is left to do.
-        self.fused_update = None      # dict(master, m, v, shadow, grad, hyper) or None
-        self.fused_info = None        # (ranges, sq, n_extra) of the last backward, or None
-        self._lazy = False            # set per forward()
-        self._lazy_tags = {}          # tag -> LazyLN of this step's forward (read by the backward)
-
-    def _use_lazy_ln(self, train, save):
-        if self.lazy_ln_mode != "1" or not (train and save):
-            return False
-        ok = self.group_all and self.group_wgrad and self.eng.gemm_impl == 0 and not self.use_side and \
-            not self.aan and not self.fuse and self.H % 128 == 0 and self.H // 64 <= 16 and self.F % 64 == 0 and \
-            not self.eng.programs_enabled
-        if self.lazy_ln_mode == "1" and not ok:
-            raise hip.ZeroHipError("ZERO_HIP_LAZY_LN=1: the LayerNorm-free forward needs one rank (all weight gradients in "
-                                   "one deferred launch), the plain / rpr Transformer and H a multiple of 128 (<= 1024)")
-        return ok
-
-    def _lazy_pairs(self):
-        """[(linear scope, LayerNorm scope)]: every linear layer of the training forward whose input is the output of a
-        LayerNorm that is not materialised -- the weights zk_ln_fold prepares at the head of the step."""
-        hp, out = self.hp, []
-        for l in range(hp.num_encoder_layer):
-            pre = "encoder/layer_%d" % l
-            if l > 0:
-                out.append((pre + "/self_attention/dot_attention/qkv_map", "encoder/layer_%d/feed_forward" % (l - 1)))
-            out.append((pre + "/feed_forward/ffn_layer/enlarge", pre + "/self_attention"))
-        for l in range(hp.num_decoder_layer):
-            pre = "decoder/layer_%d" % l
-            if l > 0:
-                out.append((pre + "/self_attention/dot_attention/qkv_map", "decoder/layer_%d/feed_forward" % (l - 1)))
-            out.append((pre + "/%s/dot_attention/q_map" % self.cross, pre + "/self_attention"))
-            out.append((pre + "/feed_forward/ffn_layer/enlarge", pre + "/" + self.cross))
-        return out
-
-    def _fold_weights(self):
-        """zk_ln_fold for every pair of _lazy_pairs(): ONE launch at the head of the step (the fp32 masters changed in
-        the previous update)."""
-        e, st = self.eng, self.store
-        probs = []
-        for lin, ln in self._lazy_pairs():
-            W = st.w(lin + "/W_0_0")
-            K, N = W.shape
-            probs.append((W, st.w(ln + "/layer_norm/scale"), st.w(ln + "/layer_norm/offset"), st.w(lin + "/b_0"),
-                          e.mat("fold.W." + lin, K, N), e.buf("fold.c." + lin, (N,), F32), e.buf("fold.d." + lin, (N,), F32)))
-        e.ln_fold(probs)
 
     def _use_oproj(self, B):
         if self.attn_oproj in ("0", "1"):
             return self.attn_oproj == "1"
         return (not self.rpr) and self.H <= 512 and B * self.nh <= 512
 
-    @property
-    def side(self):
-        if self._side_stream is None and self.eng.device.type == "cuda":
-            self._side_stream = torch.cuda.Stream(self.eng.device)
-        return self._side_stream
-
-    # ------------------------------------------------------------------ stream plumbing
-    def _side(self, fn):
-        """Run fn() on the side stream, ordered after everything enqueued so far on the current one."""
-        if not self.use_side:
-            fn()
-            return
-        ev = torch.cuda.Event()
-        ev.record()
-        self.side.wait_event(ev)
-        with torch.cuda.stream(self.side):
-            fn()
-
     def _flush_wgrads(self):
-        """Launch every deferred weight-gradient GEMM as one grouped grid on the side stream."""
+        """Launch every deferred weight-gradient GEMM as one grouped grid."""
         if self._pending_wgrads:
             probs = self._pending_wgrads
             self._pending_wgrads = []
-            if self.fused_update is not None and self.group_all and self.wgrad_tile == (256, 256, 0) and \
-                    not self.use_side and self.eng.gemm_impl == 0 and self.fused_info is None and \
-                    not self._pending_adds:      # (a variable used twice gets a second contribution AFTER this launch)
-                self.fused_info = self.eng.gemm_grouped_update(probs, self.fused_update)
-            else:
-                self._side(lambda: self.eng.gemm_grouped([p[:9] for p in probs], 1, 0, tile=self.wgrad_tile))
+            self.eng.gemm_grouped(probs, 1, 0, tile=self.wgrad_tile)
         if self._pending_colsums or self._pending_lnred or self._pending_rpr:
             cs, ln, rp = self._pending_colsums, self._pending_lnred, self._pending_rpr
             self._pending_colsums, self._pending_lnred, self._pending_rpr = [], [], []
-            self._side(lambda: self.eng.reductions_grouped(cs, ln, rp))
+            self.eng.reductions_grouped(cs, ln, rp)
         if self._pending_adds:
             adds = self._pending_adds
             self._pending_adds = []
-            self._side(lambda: [self._accumulate(dst, src) for dst, src in adds])
+            for dst, src in adds:
+                self._accumulate(dst, src)
 
     def _defer_rpr(self):
         """Relative positions: the table-gradient partials of every attention layer summed by the grouped reduction
@@ -270,12 +163,6 @@ class TransformerCore(object):
         """dst += src (fp32 gradient views of equal size)."""
         self.eng.lib.call("zk_axpby_f32", dst.data_ptr(), src.data_ptr(), 1.0, 1.0, dst.numel(), self.eng.stream)
 
-    def _join_side(self):
-        if self.use_side:
-            ev = torch.cuda.Event()
-            ev.record(self.side)
-            torch.cuda.current_stream(self.eng.device).wait_event(ev)
-
     # ------------------------------------------------------------------ helpers
     def W(self, name):
         t = self.store.s(name)
@@ -292,15 +179,7 @@ class TransformerCore(object):
         return self.store.g(name)
 
     def _linear(self, x, scope, out, act=0, drop_p=0.0, sid=0):
-        """y = x @ W + b  (func.py:14-65).  x a LazyLN: y = LN(s) @ W + b from the un-normalised sum, the gamma-folded
-        weight and the row statistics (zk_gemm_ln consumer form)."""
-        if isinstance(x, LazyLN):
-            e = self.eng
-            K, N = self.store.pshape[scope + "/W_0_0"]
-            e.gemm_ln(x.s, e.mat("fold.W." + scope, K, N), out, x.rows, N, K, e.buf("fold.d." + scope, (N,), F32),
-                      self.H // 64, act=act, drop_p=drop_p, sid=sid, in_part=x.part,
-                      in_c=e.buf("fold.c." + scope, (N,), F32))
-            return
+        """y = x @ W + b  (func.py:14-65)."""
         Wm = self.W(scope + "/W_0_0")
         self.eng.gemm(x, Wm, out, x.rows, Wm.cols, Wm.rows, 0, 0, bias=self.b(scope + "/b_0"), act=act,
                       drop_p=drop_p, sid=sid)
@@ -324,20 +203,16 @@ class TransformerCore(object):
         # (256x256 tiles: by two extra MFMAs per eight on the fragments the tm = 0 tiles hold anyway)
         fold_cs = bias_grad and isinstance(self.wgrad_tile, tuple)
         if self.group_wgrad and self.eng.gemm_impl == 0:
-            # (10th element: the variable's gradient is complete with this product -> its update may run in the launch)
-            self._pending_wgrads.append((x, dy, gW, Wm.rows, Wm.cols, x.rows, None, None, gb if fold_cs else None,
-                                         not accumulate and not adds))
+            self._pending_wgrads.append((x, dy, gW, Wm.rows, Wm.cols, x.rows, None, None, gb if fold_cs else None))
             if bias_grad and not fold_cs:
                 gy = self.eng.lib.raw("zk_colsum_rowchunks")(dy.rows)
                 pw = self.eng.buf("g.cs%d" % len(self._pending_colsums) + scope, (gy * dy.cols,), F32)
                 self._pending_colsums.append((dy, gb, pw))
             self._pending_adds += adds
         else:
-            def wgrad():
-                self.eng.gemm(x, dy, gW, Wm.rows, Wm.cols, x.rows, 1, 0)
-                if bias_grad:
-                    self.eng.colsum(dy, gb)
-            self._side(wgrad)
+            self.eng.gemm(x, dy, gW, Wm.rows, Wm.cols, x.rows, 1, 0)
+            if bias_grad:
+                self.eng.colsum(dy, gb)
             # the overwriting use of the variable must already have run: callers issue it first
             self._pending_adds += adds
         if dx is not None:
@@ -348,31 +223,6 @@ class TransformerCore(object):
                 return
             self.eng.gemm(dy, Wm, dx, dy.rows, Wm.rows, Wm.cols, 0, 1, residual=residual, act=act, aux=aux,
                           aux_scale=aux_scale)
-
-    def _attn_bwd_ln(self, q, k, v, att, lse, dq, dk, dv, B, Lq, Lk, kmask, causal, attn_sid, oproj, dA, Wm, residual):
-        """attention backward + the dgrad of the projection in front of it + the LayerNorm backward below in one launch
-        (zk_attn_bwd_ln) when self._ln_next names that LayerNorm and the shape is covered; False otherwise (the caller
-        issues attn_bwd and the dgrad)."""
-        e, H, hp = self.eng, self.H, self.hp
-        if not (self._ln_next is not None and self.sync_attn_bwd and oproj is not None and not self.rpr and self.d == 64 and
-                Lq <= 64 and Lk <= 64 and e.attn_impl in (0, 2)):
-            return False
-        scope, tag, prev_bias, drop_p, sid = self._ln_next
-        T = B * Lq
-        ds = e.mat("g.%s.ds" % tag, T, H)
-        dyo = e.mat("g.%s.dy" % tag, T, H) if drop_p > 0.0 else None
-        nbytes = max(B * 3 * H * 4, e.lib.query("zk_gemm_ln_bwd_partials", T, H), e.lib.query("zk_add_ln_bwd_workspace", T, H))
-        pws = e.buf("g.%s.lnws" % tag, (nbytes // 4,), F32)
-        ok = e.attn_bwd_ln(q, k, v, att, lse, dq, dk, dv, B, self.nh, Lq, Lk, self.d, kmask, causal, hp.attention_dropout,
-                           attn_sid, oproj, dA, Wm, residual, e.mat(tag + ".s", T, H), e.buf(tag + ".mean", (T,), F32),
-                           e.buf(tag + ".rstd", (T,), F32), self.b(scope + "/layer_norm/scale"), ds, dyo, pws, drop_p, sid)
-        if not ok:
-            return False
-        dbp = self.gb(prev_bias) if prev_bias is not None else None
-        self._pending_lnred.append((pws, T, H, self.gb(scope + "/layer_norm/scale"), self.gb(scope + "/layer_norm/offset"),
-                                    dbp, B))
-        self._ln_bwd_done[tag] = (ds, dyo if dyo is not None else ds)
-        return True
 
     def _gemm_ln_bwd(self, dy, Wm, residual, ln_next):
         e, H = self.eng, self.H
@@ -390,46 +240,24 @@ class TransformerCore(object):
         self._ln_bwd_done[tag] = (ds, dyo if dyo is not None else ds)
 
     # ------------------------------------------------------------------ sub-layers (forward)
-    def _out_ln(self, a, lin, x, scope, tag, save, drop_p, sid, last=False):
-        """The tail of a sub-layer: LN(x + dropout(a @ W + b)) (func.py:321-324, 289-303; transformer.py:57-58).
-        Default: the GEMM, then the residual + LayerNorm launch.  With the LayerNorm-free forward (self._lazy) the GEMM
-        adds the residual itself -- normalising it on the fly when x is a LazyLN -- and leaves the un-normalised sum with
-        its row statistics; nothing normalises it here unless it ends a stack (last)."""
+    def _out_ln(self, a, lin, x, scope, tag, save, drop_p, sid):
+        """The tail of a sub-layer: LN(x + dropout(a @ W + b)) (func.py:321-324, 289-303; transformer.py:57-58): one
+        launch with the in-launch LayerNorm, else the GEMM, then the residual + LayerNorm launch."""
         e, H = self.eng, self.H
         T = a.rows
-        if not self._lazy:
-            if self._sync_ln and not e.lib.recording and self._sync_fits(T):
-                # one launch: the workgroups of a block of rows exchange their LayerNorm partials (zk_gemm_add_ln)
-                Wm = self.W(lin + "/W_0_0")
-                out = e.mat(tag + ".o", T, H)
-                s = e.mat(tag + ".s", T, H) if save else None
-                mean = e.buf(tag + ".mean", (T,), F32) if save else None
-                rstd = e.buf(tag + ".rstd", (T,), F32) if save else None
-                e.gemm_add_ln(a, Wm, T, H, Wm.rows, self.b(lin + "/b_0"), x, self.b(scope + "/layer_norm/scale"),
-                              self.b(scope + "/layer_norm/offset"), out, s, mean, rstd, drop_p, sid)
-                return out
-            y = e.mat("tmp.y%d" % T, T, H)
-            self._linear(a, lin, y)
-            return self._ln_fwd(x, y, scope, tag, save, drop_p, sid)
-        Wm = self.W(lin + "/W_0_0")
-        s = e.mat(tag + ".s", T, H)
-        part = e.buf(tag + ".part", (T, H // 64, 2), F32)
-        lazy_res = isinstance(x, LazyLN)
-        e.gemm_ln(a, Wm, s, T, H, Wm.rows, self.b(lin + "/b_0"), H // 64, residual=x.s if lazy_res else x,
-                  drop_p=drop_p, sid=sid, stat_out=part, res_part=x.part if lazy_res else None,
-                  res_gamma=self.b(x.scope + "/layer_norm/scale") if lazy_res else None,
-                  res_beta=self.b(x.scope + "/layer_norm/offset") if lazy_res else None)
-        if not last:
-            out = LazyLN(s, part, scope, tag)
-            self._lazy_tags[tag] = out
+        if self._sync_ln and self._sync_fits(T):
+            # one launch: the workgroups of a block of rows exchange their LayerNorm partials (zk_gemm_add_ln)
+            Wm = self.W(lin + "/W_0_0")
+            out = e.mat(tag + ".o", T, H)
+            s = e.mat(tag + ".s", T, H) if save else None
+            mean = e.buf(tag + ".mean", (T,), F32) if save else None
+            rstd = e.buf(tag + ".rstd", (T,), F32) if save else None
+            e.gemm_add_ln(a, Wm, T, H, Wm.rows, self.b(lin + "/b_0"), x, self.b(scope + "/layer_norm/scale"),
+                          self.b(scope + "/layer_norm/offset"), out, s, mean, rstd, drop_p, sid)
             return out
-        # end of a stack: the normalised rows feed grouped / 256-tile GEMMs -> one LayerNorm launch over the stored sum
-        # (its own statistics; the backward of this sub-layer is the ordinary one)
-        out = e.mat(tag + ".o", T, H)
-        e.add_ln_fwd(s, None, self.b(scope + "/layer_norm/scale"), self.b(scope + "/layer_norm/offset"), out, None,
-                     e.buf(tag + ".mean", (T,), F32), e.buf(tag + ".rstd", (T,), F32), 0.0, sid)
-        return out
-
+        y = e.mat("tmp.y%d" % T, T, H)
+        self._linear(a, lin, y)
+        return self._ln_fwd(x, y, scope, tag, save, drop_p, sid)
     def _sync_fits(self, rows):
         """The in-launch exchange pays while the launch is little more than ONE resident round of workgroups (two 64x64-tile
         workgroups per CU): a workgroup that waits for its peers keeps its slot, and with several rounds the waiting slots
@@ -440,7 +268,7 @@ class TransformerCore(object):
 
     def _attn_out_ln_ok(self, B, Lq, Lk):
         e = self.eng
-        return (self._sync_ln and self.sync_attn and not self.rpr and not e.lib.recording and self.d == 64 and
+        return (self._sync_ln and self.sync_attn and not self.rpr and self.d == 64 and
                 Lq <= 64 and Lk <= 256 and e.attn_impl in (0, 2) and B * self.nh <= 3 * e.cu_count)
 
     def _attn_out_ln(self, q, k, v, att, lse, B, Lq, Lk, kmask, causal, attn_drop, attn_sid, lin, x, scope, tag, save,
@@ -489,7 +317,7 @@ class TransformerCore(object):
         lse = e.buf(tag + ".lse", (B * self.nh * L,), F32) if save else None
         rk = self.store.s(p + "rpr_keys/embeddings") if self.rpr else None
         rv = self.store.s(p + "rpr_values/embeddings") if self.rpr else None
-        fuse_proj = self.proj_attn and not isinstance(x, LazyLN) and self._attn_out_ln_ok(B, L, L)
+        fuse_proj = self.proj_attn and self._attn_out_ln_ok(B, L, L)
         for pj in ((p + "qkv_map", 3), None) if fuse_proj else (None,):
             if pj is None:
                 self._linear(x, p + "qkv_map", qkv)
@@ -505,7 +333,7 @@ class TransformerCore(object):
 
     def _cross_kv_grouped(self, mem, n_layers):
         """k_map / v_map of EVERY decoder layer read only the encoder output (func.py:206-216): one
-        grouped GEMM on the side stream, overlapped with the first decoder sub-layer."""
+        grouped GEMM."""
         e, H = self.eng, self.H
         probs = []
         for l in range(n_layers):
@@ -514,7 +342,7 @@ class TransformerCore(object):
             for nm, c0 in (("k_map", 0), ("v_map", H)):
                 Wm = self.W(p + nm + "/W_0_0")
                 probs.append((mem, Wm, kv.cols_slice(c0, c0 + H), mem.rows, H, H, self.b(p + nm + "/b_0")))
-        self._side(lambda: e.gemm_grouped(probs, 0, 0))
+        e.gemm_grouped(probs, 0, 0)
 
     def _cross_attn_fwd(self, x, mem, B, Lq, Lk, scope, tag, kmask, save, sid0, train, kv_ready=False,
                         fuse_tmask=None):
@@ -522,8 +350,7 @@ class TransformerCore(object):
         hp = self.hp
         p = scope + "/dot_attention/"
         q = e.mat(tag + ".q", x.rows, H)
-        fuse_proj = (self.proj_attn and fuse_tmask is None and not isinstance(x, LazyLN) and
-                     self._attn_out_ln_ok(B, Lq, Lk))
+        fuse_proj = self.proj_attn and fuse_tmask is None and self._attn_out_ln_ok(B, Lq, Lk)
         if not fuse_proj:
             self._linear(x, p + "q_map", q)
         kv = e.mat(tag + ".kv", mem.rows, 2 * H)
@@ -555,14 +382,13 @@ class TransformerCore(object):
             att = atts
         return self._out_ln(att, p + "o_map", x, scope, tag, save, hp.residual_dropout if train else 0.0, sid0 + 1)
 
-    def _ffn_fwd(self, x, scope, tag, save, sid0, train, last=False):
+    def _ffn_fwd(self, x, scope, tag, save, sid0, train):
         e, H, F = self.eng, self.H, self.F
         hp = self.hp
         p = scope + "/ffn_layer/"
         h = e.mat(tag + ".h", x.rows, F)
         self._linear(x, p + "enlarge", h, act=1, drop_p=hp.relu_dropout if train else 0.0, sid=sid0)
-        return self._out_ln(h, p + "output", x, scope, tag, save, hp.residual_dropout if train else 0.0, sid0 + 1,
-                            last=last)
+        return self._out_ln(h, p + "output", x, scope, tag, save, hp.residual_dropout if train else 0.0, sid0 + 1)
 
     def _aan_fwd(self, x, B, L, scope, tag, tmask, save, sid0, train):
         e, H = self.eng, self.H
@@ -596,16 +422,7 @@ class TransformerCore(object):
         dy = e.mat("g.%s.dy" % tag, T, H) if drop_p > 0.0 else None
         dgam, dbet = self.gb(scope + "/layer_norm/scale"), self.gb(scope + "/layer_norm/offset")
         dbp = self.gb(prev_bias) if prev_bias is not None else None
-        lz = self._lazy_tags.get(tag)
-        if lz is not None:
-            # the LayerNorm the forward never launched: statistics from the producer GEMM's partials; the normalised rows
-            # (X operand of the consumer's deferred weight gradient) are written here, by the launch that runs anyway
-            nbytes = e.lib.query("zk_add_ln_bwd_workspace", T, H)
-            pws = e.buf("g.%s.lnws" % tag, (nbytes // 4,), F32)
-            e.add_ln_bwd_lazy(dx, lz.s, lz.part, self.b(scope + "/layer_norm/scale"), self.b(scope + "/layer_norm/offset"),
-                              e.mat(tag + ".o", T, H), ds, dy, dgam, dbet, dbp, drop_p, sid, private_ws=pws)
-            self._pending_lnred.append((pws, T, H, dgam, dbet, dbp))
-        elif self.group_wgrad and e.gemm_impl == 0:
+        if self.group_wgrad and e.gemm_impl == 0:
             # per-block partial sums go to a buffer private to this sub-layer; the column reduction
             # joins the grouped reduction launch of this layer group
             nbytes = e.lib.query("zk_add_ln_bwd_workspace", T, H)
@@ -648,12 +465,6 @@ class TransformerCore(object):
         dqkv = e.mat("g.%s.dqkv" % tag, T, 3 * H)
         rk = self.store.s(p + "rpr_keys/embeddings") if self.rpr else None
         rv = self.store.s(p + "rpr_values/embeddings") if self.rpr else None
-        if self._attn_bwd_ln(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att,
-                             e.buf(tag + ".lse", (B * self.nh * L,), F32), dqkv.cols_slice(0, H), dqkv.cols_slice(H, 2 * H),
-                             dqkv.cols_slice(2 * H, 3 * H), B, L, L, kmask, causal, sid0, oproj, dqkv,
-                             self.W(p + "qkv_map/W_0_0"), ds):
-            self._linear_bwd(x_in, dqkv, p + "qkv_map", dx=None)          # the weight gradient only
-            return dx_out
         e.attn_bwd(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, datt,
                    e.buf(tag + ".lse", (B * self.nh * L,), F32), dqkv.cols_slice(0, H), dqkv.cols_slice(H, 2 * H),
                    dqkv.cols_slice(2 * H, 3 * H), B, self.nh, L, L, self.d, kmask=kmask, causal=causal,
@@ -684,22 +495,16 @@ class TransformerCore(object):
         dkv = e.mat("g.%s.dkv" % tag, mem.rows, 2 * H)
         rk = self.store.s(p + "rpr_keys/embeddings") if self.rpr else None
         rv = self.store.s(p + "rpr_values/embeddings") if self.rpr else None
-        if fuse_tmask is None and self._attn_bwd_ln(q, kv.cols_slice(0, H), kv.cols_slice(H, 2 * H), att,
-                                                    e.buf(tag + ".lse", (B * self.nh * Lq,), F32), dq, dkv.cols_slice(0, H),
-                                                    dkv.cols_slice(H, 2 * H), B, Lq, Lk, kmask, False, sid0, oproj, dq,
-                                                    self.W(p + "q_map/W_0_0"), ds):
-            self._linear_bwd(x_in, dq, p + "q_map", dx=None)              # the weight gradient only
-        else:
-            e.attn_bwd(q, kv.cols_slice(0, H), kv.cols_slice(H, 2 * H), att, datt,
-                       e.buf(tag + ".lse", (B * self.nh * Lq,), F32), dq, dkv.cols_slice(0, H),
-                       dkv.cols_slice(H, 2 * H), B, self.nh, Lq, Lk, self.d, kmask=kmask, causal=False,
-                       rpr_k=rk, rpr_v=rv,
-                       drpr_k=self.gb(p + "rpr_keys/embeddings") if self.rpr else None,
-                       drpr_v=self.gb(p + "rpr_values/embeddings") if self.rpr else None,
-                       max_rel=hp.max_relative_position, drop_p=hp.attention_dropout, sid=sid0,
-                       defer_tables=(self._pending_rpr, tag) if self._defer_rpr() else None, oproj=oproj)
-            self._linear_bwd(x_in, dq, p + "q_map", dx=dx_out, residual=ds,
-                             ln_next=self._ln_next if fuse_tmask is None else None)
+        e.attn_bwd(q, kv.cols_slice(0, H), kv.cols_slice(H, 2 * H), att, datt,
+                   e.buf(tag + ".lse", (B * self.nh * Lq,), F32), dq, dkv.cols_slice(0, H),
+                   dkv.cols_slice(H, 2 * H), B, self.nh, Lq, Lk, self.d, kmask=kmask, causal=False,
+                   rpr_k=rk, rpr_v=rv,
+                   drpr_k=self.gb(p + "rpr_keys/embeddings") if self.rpr else None,
+                   drpr_v=self.gb(p + "rpr_values/embeddings") if self.rpr else None,
+                   max_rel=hp.max_relative_position, drop_p=hp.attention_dropout, sid=sid0,
+                   defer_tables=(self._pending_rpr, tag) if self._defer_rpr() else None, oproj=oproj)
+        self._linear_bwd(x_in, dq, p + "q_map", dx=dx_out, residual=ds,
+                         ln_next=self._ln_next if fuse_tmask is None else None)
         # memory side: the gradients of all decoder layers add up in d_mem.  Default: every layer only records its
         # (dK, W_k) / (dV, W_v) pair and ONE K-segmented GEMM sums them after the decoder (see _finish_mem_grad);
         # otherwise each layer accumulates in place.
@@ -853,17 +658,11 @@ class TransformerCore(object):
         if not self.__dict__.get("_embeds_done"):      # (forward(): both embeddings went out as one launch)
             e.embed_fwd(batch["src"], self.store.s(self.src_emb), self.b("bias"), x, B, Ls, H,
                         drop_p=hp.dropout if train else 0.0, sid=9001)
-        def layers(x=x):
-            for l in range(hp.num_encoder_layer):
-                pre = "encoder/layer_%d" % l
-                x = self._self_attn_fwd(x, B, Ls, pre + "/self_attention", "e%d.sa" % l, smask, False, save,
-                                        100 * l + 1, train)
-                x = self._ffn_fwd(x, pre + "/feed_forward", "e%d.ff" % l, save, 100 * l + 11, train,
-                                  last=(l == hp.num_encoder_layer - 1))
-            return x
-        # the layer stack is sentence-local all the way down: one persistent launch (zk_layer.hip) when every op of
-        # it can be recorded (plain dot-product attention on the MFMA tiles), ordinary launches otherwise
-        x = e.run_program(B, layers) if (not self.rpr and not self.use_side) else layers()
+        for l in range(hp.num_encoder_layer):
+            pre = "encoder/layer_%d" % l
+            x = self._self_attn_fwd(x, B, Ls, pre + "/self_attention", "e%d.sa" % l, smask, False, save,
+                                    100 * l + 1, train)
+            x = self._ffn_fwd(x, pre + "/feed_forward", "e%d.ff" % l, save, 100 * l + 11, train)
         return x, smask
 
     def decode_train(self, batch, enc, smask, train, save):
@@ -894,42 +693,31 @@ class TransformerCore(object):
             elif not self.fuse:
                 x = self._self_attn_fwd(x, B, Lt, pre + "/self_attention", "d%d.sa" % l, None, True, save,
                                         sid + 1, train)
-            if group_kv and l == 0:
-                self._join_side()
             x = self._cross_attn_fwd(x, enc, B, Lt, Ls, pre + "/" + self.cross, "d%d.ca" % l, smask, save,
                                      sid + 11, train, kv_ready=group_kv, fuse_tmask=tmask if self.fuse else None)
-            x = self._ffn_fwd(x, pre + "/feed_forward", "d%d.ff" % l, save, sid + 21, train,
-                              last=(l == hp.num_decoder_layer - 1))
+            x = self._ffn_fwd(x, pre + "/feed_forward", "d%d.ff" % l, save, sid + 21, train)
         return x, tmask, w
 
     def loss_head(self, batch, feat, w, label_smooth, need_grad):
-        """transformer.py:182-216: logits GEMM + k_ce_fused, or with ZERO_HIP_FUSED_CE=1 the fused form (the
-        [T, V] fp32 logits are never written; the backward recomputes them tile by tile)."""
+        """transformer.py:182-216: logits GEMM + k_ce_fused."""
         e = self.eng
         B, Lt = batch["B"], batch["Lt"]
         Tt = B * Lt
         E = self.W(self.soft_emb)
         ce = e.buf("ce", (Tt,), F32)
-        self._fused_ce = self.fused_ce and e.gemm_impl != 1 and self.H % 8 == 0
-        if self._fused_ce:
-            logits, dlogits = None, None
-            lse = e.buf("lse", (Tt,), F32)
-            e.logits_ce_fwd(feat, E, batch["tgt"], ce, lse, Tt, self.V, label_smooth)
-            self._ce_ctx = (lse, w, label_smooth) if need_grad else None
+        logits = e.mat("logits", Tt, self.Vpad, F32)
+        if self.logits_tile256 and e.gemm_impl == 0 and self.H % 8 == 0:
+            # 256x256 tiles, fp32 tile stored straight from the accumulators (scripts/gemm_big_bench.py:
+            # 223 us against 274-291 us for the 128x128 kernels on the 4096 x 32000 x 512 problem).  bf16 logits
+            # were measured and are slower (profiles/r03_negative_results.txt: a bf16 32x32 MFMA tile leaves
+            # as 64-byte half lines, +118 us on a GEMM that is not output-bound, for -16 us of cross entropy)
+            # (round 5: the form that issues its LDS-DMA in one place per half-workgroup -- tuning key 14 -- instead of
+            # spread between the MFMA groups: 163-167 us against 171-175 in scripts/gemm_big_bench.py --sched)
+            e.gemm_grouped([(feat, E, logits, Tt, self.V, self.H, None)], 0, 1, tile=(256, 256, 0))
         else:
-            logits = e.mat("logits", Tt, self.Vpad, F32)
-            if self.logits_tile256 and e.gemm_impl == 0 and self.H % 8 == 0:
-                # 256x256 tiles, fp32 tile stored straight from the accumulators (scripts/gemm_big_bench.py:
-                # 223 us against 274-291 us for the 128x128 kernels on the 4096 x 32000 x 512 problem).  bf16 logits
-                # were measured and are slower (profiles/r03_negative_results.txt: a bf16 32x32 MFMA tile leaves
-                # as 64-byte half lines, +118 us on a GEMM that is not output-bound, for -16 us of cross entropy)
-                # (round 5: the form that issues its LDS-DMA in one place per half-workgroup -- tuning key 14 -- instead of
-                # spread between the MFMA groups: 163-167 us against 171-175 in scripts/gemm_big_bench.py --sched)
-                e.gemm_grouped([(feat, E, logits, Tt, self.V, self.H, None)], 0, 1, tile=(256, 256, 0))
-            else:
-                e.gemm(feat, E, logits, Tt, self.V, self.H, 0, 1)
-            dlogits = e.mat("dlogits", Tt, self.Vpad) if need_grad else None
-            e.ce_fused(logits, batch["tgt"], w if need_grad else None, ce, dlogits, Tt, self.V, label_smooth)
+            e.gemm(feat, E, logits, Tt, self.V, self.H, 0, 1)
+        dlogits = e.mat("dlogits", Tt, self.Vpad) if need_grad else None
+        e.ce_fused(logits, batch["tgt"], w if need_grad else None, ce, dlogits, Tt, self.V, label_smooth)
         per_sample = e.buf("per_sample", (B,), F32)
         loss = e.buf("loss", (1,), F32)
         e.loss_reduce(ce, batch["tgt"], per_sample, loss, B, Lt)
@@ -937,16 +725,12 @@ class TransformerCore(object):
 
     def forward(self, batch, train=False, save=False, label_smooth=None):
         ls = self.hp.label_smooth if label_smooth is None else label_smooth
-        self._lazy = self._use_lazy_ln(train, save)
-        self._lazy_tags = {}
         # residual + LayerNorm inside the sub-layer output GEMMs (ZERO_HIP_SYNC_LN=0: a launch of their own)
-        self._sync_ln = self.sync_ln_mode and not self._lazy and self.eng.gemm_impl == 0 and self.H % 64 == 0 and \
+        self._sync_ln = self.sync_ln_mode and self.eng.gemm_impl == 0 and self.H % 64 == 0 and \
             self.H <= 1024 and self.F % 64 == 0 and self.eng.sync_ln_usable()
-        pair_embeds = self.merge_small and "tgt" in batch and not self.eng.lib.recording
+        pair_embeds = self.merge_small and "tgt" in batch
         if self._sync_ln and not pair_embeds:
             self.eng.ln_epoch_bump()          # (else the paired embedding launch below advances the epoch)
-        if self._lazy:
-            self._fold_weights()
         # round 6: both input embeddings depend on the ids alone -- one launch in front of the step instead of two
         # (ZERO_HIP_MERGE_SMALL=0: the round-5 launches)
         self._embeds_done = False
@@ -963,8 +747,7 @@ class TransformerCore(object):
         finally:
             self._embeds_done = False
         loss, per_sample, logits, dlogits = self.loss_head(batch, feat, w, ls, save)
-        self._lazy = False        # (encode() / decode_train() are also called directly by the decode path)
-        self._sync_ln = False
+        self._sync_ln = False     # (encode() / decode_train() are also called directly by the decode path)
         self._ctx = (batch, enc, smask, feat, tmask, dlogits)
         return loss, per_sample, logits
 
@@ -979,11 +762,6 @@ class TransformerCore(object):
         batch, enc, smask, feat, tmask, dlogits = self._ctx
         B, Ls, Lt = batch["B"], batch["Ls"], batch["Lt"]
         Ts, Tt = B * Ls, B * Lt
-        self.fused_info = None
-        if dlogits is None:      # fused cross entropy: recompute the logits tiles, write d(loss)/d(logits)
-            lse, w, ls = self._ce_ctx
-            dlogits = e.mat("dlogits", Tt, self.Vpad)
-            e.logits_ce_bwd(feat, self.W(self.soft_emb), batch["tgt"], w, lse, dlogits, Tt, self.V, ls)
         st = self.store
         # embedding tables receive dense gradients (zero rows for unseen ids): untouched rows must
         # read as zero.  The softmax table is fully overwritten by its wgrad GEMM instead.
@@ -999,11 +777,9 @@ class TransformerCore(object):
         e.gemm(dlogits, E, P[cur], Tt, H, self.Vpad, 0, 0)
         gE = self.gW(self.soft_emb)
         if self.group_wgrad and e.gemm_impl == 0:
-            # (the table's gradient is complete here only if no embedding lookup adds rows to it afterwards)
-            self._pending_wgrads.append((dlogits, feat, gE, self.Vpad, H, Tt, None, None, None,
-                                         self.soft_emb != self.tgt_emb and self.soft_emb != self.src_emb))
+            self._pending_wgrads.append((dlogits, feat, gE, self.Vpad, H, Tt, None, None, None))
         else:
-            self._side(lambda: e.gemm(dlogits, feat, gE, self.Vpad, H, Tt, 1, 0))
+            e.gemm(dlogits, feat, gE, self.Vpad, H, Tt, 1, 0)
         d_enc = e.mat("g.denc", Ts, H)
         if not self._use_kseg():
             e.zero(d_enc.t)
@@ -1023,8 +799,7 @@ class TransformerCore(object):
             return e.mat("dec.x0" if side == "d" else "enc.x0", Tt if side == "d" else Ts, H)
 
         fuse_ln_bwd = self.sync_ln_mode and self.sync_ln_bwd and self.group_wgrad and e.gemm_impl == 0 and \
-            H % 64 == 0 and H <= 1024 and not self.fuse and not self._lazy_tags and not e.lib.recording and \
-            e.sync_ln_usable()       # (the fallback of a failed self-test covers the backward too)
+            H % 64 == 0 and H <= 1024 and not self.fuse and e.sync_ln_usable()       # (the fallback of a failed self-test covers the backward too)
 
         def ln_below(side, l, kind):
             """(scope, tag, bias of the linear layer before it, dropout, dropout site) of the LayerNorm whose output is the
@@ -1088,22 +863,22 @@ class TransformerCore(object):
             if not self.group_all and (len(ready_d) >= self.group_layers or l == 0):
                 self._flush_wgrads()
                 for key in ready_d:
-                    self._side(lambda key=key: on_ready(key))
+                    on_ready(key)
                 ready_d = []
         dxt = P[cur]
 
         def tgt_embed_grads():
-            # side stream is in order: the softmax wgrad that overwrote the shared table is done
+            # (issued after the softmax wgrad that overwrote the shared table)
             e.embed_bwd_sorted(batch["tgt_sort"], dxt, st.g(self.tgt_emb), H,
                                accumulate=(self.tgt_emb == self.soft_emb), drop_p=hp.dropout, sid=9002)
             e.colsum(dxt, st.g("bias"), skip_L=Lt, accumulate=False, drop_p=hp.dropout, sid=9002)
         def tables_ready():
             if self.soft_emb != self.src_emb:
-                self._side(lambda: on_ready(self.soft_emb))
+                on_ready(self.soft_emb)
             if self.tgt_emb != self.soft_emb and self.tgt_emb != self.src_emb:
-                self._side(lambda: on_ready(self.tgt_emb))
+                on_ready(self.tgt_emb)
         if not self.group_all:
-            self._side(tgt_embed_grads)
+            tgt_embed_grads()
             tables_ready()
         if self._use_kseg():
             self._finish_mem_grad(d_enc)
@@ -1130,7 +905,7 @@ class TransformerCore(object):
             if (not self.group_all and len(ready_e) >= self.group_layers) or l == 0:
                 self._flush_wgrads()
                 for key in ready_d + ready_e:      # (group_all: the decoder's keys were held back with its weight gradients)
-                    self._side(lambda key=key: on_ready(key))
+                    on_ready(key)
                 ready_d, ready_e = [], []
         dxs = Q[cur]
         # round 6 (one rank, different tables): the two gradient scatters as one launch, the two bias column sums as one pair
@@ -1139,9 +914,9 @@ class TransformerCore(object):
             if ready_d:                            # a model without encoder layers
                 self._flush_wgrads()
                 for key in ready_d:
-                    self._side(lambda key=key: on_ready(key))
+                    on_ready(key)
             if not pair:
-                self._side(tgt_embed_grads)   # after the (single) grouped launch that overwrote the shared softmax table
+                tgt_embed_grads()   # after the (single) grouped launch that overwrote the shared softmax table
                 tables_ready()
 
         def src_embed_grads():
@@ -1156,9 +931,9 @@ class TransformerCore(object):
                                     batch["src_sort"], dxs, st.g(self.src_emb), False, 9001, H, drop_p=hp.dropout)
             e.colsum_pair(dxt, Lt, 9002, dxs, 0, 9001, st.g("bias"), drop_p=hp.dropout)
         if pair:
-            self._side(both_embed_grads)
+            both_embed_grads()
             tables_ready()
-            self._side(lambda: (on_ready("bias"), on_ready(self.src_emb)))
+            on_ready("bias")
+            on_ready(self.src_emb)
         else:
-            self._side(src_embed_grads)
-        self._join_side()
+            src_embed_grads()
