@@ -458,6 +458,19 @@ int zk_beam_topk_advance(const float* logits, int ld, float temperature, float f
 /* search.py:143-145 (enable_noise_beam_search): logits += Gumbel noise -log(-log(u + eps) + eps), util.py:189-195 */
 int zk_add_gumbel(float* logits, int rows, int V, int ld, float eps, const uint64_t* seed, uint32_t sid,
                   zk_stream_t stream);
+/* ---- main.py:65-115 ensemble decoding, the combination of main.py:101-103 (see zk_ensemble.hip):
+ * out[r, v] = log( (1/M) * sum_m softmax(logits_m[r, :])[v] ) for v < V (columns >= V of `out` are left untouched), in the
+ * stable form logsumexp_m(logits_m[r, v] - logsumexp(logits_m[r, :])) - log M with fp32 arithmetic and accumulation: where
+ * every member's probability underflows, the result is the finite log-probability instead of the reference's tf.log(0) =
+ * -inf (the one intended deviation); M = 1 is a plain fp32 log-softmax.
+ * logits / ld: HOST arrays of M device pointers (fp32 [rows, ld[m]], 16-byte aligned) and leading dimensions (multiples
+ * of 4, >= V); they travel by value in the launch arguments, so the call allocates, copies and synchronises nothing and
+ * can be captured.  M <= zk_ensemble_max() (8), otherwise an argument error.
+ * workspace: zk_ensemble_logprob_workspace(rows, M, V) bytes (the per-chunk row statistics of the first pass). */
+int zk_ensemble_max(void);
+size_t zk_ensemble_logprob_workspace(int rows, int M, int V);
+int zk_ensemble_logprob(const float* const* logits, const int* ld, int M, int rows, int V, float* out, int ld_out,
+                        void* workspace, size_t ws_bytes, zk_stream_t stream);
 /* k/v cache rows with the time step in device memory (hipGraph replay of func.py:199-205 and of the
    beam reorder search.py:206-209).  mode 0 (append): dst[r][*time_dev] <- src[r] (unit_bytes);
    mode 1 (reorder): dst[r][0 .. *time_dev) <- src[index[r]][0 .. *time_dev) in units of unit_bytes;

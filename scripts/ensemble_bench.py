@@ -1,0 +1,165 @@
+"""Ensemble decode throughput on the BASELINE configs[3] decode shape (transformer_aan, Transformer-base sizes, beam 4,
+alpha 0.6, decode_length 50, eval batch 32, V = 32000; the workload of scripts/decode_bench.py): M in {1, 2, 4} members of
+identical shape (different random weights) against the single model, and the combine kernel (zk_ensemble_logprob) alone.
+
+Prints ONE JSON line:
+  single / ensemble[M]: sentences/s and ms per decode step -- median over --repeats passes over the same batches, after
+      one warm-up pass (buffer sizing; the ensemble captures its step graphs anew for every batch, the single model
+      replays cached ones), host clock around work that ends in a device synchronise;
+  ensemble[M].steps_vs_single: ms per ensemble step / (M * ms per single-model step of this run);
+  kernel[M]: the combine on [128, 32000] fp32 logits per member -- median of --kernel-iters calls, each between two HIP
+      events, and the bytes it must move ((M + 1) * rows * V * 4: every member's logits read once, the result written
+      once) over that time.  The kernel reads the logits a second time in its combine pass, mostly from the caches.
+
+Every leg runs in a child process of its own under its own time limit; the first failing leg ends the run.
+
+usage: python scripts/ensemble_bench.py [--sentences 256] [--repeats 3] [--dtype bfloat16]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+V = 32000
+ROWS = 128
+
+
+def _params(args, i):
+    from zero_amd.config import transformer_base_params, SyntheticVocab
+    hp = transformer_base_params(model_name="transformer_aan", scope_name="ensbench%d" % i, beam_size=4, decode_alpha=0.6,
+                                 decode_length=50, eval_batch_size=32)
+    hp.src_vocab = SyntheticVocab(V)
+    hp.tgt_vocab = SyntheticVocab(V)
+    hp.decode_dtype = args.dtype
+    hp.random_seed = 1234 + i            # members of identical shape, different weights
+    return hp
+
+
+def _batches(args, hp):
+    import numpy as np
+    rng = np.random.default_rng(1234)
+    lens = np.clip(np.rint(rng.normal(28, 14, args.sentences)), 4, 100).astype(int)
+    order = np.argsort(lens, kind="stable")                     # length-sorted batches (data.py:69-73)
+    out = []
+    for b0 in range(0, args.sentences, hp.eval_batch_size):
+        idx = order[b0:b0 + hp.eval_batch_size]
+        src = np.zeros((len(idx), int(lens[idx].max()) + 1), dtype=np.int64)
+        for r, i in enumerate(idx):
+            src[r, :lens[i]] = rng.integers(3, V, lens[i])
+            src[r, lens[i]] = 2
+        out.append(src)
+    return out
+
+
+def leg_decode(args, M):
+    """M = 0: the single model through tower_infer_graph's pair; M >= 1: M members through the ensemble pair."""
+    import numpy as np
+    import torch
+    from zero_amd.models import model as registry, load_all
+    from zero_amd.search import beam_search
+    load_all()
+    graph = registry.get_model("transformer_aan")
+    hps = [_params(args, i) for i in range(max(M, 1))]
+    batches = _batches(args, hps[0])
+
+    def one_pass():
+        steps = sent = 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for src in batches:
+            if M == 0:
+                enc, dec = graph.infer_fn(hps[0])
+                out = beam_search({"source": src}, enc, dec, hps[0])
+            else:
+                from zero_amd.models._ensemble import make_infer_fns
+                enc, dec, hp0 = make_infer_fns([graph] * M, hps)
+                out = beam_search({"source": src}, enc, dec, hp0)
+            steps += out["steps"]
+            sent += src.shape[0]
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, steps, sent
+    one_pass()                                                  # warm-up: buffer sizing, code objects
+    runs = [one_pass() for _ in range(args.repeats)]
+    ms = [1e3 * t / s for t, s, _ in runs]
+    sps = [n / t for t, _, n in runs]
+    return {"members": M, "sentences": runs[0][2], "decode_steps": runs[0][1], "repeats": args.repeats,
+            "ms_per_step": float(np.median(ms)), "ms_per_step_min": min(ms), "ms_per_step_max": max(ms),
+            "sentences_per_s": float(np.median(sps))}
+
+
+def leg_kernel(args):
+    import numpy as np
+    import torch
+    from zero_amd.func import Engine, Mat
+    from zero_amd.models._ensemble import combine
+
+    class _Core(object):                 # what combine() reads of a core
+        pass
+    core = _Core()
+    core.eng, core.V, core.Vpad = Engine("cuda:0"), V, V
+    out = {}
+    g = torch.Generator().manual_seed(5)
+    logits = [Mat((torch.randn(ROWS, V, generator=g) * 3).cuda(), ROWS, V) for _ in range(4)]
+    for M in (1, 2, 4):
+        for _ in range(10):
+            combine(core, logits[:M], ROWS)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(args.kernel_iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            combine(core, logits[:M], ROWS)
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b) * 1e-3)
+        t = float(np.median(times))
+        nbytes = (M + 1) * ROWS * V * 4
+        out[str(M)] = {"us": t * 1e6, "us_min": min(times) * 1e6, "bytes_must_move": nbytes, "bytes_per_s": nbytes / t,
+                       "iters": args.kernel_iters}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sentences", type=int, default=256)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--kernel-iters", type=int, default=200)
+    ap.add_argument("--dtype", default="bfloat16")
+    ap.add_argument("--leg-timeout", type=int, default=240, help="seconds per leg (a child process each)")
+    ap.add_argument("--leg", default="", help="internal: run one leg in this process and print its JSON")
+    args = ap.parse_args()
+    if args.leg:
+        res = leg_kernel(args) if args.leg == "kernel" else leg_decode(args, int(args.leg))
+        print("LEG " + json.dumps(res))
+        return 0
+    legs = {}
+    for leg in ("0", "1", "2", "4", "kernel"):
+        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--sentences", str(args.sentences), "--repeats",
+               str(args.repeats), "--kernel-iters", str(args.kernel_iters), "--dtype", args.dtype]
+        try:
+            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=args.leg_timeout, text=True)
+        except subprocess.TimeoutExpired:
+            print("ensemble_bench: leg %s exceeded %d s; stopping" % (leg, args.leg_timeout), file=sys.stderr)
+            return 124
+        lines = [l for l in p.stdout.splitlines() if l.startswith("LEG ")]
+        if p.returncode != 0 or not lines:
+            sys.stderr.write(p.stderr[-4000:])
+            print("ensemble_bench: leg %s failed (exit %d); stopping" % (leg, p.returncode), file=sys.stderr)
+            return p.returncode or 1
+        legs[leg] = json.loads(lines[-1][4:])
+    single = legs["0"]
+    ens = {}
+    for M in ("1", "2", "4"):
+        ens[M] = dict(legs[M], steps_vs_single=legs[M]["ms_per_step"] / (int(M) * single["ms_per_step"]))
+    print(json.dumps({"workload": "BASELINE configs[3] decode shape: transformer_aan base, beam 4, batch 32, V=32000, "
+                                  "%d synthetic sentences, decode_dtype=%s" % (args.sentences, args.dtype),
+                      "single": single, "ensemble": ens, "kernel": legs["kernel"]}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -160,9 +160,10 @@ def decode_many(items, work, streams=None, each_lane=False):
     return [results[k] for k in range(counter[0])]
 
 
-def decoding(graph, dataset, params, infer=None):
+def decoding(graph, dataset, params, infer=None, streams=None):
     """Translate ``dataset``; ``infer(features, graph, params) -> (seqs [B,K,L], scores [B,K])``
-    defaults to zero_amd.main.tower_infer_graph.  Batches are decoded ``decode_streams()`` at a time (decode_many)."""
+    defaults to zero_amd.main.tower_infer_graph.  Batches are decoded ``streams`` (default ``decode_streams()``) at a
+    time (decode_many)."""
     if infer is None:
         from zero_amd.main import tower_infer_graph as infer
     translations, scores, indices = [], [], []
@@ -174,7 +175,10 @@ def decoding(graph, dataset, params, infer=None):
         return data, np.asarray(seqs), np.asarray(sc), time.time() - start
 
     # (dev-mode search re-encodes on the training path of lane 0's engine: one batch at a time)
-    streams = decode_streams() if getattr(params, "search_mode", "cache") == "cache" else 1
+    if streams is None:
+        streams = decode_streams()
+    if getattr(params, "search_mode", "cache") != "cache":
+        streams = 1
     for bidx, (data, seqs, sc, used) in enumerate(decode_many(_batches(dataset, params), work, streams)):
         hyp, marks = decode_hypothesis([seqs], [sc], params)
         translations.extend(hyp)

@@ -10,6 +10,8 @@ Counterparts:
     host scalar evaluated before the step (main.py:280; lrs/noamlr.py).
   * ``tower_infer_graph`` (main.py:48-62) / ``tower_score_graph`` (main.py:118-130)
     -> :func:`tower_infer_graph` / :func:`tower_score_graph`.
+  * ``tower_ensemble_graph`` (main.py:65-115) / ``ensemble`` (main.py:623-747)
+    -> :func:`tower_ensemble_graph` / :func:`ensemble` (zero_amd/models/_ensemble.py).
 
 Data loading, evaluation cadence, checkpoints and logging of main.py are host control plane
 outside the hot path.
@@ -45,6 +47,12 @@ def tower_infer_graph(eval_features, graph, params):
     encoding_fn, decoding_fn = graph.infer_fn(params)
     out = beam_search(eval_features, encoding_fn, decoding_fn, params)
     return out["seq"], out["score"]
+
+
+def tower_ensemble_graph(eval_features, total_graphs, total_params):
+    """main.py:65-115: several models per beam step, combined on the device (zero_amd/models/_ensemble.py)."""
+    from zero_amd.models._ensemble import tower_ensemble_graph as impl
+    return impl(eval_features, total_graphs, total_params)
 
 
 def _os_environ_int(name):
@@ -797,3 +805,49 @@ def scorer(params):
     log.info("Scores %s, PPL %s, Duration %ss", np.mean(scores), ppl, time.time() - t0)
     evalu.dump_tanslation(scores, params.test_output)
     return float(np.mean(scores))
+
+
+def restore_ensemble_member(params, midx):
+    """main.py:660-730 for one member: the latest checkpoint of ``params.output_dir`` (EMA shadows in place of the plain
+    values when ``ema_decay > 0``) assigned into the variable store of scope ``<scope>_ensembler_<midx>``.  A store plus
+    its core is all a member needs: no Trainer, no optimiser state.  Returns the member's core."""
+    from zero_amd.models._ensemble import member_params, member_scope, member_tensors
+    from zero_amd.models._factory import get_core
+    from zero_amd.utils.saver import Saver, assign_tensors
+    tensors = Saver(checkpoints=params.checkpoints, output_dir=params.output_dir).restore(params.output_dir)
+    if tensors is None:
+        raise ZeroHipError("ensemble member %d: no checkpoint in %s" % (midx, params.output_dir))
+    core = get_core(member_params(params, midx), params.model_name)
+    got, missing, _ = assign_tensors(core.store, member_scope(params, midx),
+                                     member_tensors(tensors, midx, ema=params.ema_decay > 0.))
+    for name in missing:
+        log.warning("%s/%s --Bad--", member_scope(params, midx), name)
+    log.info("member %d (%s, %s): restored %d variables (%d missing)", midx, params.model_name, params.output_dir,
+             len(got), len(missing))
+    return core
+
+
+def ensemble(total_params):
+    """main.py:623-747: translate member 0's test set with all members decoding together, BLEU against member 0's
+    ``tgt_test_file``, dump to its ``test_output``.  Batches are decoded one at a time (zero_amd/models/_ensemble.py)."""
+    from zero_amd import evalu
+    from zero_amd.data import Dataset
+    from zero_amd.models._ensemble import check_members
+    load_all()
+    check_members(total_params)
+    default_params = total_params[0]
+    # (different members are assumed to use the same test file and to share both vocabularies, main.py:627-629)
+    dataset = Dataset(default_params.src_test_file, default_params.src_test_file, default_params.src_vocab,
+                      default_params.src_vocab, default_params.eval_max_len, batch_or_token='batch',
+                      data_leak_ratio=default_params.data_leak_ratio)
+    total_graphs = [model_registry.get_model(p.model_name) for p in total_params]
+    for midx, p in enumerate(total_params):
+        restore_ensemble_member(p, midx)
+    t0 = time.time()
+    tranes, scores, indices = evalu.decoding(
+        total_graphs[0], dataset, default_params, streams=1,
+        infer=lambda features, graph, params: tower_ensemble_graph(features, total_graphs, total_params))
+    bleu = evalu.eval_metric(tranes, default_params.tgt_test_file, indices=indices)
+    log.info("Scores %s, BLEU %s, Duration %ss", np.mean(scores) if scores else 0.0, bleu, time.time() - t0)
+    evalu.dump_tanslation(tranes, default_params.test_output, indices=indices)
+    return bleu

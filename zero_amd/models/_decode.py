@@ -237,6 +237,36 @@ def _fuse_tail():
     return True
 
 
+def search_tail(state, core, logits, noise, temperature, forbid_value):
+    """search.py:143-176 (+ 198-228 with the device-resident bookkeeping) on the step's fp32 ``logits`` Mat [B*K, ld]:
+    optional Gumbel noise, then temperature, log-softmax, EOS ban, length penalty and top-2K in the fused tail.  Launches
+    on the current stream with the scratch of ``core``'s engine; shared by the single-model step and the ensemble step
+    (models/_ensemble.py)."""
+    e = core.eng
+    book = state.get("book")
+    sb = state["stepbuf"]
+    if noise:      # search.py:143-145; a fresh stream position every step
+        e.lib.call("zk_add_gumbel", logits.ptr, state["BK"], core.V, logits.ld, float(zdtype.epsilon()),
+                   e.seed.data_ptr(), 7001, e.stream)
+        e.lib.call("zk_seed_advance", e.seed.data_ptr(), 1, e.stream)
+    fused_tail = False
+    if book is not None and _fuse_tail():
+        # merge of the chunked top-2K and the alive / finished bookkeeping in one launch
+        ws = e.workspace(e.lib.query("zk_beam_topk_workspace", state["B"], state["K"], 2 * state["K"]))
+        e.lib.ncalls += 1
+        rc = e.lib.raw("zk_beam_topk_advance")(logits.ptr, logits.ld, float(temperature), float(forbid_value),
+                                               ws.data_ptr(), ws.numel(), *book, e.stream)
+        if rc not in (0, -2):
+            e.lib.call("zk_beam_topk_advance", logits.ptr, logits.ld, float(temperature), float(forbid_value),
+                       ws.data_ptr(), ws.numel(), *book, e.stream)      # raises with the library's message
+        fused_tail = rc == 0
+    if not fused_tail:
+        e.beam_topk(logits, state["prev"], state["ts"], state["ti"], state["B"], state["K"], core.V,
+                    2 * state["K"], temperature, 1.0, -1, forbid_value, scal_dev=sb[1:3])
+        if book is not None:
+            e.lib.call("zk_beam_dev_advance", *book, e.stream)
+
+
 def _transposed(core, name):
     """bf16 copy of a projection weight with the input dimension contiguous (row = output channel): the operand layout of
     the fused decode kernels' matrix-core fragments.  Made by zk_transpose_bf16 once per WEIGHT VERSION (an optimiser
@@ -421,26 +451,7 @@ def make_infer_fns(params, model_name):
             state.reorder(state["idx"], time_dev=sb[0:1],
                           defer_aan=core.aan)
             logits, _ = _step_cache(state["tok"], state, None, time_dev=sb[0:1])
-            if hp.enable_noise_beam_search:      # search.py:143-145; a fresh stream position every step
-                e.lib.call("zk_add_gumbel", logits.ptr, state["BK"], core.V, logits.ld, float(zdtype.epsilon()),
-                           e.seed.data_ptr(), 7001, e.stream)
-                e.lib.call("zk_seed_advance", e.seed.data_ptr(), 1, e.stream)
-            fused_tail = False
-            if book is not None and _fuse_tail():
-                # merge of the chunked top-2K and the alive / finished bookkeeping in one launch
-                ws = e.workspace(e.lib.query("zk_beam_topk_workspace", state["B"], state["K"], 2 * state["K"]))
-                e.lib.ncalls += 1
-                rc = e.lib.raw("zk_beam_topk_advance")(logits.ptr, logits.ld, float(temperature), float(forbid_value),
-                                                       ws.data_ptr(), ws.numel(), *book, e.stream)
-                if rc not in (0, -2):
-                    e.lib.call("zk_beam_topk_advance", logits.ptr, logits.ld, float(temperature), float(forbid_value),
-                               ws.data_ptr(), ws.numel(), *book, e.stream)      # raises with the library's message
-                fused_tail = rc == 0
-            if not fused_tail:
-                e.beam_topk(logits, state["prev"], state["ts"], state["ti"], state["B"], state["K"], core.V,
-                            2 * state["K"], temperature, 1.0, -1, forbid_value, scal_dev=sb[1:3])
-                if book is not None:
-                    e.lib.call("zk_beam_dev_advance", *book, e.stream)
+            search_tail(state, core, logits, hp.enable_noise_beam_search, temperature, forbid_value)
         if g is None and core.__dict__.get("_decode_warm_rows", 0) >= state["BK"]:
             # A batch of at least this many beam rows has already been decoded on this engine, so the step's
             # scratch buffers exist: capture straight away instead of spending an eager pass first.  If the
@@ -745,4 +756,5 @@ def make_infer_fns(params, model_name):
         return _step_dev(target, state, time)
 
     decoding_fn.step_static = step_static
+    decoding_fn.step_cache = _step_cache      # the cached step with the time in device memory (models/_ensemble.py)
     return encoding_fn, decoding_fn

@@ -7,8 +7,9 @@ defaults (run.py:367-376) -- same ``param.json`` one-line JSON (run.py:250-272) 
 ``record.json`` (run.py:275-293).  With ``src_train_file`` / ``src_test_file`` set the modes run
 the reference's loops over real bitext (zero_amd/main.py train / evaluate / scorer: data feed,
 save / eval cadence, BLEU, early stopping); without data files they fall back to the synthetic
-id generator so the step can be exercised on a bare GPU box.  Model ensembling
-(``--mode ensemble``) is not part of the hot path and is not provided.
+id generator so the step can be exercised on a bare GPU box.  ``--mode ensemble`` decodes the models of
+``--ensemble_dirs "A;B;..."`` together (run.py:322-363; zero_amd/main.py ensemble): one parameter set per directory,
+the latest checkpoint of each, their distributions combined on the device at every beam step.
 """
 
 import argparse
@@ -97,8 +98,9 @@ def _parse_dict_call(text):
     return out
 
 
-def build_params(parameters="", config=""):
-    """run.py:367-376."""
+def build_params(parameters="", config="", output_dir=None):
+    """run.py:367-376.  output_dir: read the saved ``param.json`` of this directory instead of ``params.output_dir``'s
+    (an ensemble member's directory, run.py:336)."""
     params = default_params()
     params.parse(parameters)
     cfg = None
@@ -111,12 +113,25 @@ def build_params(parameters="", config=""):
             # ``dict`` (or a dict display) whose values are literals and arithmetic over them -- without evaluating code
             cfg = _parse_dict_call(text)
         params.override_from_dict(cfg)
-    if params.output_dir:
-        params = load_parameters(params, params.output_dir)
+    if output_dir or params.output_dir:
+        params = load_parameters(params, output_dir or params.output_dir)
     if cfg is not None:
         params.override_from_dict(cfg)
     params.parse(parameters)
     return params
+
+
+def build_ensemble_params(ensemble_dirs, parameters="", config=""):
+    """run.py:322-343: one parameter set per directory of ``ensemble_dirs`` ("A;B;..."), each with the priority command
+    line > that directory's ``param.json`` > ``--config`` > defaults, and ``output_dir`` pointing at the directory.
+    Host only: nothing here touches the device."""
+    dirs = [d for d in ensemble_dirs.split(";") if d.strip()]
+    all_params = []
+    for model_dir in dirs:
+        params = build_params(parameters, config, output_dir=model_dir)
+        params.output_dir = os.path.abspath(model_dir)
+        all_params.append(params)
+    return all_params
 
 
 def setup(params, synthetic_vocab=32000):
@@ -154,6 +169,25 @@ def synthetic_batches(params, n_batches, sentences=64, length=64):
         yield {"source": src, "target": tgt}
 
 
+def main_ensemble(args):
+    """run.py:322-363: ``--mode ensemble``."""
+    import logging
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
+    all_params = [setup(p) for p in build_ensemble_params(args.ensemble_dirs, args.parameters, args.config)]
+    from zero_amd import main as loops
+    from zero_amd.models import model, load_all
+    load_all()
+    if all_params and all_params[0].src_test_file:
+        print(json.dumps({"bleu": loops.ensemble(all_params)}))
+        return
+    # no test file: one synthetic batch through the ensemble step (freshly initialised members), like the synthetic test mode
+    graphs = [model.get_model(p.model_name) for p in all_params]
+    default_params = all_params[0] if all_params else setup(build_params(args.parameters, args.config))
+    for feats in synthetic_batches(default_params, 1, sentences=default_params.eval_batch_size, length=24):
+        seqs, scores = loops.tower_ensemble_graph(feats, graphs, all_params)
+        print(seqs[:, 0], scores[:, 0])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="")
@@ -169,6 +203,8 @@ def main(argv=None):
         # (zero_amd/evalu.py decode_many).  Read by the HIP runtime at its first call -- nothing has touched it yet.
         os.environ["GPU_MAX_HW_QUEUES"] = "8"
         print("zero_amd.run: GPU_MAX_HW_QUEUES=8 exported for this process (unset; see zero_amd/evalu.py decode_many)")
+    if args.mode == "ensemble":
+        return main_ensemble(args)
     params = setup(build_params(args.parameters, args.config))
     from zero_amd.main import Trainer, tower_infer_graph, tower_score_graph
     from zero_amd.models import model, load_all
