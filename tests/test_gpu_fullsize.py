@@ -50,9 +50,12 @@ REPORT = os.path.join(os.path.dirname(GOLD), "..", "gpurun_out")
 
 # element-wise tolerance of the three gradient slices (relative L2 against the bf16-storage oracle).  Slice 0 is a
 # q/k block of the FIRST encoder layer's qkv_map: the end of the longest backward chain, and q/k gradients come out
-# of the cancellation dS = P (dP - rowsum(dO o O)) whose rowsum the HIP kernels take from the bf16 O they stored
-# (measured 3.4 % at d=512, 6.6 % at d=1024 -- the same against the fp32 oracle; every variable's gradient NORM is
-# within 1 %, i.e. the difference is direction noise, not a missing term).  Slices 3 / 4 (first decoder layer's
+# of the cancellation dS = P (dP - D), D_i = sum_j P_ij dP_ij (every MFMA backward kernel sums it in fp32 from the
+# recomputed P; none takes rowsum(dO o O) from the stored bf16 O any more), with P, dS and the incoming gradients stored
+# as bf16 (measured 3.4 % at d=512, 6.6 % at d=1024 -- the same against the fp32 oracle; every variable's gradient NORM
+# is within 1 %, i.e. the difference is direction noise, not a missing term; those figures were taken while the
+# two-kernel backward still used the stored O, and the bound below does not rest on them: see the oracle's own spread
+# at the end of this comment).  Slices 3 / 4 (first decoder layer's
 # ffn enlarge, fourth encoder layer's o_map) sit 17 / 26 sub-layers deep in the backward chain: measured 3.5 % / 2.4 %
 # with the 6-layer encoder, 7.2 % / 3.3 % behind the 12-layer encoder (its output already differs by bf16 noise).
 # Slices 1 / 2 (last decoder layer, target embedding) are at the start of it: 0.5 % / 0.1 %.

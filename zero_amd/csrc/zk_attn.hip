@@ -14,7 +14,7 @@
 //   * MFMA kernels (d == 64, no RPR): 64-query tile per workgroup, 4 waves x 16 rows,
 //     v_mfma_f32_16x16x32_bf16, K / V^T / P staged in LDS, softmax in registers with
 //     16-lane shuffle reductions.  Backward = flash-style recompute from the saved
-//     log-sum-exp: kernel A (per query tile) -> dQ and D=rowsum(dO*O); kernel B (per key
+//     log-sum-exp: kernel A (per query tile) -> dQ and D=rowsum(P*dP); kernel B (per key
 //     tile) -> dK, dV.
 #include "zk_attn_dev.h"
 #include "zk_gemm2_dev.h"      // gemm_tile: the output projection + residual + LayerNorm of k_attn_out_ln
@@ -505,8 +505,7 @@ __global__ void __launch_bounds__(512) k_attn_out_ln(AttnArgs a, bf16_t* __restr
 }
 
 // ---- backward A: grid (ceil(Lq/64), nh, B) -> dQ, Dbuf
-__global__ void __launch_bounds__(256) k_attn_bwd_dq_mfma(AttnArgs a, const bf16_t* __restrict__ o, int ldo,
-                                                          const bf16_t* __restrict__ dout, int lddo,
+__global__ void __launch_bounds__(256) k_attn_bwd_dq_mfma(AttnArgs a, const bf16_t* __restrict__ dout, int lddo,
                                                           const float* __restrict__ lse,
                                                           bf16_t* __restrict__ dq, int lddq,
                                                           float* __restrict__ Dbuf) {
@@ -527,38 +526,71 @@ __global__ void __launch_bounds__(256) k_attn_bwd_dq_mfma(AttnArgs a, const bf16
   const bf16_t* qb = a.q + (size_t)b * a.bsq + h * AD;
   const bf16_t* kb = a.k + (size_t)(b / a.kv_group) * a.bsk + h * AD;
   const bf16_t* vb = a.v + (size_t)(b / a.kv_group) * a.bsv + h * AD;
-  const bf16_t* ob = o + (size_t)b * a.Lq * ldo + h * AD;
   const bf16_t* dob = dout + (size_t)b * a.Lq * lddo + h * AD;
   const uint64_t seed = a.thr ? *a.seed : 0;
 
   stage_direct(sQ, qb, a.ldq, i0, a.Lq, tid);
   stage_direct(sdO, dob, lddo, i0, a.Lq, tid);
-  {  // D_i = sum_c dO[i][c] * O[i][c]; 4 threads per row
-    const int r = tid >> 2, part = tid & 3;
-    float acc = 0.f;
-    if (i0 + r < a.Lq) {
+  if (tid < TQ) {
+    const int i = i0 + tid;
+    sL[tid] = (i < a.Lq) ? lse[((size_t)b * a.nh + h) * a.Lq + i] : 0.f;
+  }
+  const int rloc = w * 16 + (lane >> 4) * 4;
+  const int nkt = (a.Lk + 63) / 64;
+  // D_i = sum_j P_ij dP_ij from a first walk over the key tiles, as in k_attn_bwd_fused64 (zk_attn_dev.h), not
+  // rowsum(dO o O) over the stored bf16 O: with the rounded O every dS_ij of a row carried a common offset
+  // ~2^-9 |dO.O| P_ij, which is a large part of dQ where few keys hold the weight (the first rows of a causal mask:
+  // 1 % of the row's norm, tests/test_gpu_attention_elementwise.py) -- sum_j dS_ij = 0 now holds to fp32 rounding.
+  {
+    float Dacc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt < nkt; ++kt) {
+      __syncthreads();
+      stage_direct(sK, kb, a.ldk, kt * 64, a.Lk, tid);
+      stage_direct(sV, vb, a.ldv, kt * 64, a.Lk, tid);
+      __syncthreads();
+      const uint4 q0 = frag(sQ, w * 16, 0, lane), q1 = frag(sQ, w * 16, 1, lane);
+      const uint4 g0 = frag(sdO, w * 16, 0, lane), g1 = frag(sdO, w * 16, 1, lane);
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        float x[8], y[8];
-        unpack8(*reinterpret_cast<const uint4*>(dob + (size_t)(i0 + r) * lddo + part * 16 + u * 8), x);
-        unpack8(*reinterpret_cast<const uint4*>(ob + (size_t)(i0 + r) * ldo + part * 16 + u * 8), y);
+      for (int nt = 0; nt < 4; ++nt) {
+        f32x4_t s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+        s = mfma16(q0, frag(sK, nt * 16, 0, lane), s);
+        s = mfma16(q1, frag(sK, nt * 16, 1, lane), s);
+        dp = mfma16(g0, frag(sV, nt * 16, 0, lane), dp);
+        dp = mfma16(g1, frag(sV, nt * 16, 1, lane), dp);
+        const int j = kt * 64 + nt * 16 + (lane & 15);
+        const bool kvalid = j < a.Lk;
+        float kbias = 0.f;
+        if (kvalid && a.kmask != nullptr && a.kmask[(size_t)(b / a.kv_group) * a.ldmask + j] == 0.f) kbias = -a.mask_inf;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) acc += x[c] * y[c];
+        for (int r = 0; r < 4; ++r) {
+          const int i = i0 + rloc + r;
+          float raw = s[r], dpv = dp[r];
+          if (a.gq != nullptr && kvalid && i < a.Lq) { raw += rpr_gather(a, a.gq, b, h, i, j); dpv += rpr_gather(a, a.gd, b, h, i, j); }
+          float sc = raw * a.scale + kbias;
+          if (a.causal && j > a.q_pos0 + i) sc -= a.mask_inf;
+          const float p = (kvalid && i < a.Lq) ? __expf(sc - sL[rloc + r]) : 0.f;
+          if (a.thr) {
+            const uint64_t idx = (((uint64_t)b * a.nh + h) * a.Lq + i) * a.Lk + j;
+            dpv *= zk_drop_scale(seed, a.sid, idx, a.thr, a.inv_keep);
+          }
+          Dacc[r] += p * dpv;
+        }
       }
     }
-    acc = quad_sum(acc);
-    if (part == 0) {
-      sD[r] = acc;
-      const int i = i0 + r;
-      sL[r] = (i < a.Lq) ? lse[((size_t)b * a.nh + h) * a.Lq + i] : 0.f;
-      if (i < a.Lq && Dbuf != nullptr) Dbuf[((size_t)b * a.nh + h) * a.Lq + i] = acc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float t = Dacc[r];
+      t += __shfl_xor(t, 1); t += __shfl_xor(t, 2); t += __shfl_xor(t, 4); t += __shfl_xor(t, 8);   // the row's 16 lanes
+      const int i = i0 + rloc + r;
+      if ((lane & 15) == 0) {
+        sD[rloc + r] = t;
+        if (i < a.Lq && Dbuf != nullptr) Dbuf[((size_t)b * a.nh + h) * a.Lq + i] = t;
+      }
     }
   }
   f32x4_t dQ[4];
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) dQ[nb] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  const int rloc = w * 16 + (lane >> 4) * 4;
-  const int nkt = (a.Lk + 63) / 64;
   for (int kt = 0; kt < nkt; ++kt) {
     __syncthreads();
     stage_direct(sK, kb, a.ldk, kt * 64, a.Lk, tid);
@@ -1101,7 +1133,7 @@ int zk_attn_bwd(const void* q, const void* k, const void* v, const void* out, co
   }
   if (impl == 2 || impl == 3 || (impl == 0 && ok)) {
     hipLaunchKernelGGL(k_attn_bwd_dq_mfma, dim3((Lq + TQ - 1) / TQ, nh, B), dim3(256), 0, stream, a,
-                       (const bf16_t*)out, ldo, (const bf16_t*)dout, lddo, lse, (bf16_t*)dq, lddq, Dbuf);
+                       (const bf16_t*)dout, lddo, lse, (bf16_t*)dq, lddq, Dbuf);
     ZK_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_attn_bwd_dkv_mfma, dim3((Lk + TQ - 1) / TQ, nh, B), dim3(256), 0, stream, a,
                        (const bf16_t*)dout, lddo, lse, Dbuf, (bf16_t*)dk, lddk, (bf16_t*)dv, lddv);

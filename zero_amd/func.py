@@ -461,8 +461,10 @@ class Engine(object):
                 code |= 256
         elif any(p[8] is not None for p in problems):
             assert code in (5, 6) and not tb, "column sums ride on the producer waves of the wide tiles (tb = 0)"
+        # (the leading dimensions and the output type belong to the key: two views of one address differ in them)
         key = (ta, tb, bm, bn, spread) + tuple((a.ptr, b.ptr, c.ptr, M, N, K, hip.ptr(bias) or 0, r.ptr if r is not None else 0,
-                                           hip.ptr(cs) or 0) for a, b, c, M, N, K, bias, r, cs in problems)
+                                           hip.ptr(cs) or 0, a.ld, b.ld, c.ld, r.ld if r is not None else 0, c.t.dtype)
+                                          for a, b, c, M, N, K, bias, r, cs in problems)
         cache = self.__dict__.setdefault("_group_cache", {})
         ent = cache.get(key)
         if ent is None:
