@@ -480,12 +480,14 @@ int zk_cache_rows(const void* src, size_t src_stride, const int* index, void* ds
 /* transformer_aan.py:110-112: cache += x; cat = [x | cache/(t+1)] */
 /* Decode-step form of the residual + LayerNorm of the decoder with its row-local neighbours in the same launch
  * (transformer_aan.py:165-192, func.py:289-303): the sub-layer output y is ybuf (bf16 [rows, H]), or
- *   z/cat_in != NULL: the AAN gate sigma(z_i) x + sigma(z_f) y, computed first (into ybuf), or
+ *   z/cat_in != NULL: the AAN gate bf16(sigma(z_i) x + sigma(z_f) y) of cat_in = [x | y], kept in registers (z NULL with
+ *                     parts: z = bf16(sum_p parts + bias) over rows of 2H), or
  *   parts != NULL   : bf16(sum_p parts[p*part_stride + r*H + :] + bias) -- the output projection left as nparts fp32
  *                     partial products by zk_dec_cross / zk_dec_self (summed in the fixed order p = 0 .. nparts-1);
  * out = LayerNorm(x + y); cache/cat_out != NULL: the next layer's running sum and [x | average] follow (zk_aan_decode).
  * The row stays in registers from the loads to the output and is rounded to bf16 where the separate kernels stored bf16:
- * the first two forms equal zk_aan_gate_fwd + zk_add_ln_fwd + zk_aan_decode bit for bit.  ybuf is only read (first form). */
+ * the first two forms equal zk_aan_gate_fwd + zk_add_ln_fwd + zk_aan_decode bit for bit.  ybuf is never written: it is
+ * read in the first form and ignored in the others. */
 int zk_ln_decode(const void* x, void* ybuf, const float* gamma, const float* beta, void* out, int rows, int H, float eps,
                  const void* z, const void* cat_in, const float* parts, int nparts, long part_stride, const float* bias,
                  float* cache, void* cat_out, float inv_count, const int* time_dev, zk_stream_t stream);

@@ -528,7 +528,8 @@ int zk_cache_rows(const void* src, size_t src_stride, const int* index, void* ds
 }
 
 // out = LayerNorm(x + y) with the optional neighbours described in zk_lndec_dev.h.  x / out dense [rows, H]; ybuf
-// [rows, H] is the sub-layer output (read), or with z != NULL / parts != NULL a scratch row buffer y is written to first.
+// [rows, H] is the sub-layer output and is only ever read; with cat_in != NULL (the gate) or parts != NULL, y is formed in
+// registers and ybuf is ignored.
 int zk_ln_decode(const void* x, void* ybuf, const float* gamma, const float* beta, void* out, int rows, int H, float eps,
                  const void* z, const void* cat_in, const float* parts, int nparts, long part_stride, const float* bias,
                  float* cache, void* cat_out, float inv_count, const int* time_dev, hipStream_t stream) {

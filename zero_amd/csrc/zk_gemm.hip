@@ -507,8 +507,9 @@ int zk_gemm_ln_bwd(const void* dY, const void* W, int M, int N, int K, int lda, 
 // A[:, K_z] B[K_z, :] over the z-th K range; no epilogue and no reduction launch -- the consumer adds them in the
 // fixed order z = 0, 1, .. (zk_ln_decode with parts / nparts / part_stride = M*N and the bias).  For products with few
 // rows and a long K (the decode step's FFN output projection: 128 x 512 x 2048 is 16 tiles of 64 x 64 -- 16 of 256
-// CUs streaming 512 KB each; with splits = 4 it is 64 workgroups of 128 KB).  Returns the number of parts written (the
-// K ranges are multiples of 64, so it can be smaller than `splits`), or < 0 / a hipError_t as a negative-free error.
+// CUs streaming 512 KB each; with splits = 4 it is 64 workgroups of 128 KB).  Returns 0 (or an error status) and sets
+// *nparts_out to the number of parts written: the K ranges are multiples of 64, so it can be smaller than `splits`;
+// the space of the parts behind it is left alone.
 int zk_gemm_parts(const void* A, const void* B, float* parts, int M, int N, int K, int lda, int ldb, int ta, int tb,
                   int splits, int* nparts_out, hipStream_t stream) {
   ZK_CHECK_ARG(M >= 0 && N >= 0 && K >= 1 && splits >= 1 && splits <= 64, "zk_gemm_parts: bad sizes");
