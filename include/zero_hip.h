@@ -602,6 +602,40 @@ int zk_f32_embed_step(const int* ids, int rows, const float* table, const float*
                       zk_stream_t stream);
 int zk_f32_gemm_legacy(int on);
 
+/* ---- transformer_l0drop at inference (models/transformer_l0drop.py:16-135, 244-273; modules/l0norm.py:75-96, 166-177)
+ * A learned hard-concrete gate drops encoder outputs; cross-attention runs over the kept ones plus ONE slot (index 0, a
+ * zero key / value) that carries the number of dropped positions as its softmax weight.
+ *   zk_l0_gate     enc: encoder rows [B*Ls, H] (row stride ld elements), bf16 or fp32 (f32 != 0); smask fp32 [B, Ls]
+ *                  (non-zero = a source token); W fp32 [H], b0 fp32 [1]: the fp32 MASTERS of source_pruning in both modes
+ *                  (the keep decision is discrete: the dot product runs in fp32).  Per sentence b:
+ *                    gate[b, j] = clip(sigmoid(enc[b, j, :] . W + b0) * 1.2 - 0.1, 0, 1)         fp32 [B, Ls]
+ *                    pos[b, 0 .. nkeep[b])  the kept positions (gate != 0 and smask != 0) in ascending order, -1 behind
+ *                    nkeep[b], ndrop[b] = (number of source tokens) - nkeep[b];  *kmax = max_b nkeep[b]   (int32)
+ *                  H and ld multiples of 4, rows aligned to four elements.
+ *   zk_l0_compact  Lm >= 1 + *kmax slots per sentence, every element of the outputs is written:
+ *                    mem[b, 0, :] = 0;  mem[b, 1 + i, :] = enc[b, pos[b, i], :] * gate (rounded to the storage type) for
+ *                    i < nkeep[b], exact zeros behind                     [B*Lm, H] of enc's type, row stride ldm
+ *                    gmask[b, 0] = ndrop[b] > 0;  gmask[b, 1 + i] = i < nkeep[b]               fp32 [B, Lm]
+ *                    kbias[b, 0] = log(max(ndrop[b], 1));  0 elsewhere                         fp32 [B, Lm]
+ *   zk_dec_cross_kb / zk_f32_attn_kb   zk_dec_cross / zk_f32_attn with kbias fp32 [.., ldmask] (may be NULL: then they ARE
+ *                  those calls) added to the scaled score of key j next to the mask term: exp(l + log c) equals the
+ *                  reference's exp(l) * c, so the softmax weighs slot 0 by its count. */
+int zk_l0_gate(const void* enc, int ld, int f32, const float* smask, const float* W, const float* b0, int B, int Ls, int H,
+               float* gate, int* pos, int* nkeep, int* ndrop, int* kmax, zk_stream_t stream);
+int zk_l0_compact(const void* enc, int ld, int f32, const float* gate, const int* pos, const int* nkeep, const int* ndrop,
+                  int B, int Ls, int H, int Lm, void* mem, int ldm, float* gmask, float* kbias, zk_stream_t stream);
+int zk_dec_cross_kb(const void* x, void* ybuf, const float* gamma, const float* beta, void* xout, int H, float eps,
+                    const void* z, const void* cat_in, const float* parts, int nparts, long part_stride, const float* bias,
+                    float* cache, void* cat_out, float inv_count, const int* time_dev, const void* wqt, int ldwq,
+                    const float* bq, const void* k, const void* v, int ldk, int ldv, long bsk, long bsv, const float* kmask,
+                    int ldmask, const float* kbias, const void* wot, int ldwo, float* out_parts, int B, int R, int nh,
+                    int Lk, float scale, float mask_inf, const void* rpr_k, const void* rpr_v, int max_rel, int pos,
+                    const int* pos_dev, zk_stream_t stream);
+int zk_f32_attn_kb(const float* q, const float* k, const float* v, float* out, int B, int nh, int Lq, int Lk, int d, int ldq,
+                   int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso, const float* kmask, int ldmask,
+                   const float* kbias, int kv_group, float scale, float mask_inf, const int* nkeys_dev, const float* rpr_k,
+                   const float* rpr_v, int max_rel, int q_pos0, const int* q_pos_dev, zk_stream_t stream);
+
 /* hipGraph plumbing: capture a sequence of the calls above once, replay per step */
 int zk_graph_begin(zk_stream_t stream);
 int zk_graph_end(zk_stream_t stream, void** exec_out);

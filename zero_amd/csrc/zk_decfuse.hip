@@ -54,6 +54,8 @@ struct DecAttnArgs {
   // cross: key j of sentence b at k + b*bsk + j*ldk.  self: caches, key j of ROW r at k + r*bsk + j*ldk (written here
   // at j = time)
   const float* kmask; int ldmask;                // cross: [B, ldmask] 1 = valid key
+  const float* kbias;                            // cross: [B, ldmask] added to the scaled score of key j, or NULL (L0Drop:
+                                                 // log of the number of source positions a slot stands for)
   const bf16_t* wot; int ldwo;                   // o_map^T [H, H]
   float* part;                                   // [nh][B*R][H]
   int B, R, nh, Lk;                              // Lk: cross = source length; self = cache capacity
@@ -146,7 +148,7 @@ __global__ void __launch_bounds__(512) k_dec_attn(DecAttnArgs a) {
   const int cr = tid >> 5, ccg = (tid >> 2) & 7, cjp = tid & 3;
   const int npair = NR * Lk;
   uint4 k_r[8], v_r[8];
-  float km_r = 1.f;
+  float km_r = 1.f, kb_r = 0.f;
   auto pair_key = [&](int e) {       // key row of pair e (clamped: always valid memory)
     const int ec = min(e, npair - 1), r = ec / Lk;
     int j = ec - r * Lk;
@@ -172,6 +174,10 @@ __global__ void __launch_bounds__(512) k_dec_attn(DecAttnArgs a) {
       if (!SELF && a.kmask != nullptr) {
         const int ec = min(tid, npair - 1), r = ec / Lk;
         km_r = a.kmask[(size_t)((row0 + r) / R) * a.ldmask + (ec - r * Lk)];
+      }
+      if (!SELF && a.kbias != nullptr) {
+        const int ec = min(tid, npair - 1), r = ec / Lk;
+        kb_r = a.kbias[(size_t)((row0 + r) / R) * a.ldmask + (ec - r * Lk)];
       }
     }
     if (!SELF) {                       // (self: register budget)
@@ -276,6 +282,7 @@ __global__ void __launch_bounds__(512) k_dec_attn(DecAttnArgs a) {
 #pragma unroll
         for (int u = 0; u < 8; ++u) k_r[u] = *reinterpret_cast<const uint4*>(kp + u * 8);
         if (!SELF && a.kmask != nullptr) km_r = a.kmask[(size_t)((row0 + r) / R) * a.ldmask + j];
+        if (!SELF && a.kbias != nullptr) kb_r = a.kbias[(size_t)((row0 + r) / R) * a.ldmask + j];
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
@@ -291,7 +298,9 @@ __global__ void __launch_bounds__(512) k_dec_attn(DecAttnArgs a) {
       const float* rk = sRk + rel_row(j);
       for (int i = 0; i < 64; ++i) dot += sQ[r * 64 + i] * rk[i];
     }
-    sS[r * LkPad + j] = dot * a.scale + ((!SELF && km_r == 0.f) ? -a.mask_inf : 0.f);
+    float sc = dot * a.scale + ((!SELF && km_r == 0.f) ? -a.mask_inf : 0.f);
+    if (!SELF && a.kbias != nullptr) sc += kb_r;
+    sS[r * LkPad + j] = sc;
   }
   __syncthreads();
 
@@ -460,23 +469,26 @@ int zk_dec_trace_read(unsigned long long* out16) {
 // LayerNorm(x + y) -- the residual input of the LayerNorm that follows this sub-layer).  k / v: keys and values of the
 // B sentences (row j of sentence b at + b*bs + j*ld), kmask [B, ldmask] or NULL.  out_parts fp32 [nh][B*R][H]: feed
 // it to zk_ln_decode(parts = out_parts, nparts = nh, part_stride = B*R*H, bias = o_map bias).
-int zk_dec_cross(const void* x, void* ybuf, const float* gamma, const float* beta, void* xout, int H, float eps,
-                 const void* z, const void* cat_in, const float* parts, int nparts, long part_stride, const float* bias,
-                 float* cache, void* cat_out, float inv_count, const int* time_dev, const void* wqt, int ldwq,
-                 const float* bq, const void* k, const void* v, int ldk, int ldv, long bsk, long bsv, const float* kmask,
-                 int ldmask, const void* wot, int ldwo, float* out_parts, int B, int R, int nh, int Lk, float scale,
-                 float mask_inf, const void* rpr_k, const void* rpr_v, int max_rel, int pos, const int* pos_dev,
-                 hipStream_t stream) {
+// zk_dec_cross_kb: kbias fp32 [B, ldmask] (may be NULL) is added to the scaled score of key j next to the mask term --
+// transformer_l0drop's count-weighted softmax (exp(l + log c) = exp(l) * c); zk_dec_cross is the same call without it.
+int zk_dec_cross_kb(const void* x, void* ybuf, const float* gamma, const float* beta, void* xout, int H, float eps,
+                    const void* z, const void* cat_in, const float* parts, int nparts, long part_stride, const float* bias,
+                    float* cache, void* cat_out, float inv_count, const int* time_dev, const void* wqt, int ldwq,
+                    const float* bq, const void* k, const void* v, int ldk, int ldv, long bsk, long bsv, const float* kmask,
+                    int ldmask, const float* kbias, const void* wot, int ldwo, float* out_parts, int B, int R, int nh,
+                    int Lk, float scale, float mask_inf, const void* rpr_k, const void* rpr_v, int max_rel, int pos,
+                    const int* pos_dev, hipStream_t stream) {
   DecAttnArgs a{};
   a.pro = LnDecArgs{(const bf16_t*)x, (bf16_t*)ybuf, gamma, beta, (bf16_t*)xout, B * R, H, eps, (const bf16_t*)z,
                     (const bf16_t*)cat_in, parts, nparts, part_stride, bias, cache, (bf16_t*)cat_out, inv_count, time_dev};
   if (int rc = check_common("zk_dec_cross", a.pro, B, R, nh, Lk, ldwq, ldwo, wqt, wot, out_parts)) return rc;
+  ZK_CHECK_ARG(kbias == nullptr || ldmask >= Lk, "zk_dec_cross_kb: kbias rows of ldmask=%d elements are shorter than Lk=%d", ldmask, Lk);
   ZK_CHECK_ARG(k && v && bq && ldk % 8 == 0 && ldv % 8 == 0 && bsk % 8 == 0 && bsv % 8 == 0 &&
                (((uintptr_t)k | (uintptr_t)v) & 15) == 0, "zk_dec_cross: keys / values must be 16-byte aligned rows");
   if (B == 0) return 0;
   a.wqt = (const bf16_t*)wqt; a.ldw = ldwq; a.bq = bq;
   a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.ldk = ldk; a.ldv = ldv; a.bsk = bsk; a.bsv = bsv;
-  a.kmask = kmask; a.ldmask = ldmask;
+  a.kmask = kmask; a.ldmask = ldmask; a.kbias = kbias;
   a.wot = (const bf16_t*)wot; a.ldwo = ldwo; a.part = out_parts;
   a.B = B; a.R = R; a.nh = nh; a.Lk = Lk; a.scale = scale; a.mask_inf = mask_inf;
   ZK_CHECK_ARG((rpr_k == nullptr) == (rpr_v == nullptr) && (rpr_k == nullptr || (max_rel >= 0 && max_rel <= 31)),
@@ -485,6 +497,18 @@ int zk_dec_cross(const void* x, void* ybuf, const float* gamma, const float* bet
   a.time = pos; a.time_dev = rpr_k ? pos_dev : nullptr;
   a.gr = dec_group_rows(R);
   return dispatch_dec_attn<false>(a, stream);
+}
+
+int zk_dec_cross(const void* x, void* ybuf, const float* gamma, const float* beta, void* xout, int H, float eps,
+                 const void* z, const void* cat_in, const float* parts, int nparts, long part_stride, const float* bias,
+                 float* cache, void* cat_out, float inv_count, const int* time_dev, const void* wqt, int ldwq,
+                 const float* bq, const void* k, const void* v, int ldk, int ldv, long bsk, long bsv, const float* kmask,
+                 int ldmask, const void* wot, int ldwo, float* out_parts, int B, int R, int nh, int Lk, float scale,
+                 float mask_inf, const void* rpr_k, const void* rpr_v, int max_rel, int pos, const int* pos_dev,
+                 hipStream_t stream) {
+  return zk_dec_cross_kb(x, ybuf, gamma, beta, xout, H, eps, z, cat_in, parts, nparts, part_stride, bias, cache, cat_out,
+                         inv_count, time_dev, wqt, ldwq, bq, k, v, ldk, ldv, bsk, bsv, kmask, ldmask, nullptr, wot, ldwo,
+                         out_parts, B, R, nh, Lk, scale, mask_inf, rpr_k, rpr_v, max_rel, pos, pos_dev, stream);
 }
 
 // Self-attention sub-layer of a decode step over per-beam caches (func.py:199-205): wqkv [H, 3H] (q | k | v column

@@ -674,7 +674,7 @@ __global__ void __launch_bounds__(256) k_f32_attn(const float* __restrict__ q, c
                                                   const float* __restrict__ v, float* __restrict__ out, int B, int nh, int Lq,
                                                   int Lk, int d, int ldq, int ldk, int ldv, int ldo, long bsq, long bsk,
                                                   long bsv, long bso, const float* __restrict__ kmask, int ldmask,
-                                                  int kv_group, float scale, float mask_inf, const int* __restrict__ nkeys_dev,
+                                                  const float* __restrict__ kbias, int kv_group, float scale, float mask_inf, const int* __restrict__ nkeys_dev,
                                                   const float* __restrict__ rpr_k, const float* __restrict__ rpr_v, int max_rel,
                                                   int q_pos0, const int* __restrict__ q_pos_dev) {
   extern __shared__ float sm[];
@@ -714,6 +714,7 @@ __global__ void __launch_bounds__(256) k_f32_attn(const float* __restrict__ q, c
           s = s + s2;
         }
         if (kmask != nullptr) s = s + (1.0f - kmask[(size_t)bk * ldmask + j]) * (-mask_inf);
+        if (kbias != nullptr) s = s + kbias[(size_t)bk * ldmask + j];      // L0Drop: log count, exp(l + log c) = exp(l) c
         sp[j] = s;
       }
       mx = fmaxf(mx, s);
@@ -755,10 +756,14 @@ __global__ void __launch_bounds__(256) k_f32_attn(const float* __restrict__ q, c
   }
 }
 
-extern "C" int zk_f32_attn(const float* q, const float* k, const float* v, float* out, int B, int nh, int Lq, int Lk, int d,
-                           int ldq, int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso, const float* kmask,
-                           int ldmask, int kv_group, float scale, float mask_inf, const int* nkeys_dev, const float* rpr_k,
-                           const float* rpr_v, int max_rel, int q_pos0, const int* q_pos_dev, hipStream_t stream) {
+// zk_f32_attn_kb: kbias fp32 [B / kv_group, ldmask] (may be NULL) is added to the score of key j next to the mask term
+// (transformer_l0drop's count-weighted softmax); zk_f32_attn is the same call without it.
+extern "C" int zk_f32_attn_kb(const float* q, const float* k, const float* v, float* out, int B, int nh, int Lq, int Lk, int d,
+                              int ldq, int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso, const float* kmask,
+                              int ldmask, const float* kbias, int kv_group, float scale, float mask_inf, const int* nkeys_dev,
+                              const float* rpr_k, const float* rpr_v, int max_rel, int q_pos0, const int* q_pos_dev,
+                              hipStream_t stream) {
+  ZK_CHECK_ARG(kbias == nullptr || ldmask >= Lk, "zk_f32_attn_kb: kbias rows of ldmask=%d elements are shorter than Lk=%d", ldmask, Lk);
   ZK_CHECK_ARG(q != nullptr && k != nullptr && v != nullptr && out != nullptr && nh >= 1 && Lq >= 1 && Lk >= 1 && d >= 4 &&
                d % 4 == 0 && kv_group >= 1, "zk_f32_attn: bad shape (nh=%d Lq=%d Lk=%d d=%d)", nh, Lq, Lk, d);
   ZK_CHECK_ARG(ldk % 4 == 0 && bsk % 4 == 0 && (((uintptr_t)k) & 15) == 0, "zk_f32_attn: keys must be 16-byte aligned rows");
@@ -769,10 +774,18 @@ extern "C" int zk_f32_attn(const float* q, const float* k, const float* v, float
   if (B <= 0) return 0;
   const long waves = (long)B * nh * Lq;
   hipLaunchKernelGGL(k_f32_attn, dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, stream, q, k, v, out, B, nh, Lq, Lk, d, ldq,
-                     ldk, ldv, ldo, bsq, bsk, bsv, bso, kmask, ldmask, kv_group, scale, mask_inf, nkeys_dev, rpr_k, rpr_v, max_rel,
-                     q_pos0, q_pos_dev);
+                     ldk, ldv, ldo, bsq, bsk, bsv, bso, kmask, ldmask, kbias, kv_group, scale, mask_inf, nkeys_dev, rpr_k, rpr_v,
+                     max_rel, q_pos0, q_pos_dev);
   ZK_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int zk_f32_attn(const float* q, const float* k, const float* v, float* out, int B, int nh, int Lq, int Lk, int d,
+                           int ldq, int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso, const float* kmask,
+                           int ldmask, int kv_group, float scale, float mask_inf, const int* nkeys_dev, const float* rpr_k,
+                           const float* rpr_v, int max_rel, int q_pos0, const int* q_pos_dev, hipStream_t stream) {
+  return zk_f32_attn_kb(q, k, v, out, B, nh, Lq, Lk, d, ldq, ldk, ldv, ldo, bsq, bsk, bsv, bso, kmask, ldmask, nullptr, kv_group,
+                        scale, mask_inf, nkeys_dev, rpr_k, rpr_v, max_rel, q_pos0, q_pos_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ average attention (decode)

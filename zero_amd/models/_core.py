@@ -54,6 +54,9 @@ class TransformerCore(object):
         # sub-layer = cross-attention + averaged v_map(query) (func.py:258-275), then the FFN
         self.fuse = model_name == "transformer_fuse"
         self.cross = "fuse_attention" if self.fuse else "cross_attention"
+        # transformer_l0drop (decode only): the layers of `transformer`; encoding_fn prunes the encoder output
+        # (models/_l0drop.py) and the cross-attention weighs the counting slot (kbias)
+        self.l0drop = model_name == "transformer_l0drop"
         if self.aan and [s.lower() for s in params.strategies] != ["aan"]:
             raise NotImplementedError("Not supported: {}".format(params.strategies))
         shared = params.shared_source_target_embedding

@@ -29,6 +29,7 @@ import torch
 from zero_amd.func import Mat
 from zero_amd.models._factory import get_core
 from zero_amd.models import _decode_f32 as _f32
+from zero_amd.models import _l0drop as _l0
 from zero_amd.utils import dtype as zdtype
 
 F32 = torch.float32
@@ -83,6 +84,8 @@ def _graph_pointers(state, book):
         b = e.bufs.get(nm)
         ptrs.append(b.data_ptr() if b is not None else 0)
     ptrs += [m.ptr for _, m in sorted(state.get("wt", {}).items())]
+    if state.get("kbias") is not None:          # transformer_l0drop: the log-count bias of the cross-attention keys
+        ptrs.append(state["kbias"].data_ptr())
     return tuple(ptrs) + (tuple(book) if book is not None else ())
 
 
@@ -311,6 +314,9 @@ def _cross_unfused(core, e, hp, state, lay, x, p, pre, l, time, time_dev):
 
 def make_infer_fns(params, model_name):
     hp = params
+    if model_name == "transformer_l0drop" and hp.search_mode != "cache":
+        raise NotImplementedError("transformer_l0drop decodes with search_mode=cache only (the other mode re-runs the "
+                                  "training-path decoder, which this model does not have here)")
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)
@@ -318,6 +324,12 @@ def make_infer_fns(params, model_name):
         K = hp.beam_size if beam_size is None else beam_size
         import os
         pad = max(1, int(os.environ.get("ZERO_HIP_DECODE_PAD_LEN", "8")))
+        if core.l0drop and not _f32.wanted(hp) and not _fuse_att_ok(core, hp, K):
+            # nothing here depends on the data: refuse before the encoder pass
+            raise ValueError("transformer_l0drop in bf16 decodes through the fused attention launch only "
+                             "(ZERO_HIP_DECODE_FUSE_ATT not 0, a head size of 64 -- got %d -- and a hidden size that is a "
+                             "power of two in 128 .. 2048 -- got %d); decode_dtype=float32 has none of these limits"
+                             % (core.d, core.H))
         if _f32.wanted(hp):
             # the fp32 mode (round 5): fp32 masters, activations and caches through zk_f32_* (models/_decode_f32.py)
             from zero_amd.models._core import trim_columns
@@ -337,10 +349,15 @@ def make_infer_fns(params, model_name):
             batch = core.upload(source)
         B, Ls = batch["B"], batch["Ls"]
         enc, smask = core.encode(batch, False, False)
-        enc_keep = e.mat("dc.enc", B * Ls, H)
-        enc_keep.t.copy_(enc.t)
-        mask_keep = e.buf("dc.smask", (B, Ls), F32)
-        mask_keep.copy_(smask)
+        kbias = None
+        if core.l0drop:
+            # the pruned memory, its mask and its length stand in for the encoder output from here on (models/_l0drop.py)
+            enc_keep, mask_keep, Ls, kbias = _l0.prune(core, enc, smask, B, Ls, pad, False)
+        else:
+            enc_keep = e.mat("dc.enc", B * Ls, H)
+            enc_keep.t.copy_(enc.t)
+            mask_keep = e.buf("dc.smask", (B, Ls), F32)
+            mask_keep.copy_(smask)
         if max_steps is None:
             src_len = (np.asarray(source.cpu() if torch.is_tensor(source) else source) != 0).sum(1)
             max_steps = -(-(int(src_len.max()) + hp.decode_length + 2) // pad) * pad
@@ -349,6 +366,8 @@ def make_infer_fns(params, model_name):
         state.update({"_core": core, "B": B, "K": K, "BK": BK, "Ls": Ls, "Tmax": max_steps,
                       "encodes": enc_keep, "mask": mask_keep, "time_filled": 0,
                       "decoder": {"state": {}}})
+        if kbias is not None:
+            state["kbias"] = kbias
         for l in range(hp.num_decoder_layer):
             p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
             kv = e.mat("dc%d.kv" % l, B * Ls, 2 * H)
@@ -377,6 +396,11 @@ def make_infer_fns(params, model_name):
                     for m in maps:
                         nm = "decoder/layer_%d/%s/dot_attention/%s/W_0_0" % (l, blk, m)
                         state["wt"][nm] = _transposed(core, nm)
+        if core.l0drop and not state["wt"]:
+            raise ValueError("transformer_l0drop in bf16 decodes through the fused attention launch only: its workgroup "
+                             "keeps the scores of max(memory slots, cache positions) = %d keys in LDS, at most 1024 of them "
+                             "and within the 160 KiB of a CU at hidden size %d; decode_dtype=float32 has no such limit"
+                             % (max(Ls, max_steps), H))
         if core.aan or core.fuse:
             e.zero(e.buf("dc.aan.0", (nl, BK, H), F32))
             e.buf("dc.aan.1", (nl, BK, H), F32)
@@ -542,10 +566,14 @@ def make_infer_fns(params, model_name):
             la = ln_args(pro) or (x_in.ptr, None, None, None, None, H, eps, None, None, None, 0, 0, None, None, None,
                                   1.0, None)
             Wq, Wo = state["wt"][p + "q_map/W_0_0"], state["wt"][p + "o_map/W_0_0"]
-            e.lib.call("zk_dec_cross", *la, Wq.ptr, Wq.ld, core.b(p + "q_map/b_0").data_ptr(), lay["mk"].ptr,
-                       lay["mv"].ptr, lay["mk"].ld, lay["mv"].ld, Ls * 2 * H, Ls * 2 * H, state["mask"].data_ptr(), Ls,
-                       Wo.ptr, Wo.ld, parts.data_ptr(), B, K, nh, Ls, float(d) ** -0.5, zdtype.inf(),
-                       *(rpr_tabs(p) + (0 if time_dev is not None else time, tdev)), e.stream)
+            tail = (Wo.ptr, Wo.ld, parts.data_ptr(), B, K, nh, Ls, float(d) ** -0.5, zdtype.inf()) + rpr_tabs(p) + \
+                (0 if time_dev is not None else time, tdev, e.stream)
+            head = la + (Wq.ptr, Wq.ld, core.b(p + "q_map/b_0").data_ptr(), lay["mk"].ptr, lay["mv"].ptr, lay["mk"].ld,
+                         lay["mv"].ld, Ls * 2 * H, Ls * 2 * H, state["mask"].data_ptr(), Ls)
+            if core.l0drop:       # the counting slot's weight (zk_dec_cross_kb)
+                e.lib.call("zk_dec_cross_kb", *head, state["kbias"].data_ptr(), *tail)
+            else:
+                e.lib.call("zk_dec_cross", *head, *tail)
 
         def dec_self(x_in, pro, p, lay, parts):
             la = ln_args(pro) or (x_in.ptr, None, None, None, None, H, eps, None, None, None, 0, 0, None, None, None,

@@ -76,17 +76,22 @@ class _Ops(object):
         return out
 
     def attn(self, q, k, v, out, B, Lq, Lk, bsq, bsk, bsv, kmask=None, ldmask=0, kv_group=1, nkeys_dev=None, rpr=None,
-             q_pos0=0, q_pos_dev=None):
-        """rpr: attention scope prefix (".../dot_attention/") whose rpr_keys / rpr_values tables take part, or None."""
+             q_pos0=0, q_pos_dev=None, kbias=None):
+        """rpr: attention scope prefix (".../dot_attention/") whose rpr_keys / rpr_values tables take part, or None.
+        kbias: fp32 [.., ldmask] added to the scores (transformer_l0drop's log counts: zk_f32_attn_kb), or None."""
         rk = rv = None
         if rpr is not None:
             rk = self.core.store.w(rpr + "rpr_keys/embeddings").data_ptr()
             rv = self.core.store.w(rpr + "rpr_values/embeddings").data_ptr()
-        self.lib.call("zk_f32_attn", q.ptr, k.ptr, v.ptr, out.ptr, B, self.nh, Lq, Lk, self.d, q.ld, k.ld, v.ld, out.ld,
-                      int(bsq), int(bsk), int(bsv), int(Lq * out.ld), kmask.data_ptr() if kmask is not None else None,
-                      int(ldmask), int(kv_group), float(self.d) ** -0.5, zdtype.inf(),
-                      nkeys_dev.data_ptr() if nkeys_dev is not None else None, rk, rv, int(self.core.hp.max_relative_position),
-                      int(q_pos0), q_pos_dev.data_ptr() if q_pos_dev is not None else None, self.e.stream)
+        head = (q.ptr, k.ptr, v.ptr, out.ptr, B, self.nh, Lq, Lk, self.d, q.ld, k.ld, v.ld, out.ld, int(bsq), int(bsk), int(bsv),
+                int(Lq * out.ld), kmask.data_ptr() if kmask is not None else None, int(ldmask))
+        tail = (int(kv_group), float(self.d) ** -0.5, zdtype.inf(), nkeys_dev.data_ptr() if nkeys_dev is not None else None,
+                rk, rv, int(self.core.hp.max_relative_position), int(q_pos0),
+                q_pos_dev.data_ptr() if q_pos_dev is not None else None, self.e.stream)
+        if kbias is not None:
+            self.lib.call("zk_f32_attn_kb", *head, kbias.data_ptr(), *tail)
+        else:
+            self.lib.call("zk_f32_attn", *head, *tail)
         return out
 
     def ln_fused(self, x, y, scope, out, gate=None, aan_next=None, time=0, time_dev=None):
@@ -200,10 +205,16 @@ def encoding_state(core, hp, source, K, max_steps, state_cls, pad, trim_columns)
         batch = core.upload(source)
     B, Ls = batch["B"], batch["Ls"]
     enc, smask = encode(core, hp, batch)
-    enc_keep = o.mat("enc", B * Ls, H)
-    enc_keep.t.copy_(enc.t)
-    mask_keep = e.buf("dq.smask", (B, Ls), F32)
-    mask_keep.copy_(smask)
+    kbias = None
+    if core.l0drop:
+        # the pruned memory, its mask and its length stand in for the encoder output from here on (models/_l0drop.py)
+        from zero_amd.models import _l0drop
+        enc_keep, mask_keep, Ls, kbias = _l0drop.prune(core, enc, smask, B, Ls, pad, True)
+    else:
+        enc_keep = o.mat("enc", B * Ls, H)
+        enc_keep.t.copy_(enc.t)
+        mask_keep = e.buf("dq.smask", (B, Ls), F32)
+        mask_keep.copy_(smask)
     if max_steps is None:
         src_len = (np.asarray(source.cpu() if torch.is_tensor(source) else source) != 0).sum(1)
         max_steps = -(-(int(src_len.max()) + hp.decode_length + 2) // pad) * pad
@@ -211,6 +222,8 @@ def encoding_state(core, hp, source, K, max_steps, state_cls, pad, trim_columns)
     state = state_cls()
     state.update({"_core": core, "B": B, "K": K, "BK": BK, "Ls": Ls, "Tmax": max_steps, "encodes": enc_keep,
                   "mask": mask_keep, "time_filled": 0, "decoder": {"state": {}}, "f32": True, "wt": {}})
+    if kbias is not None:
+        state["kbias"] = kbias
     nl = hp.num_decoder_layer
     for l in range(nl):
         p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
@@ -313,7 +326,7 @@ def step_cache(target, state, time, time_dev, hp):
         att = o.mat("att", BK, H)
         # (relative positions, transformer_rpr.py:167-169: the query sits at position `time` against the SOURCE positions)
         o.attn(qm, lay["mk"], lay["mv"], att, BK, 1, Ls, H, Ls * 2 * H, Ls * 2 * H, kmask=state["mask"], ldmask=Ls, kv_group=K,
-               rpr=p if core.rpr else None, q_pos0=t_host, q_pos_dev=time_dev)
+               rpr=p if core.rpr else None, q_pos0=t_host, q_pos_dev=time_dev, kbias=state.get("kbias"))
         if core.fuse:
             # func.py:258-275: v_q = v_map(query); aan_o = (v_q + cache) / (time + 1); cache += v_q; o += aan_o
             vq = o.mat("vq", BK, H)

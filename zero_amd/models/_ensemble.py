@@ -85,6 +85,10 @@ def check_members(total_params):
     M = len(total_params)
     if M == 0:
         raise ZeroHipError("ensemble decoding needs at least one member (got none)")
+    for i, p in enumerate(total_params):
+        if str(p.model_name).lower() == "transformer_l0drop":
+            raise ZeroHipError("ensemble member %d is a transformer_l0drop: its pruned memory has a length of its own per "
+                               "batch, the members of an ensemble step share one shape" % i)
     if M > max_members():
         raise ZeroHipError("ensemble decoding combines at most %d members per step (zk_ensemble_logprob); got %d"
                            % (max_members(), M))

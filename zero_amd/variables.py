@@ -56,7 +56,8 @@ def _ffn_specs(prefix, H, F, with_ln=True):
 def variable_specs(params, model_name):
     """[(name, logical_shape, kind, layer)] in the reference's creation order
     (transformer.py:16-33,88-102,184-192; transformer_aan.py:165-192;
-    transformer_rpr.py:54-55,144-146,167-169; transformer_fuse.py:131-160)."""
+    transformer_rpr.py:54-55,144-146,167-169; transformer_fuse.py:131-160; transformer_l0drop.py:250: the
+    source_pruning pair is created by the decoder after its embedding lookup and before its first layer)."""
     H, E, F = params.hidden_size, params.embed_size, params.filter_size
     if H != E:
         raise ValueError("hidden_size must equal embed_size for the Transformer models "
@@ -76,6 +77,9 @@ def variable_specs(params, model_name):
         specs += [(n, s, k, l) for n, s, k in _ffn_specs(pre + "/feed_forward", H, F)]
     if not shared:
         specs.append(("tgt_embedding", (Vt, E), "embed", None))
+    if model_name == "transformer_l0drop":
+        # log alpha_j = encodes[j] . W + b (func.linear(source_memory, 1, scope="source_pruning")); otherwise `transformer`
+        specs += [("source_pruning/W_0_0", (H, 1), "w", None), ("source_pruning/b_0", (1,), "zeros", None)]
     for l in range(params.num_decoder_layer):
         pre = "decoder/layer_%d" % l
         if fuse:      # transformer_fuse.py:131-160: merged attention sub-layer + FFN
