@@ -636,6 +636,30 @@ int zk_f32_attn_kb(const float* q, const float* k, const float* v, float* out, i
                    const float* kbias, int kv_group, float scale, float mask_inf, const int* nkeys_dev, const float* rpr_k,
                    const float* rpr_v, int max_rel, int q_pos0, const int* q_pos_dev, zk_stream_t stream);
 
+/* ---- transformer_rela at inference (modules/rela.py:13-109; models/transformer_rela.py:48, 134, 154 call it in place
+ * of func.dot_attention): ReLU attention weights and a gated RMSNorm over ALL H channels of the combined heads.
+ *   zk_rela_attn      bf16 q / k / v / out, fp32 arithmetic;  zk_f32_rela_attn   fp32 throughout.
+ *                  Operands as zk_f32_attn: B query sentences of Lq rows, nh heads of d channels, Lk keys; ld* row strides
+ *                  and bs* sentence strides in elements (q / k / v may be column slices of one matrix); sentence b reads
+ *                  the keys / values / mask of sentence b / kv_group (B a multiple of kv_group); kmask fp32
+ *                  [B / kv_group, ldmask], non-zero = the key takes part (may be NULL); nkeys_dev (may be NULL): the
+ *                  number of valid keys is min(*nkeys_dev + 1, Lk), read on the device, and no later key slot is read.
+ *                  post_scale / post_gate: the fp32 MASTERS of .../dot_attention/post/{scale, gate} [H] in both forms.
+ *                    s_j = (q * qscale) . k_j  per head                                 (rela.py:60-63)
+ *                    w_j = relu(s_j) * (kmask_j != 0)      multiplied, never added      (rela.py:66-72)
+ *                    c   = concat over the heads of sum_j w_j v_j                       (rela.py:77-78)
+ *                    out = post_scale * c * rsqrt(mean over H of c^2 + eps) * sigmoid(post_gate * c)   (rela.py:95-109)
+ *                  A row without a positive score gives exact zeros.  bf16 form: d % 8 == 0, d <= 128, H <= 2048, key and
+ *                  output rows 16-byte aligned; fp32 form: any d <= 256, H <= 2048.  Otherwise -1 and a message. */
+int zk_rela_attn(const void* q, const void* k, const void* v, void* out, int B, int nh, int Lq, int Lk, int d, int ldq, int ldk,
+                 int ldv, int ldo, long bsq, long bsk, long bsv, long bso, const float* kmask, int ldmask, int kv_group,
+                 float qscale, const int* nkeys_dev, const float* post_scale, const float* post_gate, float eps,
+                 zk_stream_t stream);
+int zk_f32_rela_attn(const float* q, const float* k, const float* v, float* out, int B, int nh, int Lq, int Lk, int d, int ldq,
+                     int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso, const float* kmask, int ldmask,
+                     int kv_group, float qscale, const int* nkeys_dev, const float* post_scale, const float* post_gate,
+                     float eps, zk_stream_t stream);
+
 /* hipGraph plumbing: capture a sequence of the calls above once, replay per step */
 int zk_graph_begin(zk_stream_t stream);
 int zk_graph_end(zk_stream_t stream, void** exec_out);

@@ -610,6 +610,16 @@ class Engine(object):
             self.gemm_grouped([(pb.cols_slice(h * nrp, (h + 1) * nrp), rv, out.cols_slice(h * d, (h + 1) * d), T, d, nrp,
                                 None, out.cols_slice(h * d, (h + 1) * d)) for h in range(nh)], 0, 0, tile=64)
 
+    def rela_attn_fwd(self, q, k, v, out, B, nh, Lq, Lk, d, post_scale, post_gate, kmask=None, bsq=0, bsk=0, bsv=0,
+                      kv_group=1, nkeys_dev=None):
+        """modules/rela.py:56-81 (zk_rela_attn): bf16 q / k / v / out Mats; post_scale / post_gate fp32 [H]; kmask fp32
+        [B / kv_group, Lk] (non-zero = valid key); bs* = sentence strides in elements (0: Lq or Lk rows);
+        nkeys_dev: int32 on the device, the keys 0 .. *nkeys_dev are valid."""
+        self.lib.call("zk_rela_attn", q.ptr, k.ptr, v.ptr, out.ptr, B, nh, Lq, Lk, d, q.ld, k.ld, v.ld, out.ld,
+                      bsq or Lq * q.ld, bsk or Lk * k.ld, bsv or Lk * v.ld, Lq * out.ld, hip.ptr(kmask), Lk, kv_group,
+                      float(d) ** -0.5, hip.ptr(nkeys_dev), post_scale.data_ptr(), post_gate.data_ptr(),
+                      float(zdtype.epsilon()), self.stream)
+
     def attn_bwd(self, q, k, v, out, dout, lse, dq, dk, dv, B, nh, Lq, Lk, d, kmask=None, causal=False,
                  rpr_k=None, rpr_v=None, drpr_k=None, drpr_v=None, max_rel=0, drop_p=0.0, sid=0, impl=None,
                  defer_tables=None, oproj=None):

@@ -57,6 +57,9 @@ class TransformerCore(object):
         # transformer_l0drop (decode only): the layers of `transformer`; encoding_fn prunes the encoder output
         # (models/_l0drop.py) and the cross-attention weighs the counting slot (kbias)
         self.l0drop = model_name == "transformer_l0drop"
+        # transformer_rela (decode only): every dot_attention is ReLU attention + gated RMSNorm (modules/rela.py); the
+        # attention sub-layers run projection, zk_rela_attn, o_map + LayerNorm, never the fused softmax launches
+        self.rela = model_name == "transformer_rela"
         if self.aan and [s.lower() for s in params.strategies] != ["aan"]:
             raise NotImplementedError("Not supported: {}".format(params.strategies))
         shared = params.shared_source_target_embedding
@@ -318,6 +321,11 @@ class TransformerCore(object):
         qkv = e.mat(tag + ".qkv", T, 3 * H)
         att = e.mat(tag + ".att", T, H)
         lse = e.buf(tag + ".lse", (B * self.nh * L,), F32) if save else None
+        if self.rela:
+            # (inference only: the ReLU weights and the gated RMSNorm have no backward here, nothing is saved)
+            self._linear(x, p + "qkv_map", qkv)
+            self._rela_attn(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, B, L, L, p, kmask)
+            return self._out_ln(att, p + "o_map", x, scope, tag, save, 0.0, sid0 + 1)
         rk = self.store.s(p + "rpr_keys/embeddings") if self.rpr else None
         rv = self.store.s(p + "rpr_values/embeddings") if self.rpr else None
         fuse_proj = self.proj_attn and self._attn_out_ln_ok(B, L, L)
@@ -333,6 +341,12 @@ class TransformerCore(object):
                    self.nh, L, L, self.d, kmask=kmask, causal=causal, rpr_k=rk, rpr_v=rv,
                    max_rel=hp.max_relative_position, drop_p=hp.attention_dropout if train else 0.0, sid=sid0)
         return self._out_ln(att, p + "o_map", x, scope, tag, save, hp.residual_dropout if train else 0.0, sid0 + 1)
+
+    def _rela_attn(self, q, k, v, att, B, Lq, Lk, p, kmask, **kw):
+        """modules/rela.py:56-81 on the projections: ReLU weights, masked by multiplication, and the gated RMSNorm over the
+        combined heads with the fp32 masters of p + post/{scale, gate} (zk_rela_attn)."""
+        self.eng.rela_attn_fwd(q, k, v, att, B, self.nh, Lq, Lk, self.d, self.b(p + "post/scale"), self.b(p + "post/gate"),
+                               kmask=kmask, **kw)
 
     def _cross_kv_grouped(self, mem, n_layers):
         """k_map / v_map of EVERY decoder layer read only the encoder output (func.py:206-216): one
@@ -353,7 +367,7 @@ class TransformerCore(object):
         hp = self.hp
         p = scope + "/dot_attention/"
         q = e.mat(tag + ".q", x.rows, H)
-        fuse_proj = self.proj_attn and fuse_tmask is None and self._attn_out_ln_ok(B, Lq, Lk)
+        fuse_proj = self.proj_attn and fuse_tmask is None and self._attn_out_ln_ok(B, Lq, Lk) and not self.rela
         if not fuse_proj:
             self._linear(x, p + "q_map", q)
         kv = e.mat(tag + ".kv", mem.rows, 2 * H)
@@ -361,6 +375,9 @@ class TransformerCore(object):
             self._linear(mem, p + "k_map", kv.cols_slice(0, H))
             self._linear(mem, p + "v_map", kv.cols_slice(H, 2 * H))
         att = e.mat(tag + ".att", x.rows, H)
+        if self.rela:
+            self._rela_attn(q, kv.cols_slice(0, H), kv.cols_slice(H, 2 * H), att, B, Lq, Lk, p, kmask)
+            return self._out_ln(att, p + "o_map", x, scope, tag, save, 0.0, sid0 + 1)
         lse = e.buf(tag + ".lse", (B * self.nh * Lq,), F32) if save else None
         rk = self.store.s(p + "rpr_keys/embeddings") if self.rpr else None
         rv = self.store.s(p + "rpr_values/embeddings") if self.rpr else None

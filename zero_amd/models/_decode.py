@@ -230,7 +230,7 @@ def _fuse_att_ok(core, hp, K):
     """The attention sub-layers of a cached decode step as one launch per (sentence, head) (zk_dec_cross / zk_dec_self)."""
     import os
     return (os.environ.get("ZERO_HIP_DECODE_FUSE_ATT", "1") != "0" and core.d == 64
-            and core.H in (128, 256, 512, 1024, 2048) and not core.fuse
+            and core.H in (128, 256, 512, 1024, 2048) and not core.fuse and not core.rela
             and (not core.rpr or hp.max_relative_position <= 31)
             and (not core.aan or os.environ.get("ZERO_HIP_DECODE_FUSE_LN", "1") != "0") and not hp.use_ffn)
 
@@ -296,9 +296,14 @@ def _cross_unfused(core, e, hp, state, lay, x, p, pre, l, time, time_dev):
     att = e.mat("dc.att", BK, H)
     rk = core.store.s(p + "rpr_keys/embeddings") if core.rpr else None
     rv = core.store.s(p + "rpr_values/embeddings") if core.rpr else None
-    e.attn_fwd(q, lay["mk"], lay["mv"], att, None, BK, nh, 1, Ls, d, kmask=state["mask"], causal=False,
-               q_pos0=time if time is not None else 0, rpr_k=rk, rpr_v=rv, max_rel=hp.max_relative_position, bsq=H,
-               bsk=Ls * 2 * H, bsv=Ls * 2 * H, kv_group=K, pos_dev=time_dev, pos_flags=1)
+    if core.rela:
+        # rela.py:44-81: the K beam rows of a sentence share one pass over its keys / values; the source mask multiplies
+        core._rela_attn(q, lay["mk"], lay["mv"], att, BK, 1, Ls, p, state["mask"], bsq=H, bsk=Ls * 2 * H, bsv=Ls * 2 * H,
+                        kv_group=K)
+    else:
+        e.attn_fwd(q, lay["mk"], lay["mv"], att, None, BK, nh, 1, Ls, d, kmask=state["mask"], causal=False,
+                   q_pos0=time if time is not None else 0, rpr_k=rk, rpr_v=rv, max_rel=hp.max_relative_position, bsq=H,
+                   bsk=Ls * 2 * H, bsv=Ls * 2 * H, kv_group=K, pos_dev=time_dev, pos_flags=1)
     if core.fuse:
         # func.py:258-272: v_q = v_map(query); cache += v_q; o += cache / (time + 1)
         vq = e.mat("dc.vq", BK, H)
@@ -317,6 +322,9 @@ def make_infer_fns(params, model_name):
     if model_name == "transformer_l0drop" and hp.search_mode != "cache":
         raise NotImplementedError("transformer_l0drop decodes with search_mode=cache only (the other mode re-runs the "
                                   "training-path decoder, which this model does not have here)")
+    if model_name == "transformer_rela" and hp.search_mode != "cache":
+        raise NotImplementedError("transformer_rela decodes with search_mode=cache only: search_mode=dev re-runs the "
+                                  "training-path decoder, which this model does not have here")
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)
@@ -329,6 +337,12 @@ def make_infer_fns(params, model_name):
             raise ValueError("transformer_l0drop in bf16 decodes through the fused attention launch only "
                              "(ZERO_HIP_DECODE_FUSE_ATT not 0, a head size of 64 -- got %d -- and a hidden size that is a "
                              "power of two in 128 .. 2048 -- got %d); decode_dtype=float32 has none of these limits"
+                             % (core.d, core.H))
+        if core.rela and not _f32.wanted(hp) and (core.d % 8 != 0 or core.d > 128 or core.H > 2048):
+            # nothing here depends on the data: refuse before the encoder pass
+            raise ValueError("transformer_rela in bf16 needs a head size that is a multiple of 8 and at most 128 -- got %d -- "
+                             "and a hidden size of at most 2048 -- got %d (zk_rela_attn reads keys 16 bytes at a time and "
+                             "keeps four rows of H floats in LDS); decode_dtype=float32 takes any head size"
                              % (core.d, core.H))
         if _f32.wanted(hp):
             # the fp32 mode (round 5): fp32 masters, activations and caches through zk_f32_* (models/_decode_f32.py)
@@ -696,11 +710,18 @@ def make_infer_fns(params, model_name):
                 att = e.mat("dc.att", BK, H)
                 rk = core.store.s(p + "rpr_keys/embeddings") if core.rpr else None
                 rv = core.store.s(p + "rpr_values/embeddings") if core.rpr else None
-                e.attn_fwd(qkv.cols_slice(0, H), Mat(lay["k"], BK * Tmax, H), Mat(lay["v"], BK * Tmax, H), att,
-                           None, BK, nh, 1, Tmax if time_dev is not None else time + 1, d, kmask=None, causal=False,
-                           q_pos0=0 if time_dev is not None else time, rpr_k=rk,
-                           rpr_v=rv, max_rel=hp.max_relative_position, bsq=3 * H, bsk=Tmax * H, bsv=Tmax * H,
-                           pos_dev=time_dev, pos_flags=3)
+                if core.rela:
+                    # rela.py:37-43, 66-68: the causal bias of a single query is all zeros, so every cached key 0 .. time
+                    # counts and there is no mask; the key count comes from the device at a captured step
+                    core._rela_attn(qkv.cols_slice(0, H), Mat(lay["k"], BK * Tmax, H), Mat(lay["v"], BK * Tmax, H), att, BK,
+                                    1, Tmax if time_dev is not None else time + 1, p, None, bsq=3 * H, bsk=Tmax * H,
+                                    bsv=Tmax * H, nkeys_dev=time_dev)
+                else:
+                    e.attn_fwd(qkv.cols_slice(0, H), Mat(lay["k"], BK * Tmax, H), Mat(lay["v"], BK * Tmax, H), att,
+                               None, BK, nh, 1, Tmax if time_dev is not None else time + 1, d, kmask=None, causal=False,
+                               q_pos0=0 if time_dev is not None else time, rpr_k=rk,
+                               rpr_v=rv, max_rel=hp.max_relative_position, bsq=3 * H, bsk=Tmax * H, bsv=Tmax * H,
+                               pos_dev=time_dev, pos_flags=3)
                 y = e.mat("dc.y", BK, H)
                 core._linear(att, p + "o_map", y)
                 x = core._ln_fwd(x, y, pre + "/self_attention", "dc%d.sa" % l, False, 0.0, 0)

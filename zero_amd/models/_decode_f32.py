@@ -94,6 +94,17 @@ class _Ops(object):
             self.lib.call("zk_f32_attn", *head, *tail)
         return out
 
+    def rela_attn(self, q, k, v, out, B, Lq, Lk, bsq, bsk, bsv, scope, kmask=None, ldmask=0, kv_group=1, nkeys_dev=None):
+        """modules/rela.py:56-81 (zk_f32_rela_attn).  scope: the attention scope prefix (".../dot_attention/") whose
+        post/{scale, gate} normalise the combined heads; the other arguments as attn()."""
+        st = self.core.store
+        self.lib.call("zk_f32_rela_attn", q.ptr, k.ptr, v.ptr, out.ptr, B, self.nh, Lq, Lk, self.d, q.ld, k.ld, v.ld, out.ld,
+                      int(bsq), int(bsk), int(bsv), int(Lq * out.ld), kmask.data_ptr() if kmask is not None else None,
+                      int(ldmask), int(kv_group), float(self.d) ** -0.5,
+                      nkeys_dev.data_ptr() if nkeys_dev is not None else None, st.w(scope + "post/scale").data_ptr(),
+                      st.w(scope + "post/gate").data_ptr(), float(zdtype.epsilon()), self.e.stream)
+        return out
+
     def ln_fused(self, x, y, scope, out, gate=None, aan_next=None, time=0, time_dev=None):
         """zk_f32_ln_fused (round 6): LN(x + y) with row-local neighbours in the same launch.  gate = (z, cat): y is the
         average-attention gate of transformer_aan.py:186-189 and the residual is cat[:, :H] (x, y = None);
@@ -137,8 +148,12 @@ def encode(core, hp, batch):
         qkv = o.mat("enc.qkv", T, 3 * H)
         o.linear(x, p + "qkv_map", qkv)
         att = o.mat("enc.att", T, H)
-        o.attn(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, B, Ls, Ls,
-               Ls * 3 * H, Ls * 3 * H, Ls * 3 * H, kmask=smask, ldmask=Ls, rpr=p if core.rpr else None)
+        if core.rela:
+            o.rela_attn(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, B, Ls, Ls,
+                        Ls * 3 * H, Ls * 3 * H, Ls * 3 * H, p, kmask=smask, ldmask=Ls)
+        else:
+            o.attn(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, B, Ls, Ls,
+                   Ls * 3 * H, Ls * 3 * H, Ls * 3 * H, kmask=smask, ldmask=Ls, rpr=p if core.rpr else None)
         y = o.mat("y", T, H)
         o.linear(att, p + "o_map", y)
         x = o.add_ln(x, y, pre + "/self_attention", o.mat("e%d.sa.o" % l, T, H))
@@ -314,8 +329,12 @@ def step_cache(target, state, time, time_dev, hp):
             kc, vc = Mat(lay["k"], BK * Tmax, H), Mat(lay["v"], BK * Tmax, H)
             # one query per beam row over the positions 0 .. time of ITS cache (no padding mask on the target side,
             # transformer.py:136; causality is the cache's length)
-            o.attn(qkv.cols_slice(0, H), kc, vc, att, BK, 1, Tmax if time_dev is not None else time + 1, 3 * H, Tmax * H,
-                   Tmax * H, nkeys_dev=time_dev, rpr=p if core.rpr else None, q_pos0=t_host, q_pos_dev=time_dev)
+            if core.rela:      # (rela.py:66-68: a single query's causal bias is all zeros -- no mask, the cache's length)
+                o.rela_attn(qkv.cols_slice(0, H), kc, vc, att, BK, 1, Tmax if time_dev is not None else time + 1, 3 * H,
+                            Tmax * H, Tmax * H, p, nkeys_dev=time_dev)
+            else:
+                o.attn(qkv.cols_slice(0, H), kc, vc, att, BK, 1, Tmax if time_dev is not None else time + 1, 3 * H, Tmax * H,
+                       Tmax * H, nkeys_dev=time_dev, rpr=p if core.rpr else None, q_pos0=t_host, q_pos_dev=time_dev)
             y = o.mat("y", BK, H)
             o.linear(att, p + "o_map", y)
             x = o.add_ln(x, y, pre + "/self_attention", o.mat("d%d.sa.o" % l, BK, H))
@@ -325,8 +344,12 @@ def step_cache(target, state, time, time_dev, hp):
         o.linear(x, p + "q_map", qm)
         att = o.mat("att", BK, H)
         # (relative positions, transformer_rpr.py:167-169: the query sits at position `time` against the SOURCE positions)
-        o.attn(qm, lay["mk"], lay["mv"], att, BK, 1, Ls, H, Ls * 2 * H, Ls * 2 * H, kmask=state["mask"], ldmask=Ls, kv_group=K,
-               rpr=p if core.rpr else None, q_pos0=t_host, q_pos_dev=time_dev, kbias=state.get("kbias"))
+        if core.rela:
+            o.rela_attn(qm, lay["mk"], lay["mv"], att, BK, 1, Ls, H, Ls * 2 * H, Ls * 2 * H, p, kmask=state["mask"], ldmask=Ls,
+                        kv_group=K)
+        else:
+            o.attn(qm, lay["mk"], lay["mv"], att, BK, 1, Ls, H, Ls * 2 * H, Ls * 2 * H, kmask=state["mask"], ldmask=Ls,
+                   kv_group=K, rpr=p if core.rpr else None, q_pos0=t_host, q_pos_dev=time_dev, kbias=state.get("kbias"))
         if core.fuse:
             # func.py:258-275: v_q = v_map(query); aan_o = (v_q + cache) / (time + 1); cache += v_q; o += aan_o
             vq = o.mat("vq", BK, H)

@@ -89,6 +89,9 @@ def check_members(total_params):
         if str(p.model_name).lower() == "transformer_l0drop":
             raise ZeroHipError("ensemble member %d is a transformer_l0drop: its pruned memory has a length of its own per "
                                "batch, the members of an ensemble step share one shape" % i)
+        if str(p.model_name).lower() == "transformer_rela":
+            raise NotImplementedError("ensemble member %d is a transformer_rela: the ensemble step is built from the fused "
+                                      "softmax attention launches, which this model does not use; composing it is not built" % i)
     if M > max_members():
         raise ZeroHipError("ensemble decoding combines at most %d members per step (zk_ensemble_logprob); got %d"
                            % (max_members(), M))

@@ -28,7 +28,7 @@ import torch
 ALIGN = 64  # elements; keeps every variable 256-byte (fp32) / 128-byte (bf16) aligned
 
 
-def _attn_specs(prefix, H, self_att, rpr, nrel, d):
+def _attn_specs(prefix, H, self_att, rpr, nrel, d, rela=False):
     p = prefix + "/dot_attention/"
     v = []
     if self_att:
@@ -39,6 +39,10 @@ def _attn_specs(prefix, H, self_att, rpr, nrel, d):
     if rpr:
         v += [(p + "rpr_keys/embeddings", (nrel, d), "w"),
               (p + "rpr_values/embeddings", (nrel, d), "w")]
+    if rela:
+        # modules/rela.py:81, 95-109: gated_rms_norm(scope="post") runs after the projections that feed the attention and
+        # before o_map; scale is ones-initialised, gate is drawn from the scope initialiser like any weight
+        v += [(p + "post/scale", (H,), "ones"), (p + "post/gate", (H,), "w")]
     v += [(p + "o_map/W_0_0", (H, H), "w"), (p + "o_map/b_0", (H,), "zeros"),
           (prefix + "/layer_norm/scale", (H,), "ones"), (prefix + "/layer_norm/offset", (H,), "zeros")]
     return v
@@ -57,7 +61,8 @@ def variable_specs(params, model_name):
     """[(name, logical_shape, kind, layer)] in the reference's creation order
     (transformer.py:16-33,88-102,184-192; transformer_aan.py:165-192;
     transformer_rpr.py:54-55,144-146,167-169; transformer_fuse.py:131-160; transformer_l0drop.py:250: the
-    source_pruning pair is created by the decoder after its embedding lookup and before its first layer)."""
+    source_pruning pair is created by the decoder after its embedding lookup and before its first layer;
+    transformer_rela.py:48,134,154 + modules/rela.py:34-84: `transformer` plus post/{scale,gate} per attention scope)."""
     H, E, F = params.hidden_size, params.embed_size, params.filter_size
     if H != E:
         raise ValueError("hidden_size must equal embed_size for the Transformer models "
@@ -66,6 +71,7 @@ def variable_specs(params, model_name):
     rpr = model_name == "transformer_rpr"
     aan = model_name == "transformer_aan"
     fuse = model_name == "transformer_fuse"
+    rela = model_name == "transformer_rela"
     nrel = 2 * params.max_relative_position + 1
     Vs, Vt = params.src_vocab.size(), params.tgt_vocab.size()
     shared = params.shared_source_target_embedding
@@ -73,7 +79,7 @@ def variable_specs(params, model_name):
              ("bias", (E,), "w", None)]
     for l in range(params.num_encoder_layer):
         pre = "encoder/layer_%d" % l
-        specs += [(n, s, k, l) for n, s, k in _attn_specs(pre + "/self_attention", H, True, rpr, nrel, d)]
+        specs += [(n, s, k, l) for n, s, k in _attn_specs(pre + "/self_attention", H, True, rpr, nrel, d, rela)]
         specs += [(n, s, k, l) for n, s, k in _ffn_specs(pre + "/feed_forward", H, F)]
     if not shared:
         specs.append(("tgt_embedding", (Vt, E), "embed", None))
@@ -95,8 +101,8 @@ def variable_specs(params, model_name):
                       (a + "/layer_norm/scale", (H,), "ones", l),
                       (a + "/layer_norm/offset", (H,), "zeros", l)]
         else:
-            specs += [(n, s, k, l) for n, s, k in _attn_specs(pre + "/self_attention", H, True, rpr, nrel, d)]
-        specs += [(n, s, k, l) for n, s, k in _attn_specs(pre + "/cross_attention", H, False, rpr, nrel, d)]
+            specs += [(n, s, k, l) for n, s, k in _attn_specs(pre + "/self_attention", H, True, rpr, nrel, d, rela)]
+        specs += [(n, s, k, l) for n, s, k in _attn_specs(pre + "/cross_attention", H, False, rpr, nrel, d, rela)]
         specs += [(n, s, k, l) for n, s, k in _ffn_specs(pre + "/feed_forward", H, F)]
     if not shared and not params.shared_target_softmax_embedding:
         specs.append(("softmax_embedding", (Vt, E), "embed", None))
