@@ -660,6 +660,31 @@ int zk_f32_rela_attn(const float* q, const float* k, const float* v, float* out,
                      int kv_group, float qscale, const int* nkeys_dev, const float* post_scale, const float* post_gate,
                      float eps, zk_stream_t stream);
 
+/* ---- transformer_fixup at inference and scoring (modules/fixup.py:15-26 shift_layer / scale_layer, 29-55 ffn_layer;
+ * models/transformer_fixup.py:47-73, 136-189): the Transformer without LayerNorm.  Row-wise element-wise passes over
+ * [rows, H] matrices, row strides ld* in elements.  Every scalar is an fp32 MASTER [1] read ON THE DEVICE at run time (a
+ * captured step graph follows a weight reload); a NULL scalar pointer is the neutral value.
+ *   zk_fixup_residual     the sub-layer boundary (fixup.py:15-26; transformer_fixup.py:59-60, 73, 154-155, 189):
+ *                           x_out[r,c]  = x[r,c] + a * y[r,c]        a = *scale (NULL: 1);  x NULL: 0;  y NULL: 0
+ *                           xs_out[r,c] = b * (x_out[r,c] - o)       o = *offset (NULL: 0);  b = *scale2 (NULL: 1)
+ *                         x / x_out: fp32, the residual stream (may be the same buffer; x_out NULL: not written);
+ *                         y / xs_out: the storage type (bf16; fp32 in zk_f32_fixup_residual); xs_out NULL: not written.
+ *                         xs_out is formed from the unrounded fp32 x_out and rounded once (round to nearest even).
+ *                         One launch is, by its arguments: residual + the next sub-layer's shift; the shift of an embedding
+ *                         (x NULL, the embedding row as y); the encoder's final scale(shift(x)); the decoder's final shift.
+ *   zk_fixup_relu_shift   the middle of the feed-forward layer (fixup.py:45-50): out = relu(h - o) - o, the SAME offset
+ *                         twice (ffn_layer/shift/offset under AUTO_REUSE); out may be h; storage type, fp32 arithmetic.
+ * H (F) and every row stride multiples of 8 elements, every matrix 16-byte aligned; otherwise -1 and a message, and
+ * nothing is launched.  Every product and sum is rounded on its own (no fused multiply-add). */
+int zk_fixup_residual(const float* x, int ldx, const void* y, int ldy, const float* scale, const float* offset,
+                      const float* scale2, float* x_out, int ldxo, void* xs_out, int ldxs, int rows, int H, zk_stream_t stream);
+int zk_f32_fixup_residual(const float* x, int ldx, const float* y, int ldy, const float* scale, const float* offset,
+                          const float* scale2, float* x_out, int ldxo, float* xs_out, int ldxs, int rows, int H,
+                          zk_stream_t stream);
+int zk_fixup_relu_shift(const void* h, int ldh, const float* offset, void* out, int ldo, int rows, int F, zk_stream_t stream);
+int zk_f32_fixup_relu_shift(const float* h, int ldh, const float* offset, float* out, int ldo, int rows, int F,
+                            zk_stream_t stream);
+
 /* hipGraph plumbing: capture a sequence of the calls above once, replay per step */
 int zk_graph_begin(zk_stream_t stream);
 int zk_graph_end(zk_stream_t stream, void** exec_out);

@@ -620,6 +620,23 @@ class Engine(object):
                       float(d) ** -0.5, hip.ptr(nkeys_dev), post_scale.data_ptr(), post_gate.data_ptr(),
                       float(zdtype.epsilon()), self.stream)
 
+    def fixup_residual(self, x, y, scale, offset, scale2, x_out, xs_out):
+        """modules/fixup.py:15-26 at a sub-layer boundary (zk_fixup_residual / zk_f32_fixup_residual, chosen by the dtype of
+        y / xs_out): x_out = x + *scale y; xs_out = *scale2 (x_out - *offset).  x / x_out: fp32 Mats; y / xs_out: Mats of
+        the storage type; scale / offset / scale2: fp32 [1] device tensors.  Any of them may be None."""
+        st = y if y is not None else xs_out
+        m = next(t for t in (xs_out, x_out, y, x) if t is not None)
+        name = "zk_f32_fixup_residual" if st is not None and st.t.dtype == torch.float32 else "zk_fixup_residual"
+        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
+        self.lib.call(name, *mp(x), *mp(y), hip.ptr(scale), hip.ptr(offset), hip.ptr(scale2), *mp(x_out), *mp(xs_out),
+                      m.rows, m.cols, self.stream)
+
+    def fixup_relu_shift(self, h, offset, out):
+        """modules/fixup.py:45-50: out = relu(h - *offset) - *offset (zk_fixup_relu_shift / zk_f32_fixup_relu_shift); out may
+        be h."""
+        name = "zk_f32_fixup_relu_shift" if h.t.dtype == torch.float32 else "zk_fixup_relu_shift"
+        self.lib.call(name, h.ptr, h.ld, hip.ptr(offset), out.ptr, out.ld, h.rows, h.cols, self.stream)
+
     def attn_bwd(self, q, k, v, out, dout, lse, dq, dk, dv, B, nh, Lq, Lk, d, kmask=None, causal=False,
                  rpr_k=None, rpr_v=None, drpr_k=None, drpr_v=None, max_rel=0, drop_p=0.0, sid=0, impl=None,
                  defer_tables=None, oproj=None):

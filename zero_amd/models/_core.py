@@ -60,6 +60,9 @@ class TransformerCore(object):
         # transformer_rela (decode only): every dot_attention is ReLU attention + gated RMSNorm (modules/rela.py); the
         # attention sub-layers run projection, zk_rela_attn, o_map + LayerNorm, never the fused softmax launches
         self.rela = model_name == "transformer_rela"
+        # transformer_fixup (decoding and scoring): no LayerNorm and no bias anywhere; the sub-layer boundaries are
+        # zk_fixup_residual launches on an fp32 residual stream (models/_fixup.py issues the whole schedule)
+        self.fixup = model_name == "transformer_fixup"
         if self.aan and [s.lower() for s in params.strategies] != ["aan"]:
             raise NotImplementedError("Not supported: {}".format(params.strategies))
         shared = params.shared_source_target_embedding
@@ -187,8 +190,8 @@ class TransformerCore(object):
     def _linear(self, x, scope, out, act=0, drop_p=0.0, sid=0):
         """y = x @ W + b  (func.py:14-65)."""
         Wm = self.W(scope + "/W_0_0")
-        self.eng.gemm(x, Wm, out, x.rows, Wm.cols, Wm.rows, 0, 0, bias=self.b(scope + "/b_0"), act=act,
-                      drop_p=drop_p, sid=sid)
+        bias = None if self.fixup else self.b(scope + "/b_0")          # (fixup.py: every linear map is bias=False)
+        self.eng.gemm(x, Wm, out, x.rows, Wm.cols, Wm.rows, 0, 0, bias=bias, act=act, drop_p=drop_p, sid=sid)
 
     def _linear_bwd(self, x, dy, scope, dx=None, residual=None, bias_grad=True, act=0, aux=None, aux_scale=1.0,
                     accumulate=False, ln_next=None):
@@ -668,6 +671,9 @@ class TransformerCore(object):
     def encode(self, batch, train, save):
         """transformer.py:15-84."""
         e, hp, H = self.eng, self.hp, self.H
+        if self.fixup:
+            from zero_amd.models._fixup import Fixup
+            return Fixup(self, False).encode(batch)
         B, Ls = batch["B"], batch["Ls"]
         Ts = B * Ls
         smask = batch.get("smask")
@@ -697,6 +703,9 @@ class TransformerCore(object):
             tmask = e.buf("tmask", (B, Lt), F32)
             w = e.buf("tw", (B, Lt), F32)
             e.target_stats(batch["tgt"], tmask, w, B, Lt, want)
+        if self.fixup:
+            from zero_amd.models._fixup import Fixup
+            return Fixup(self, False).decode_train(batch, enc, smask), tmask, w
         x = e.mat("dec.x0", Tt, H)
         if not self.__dict__.get("_embeds_done"):
             e.embed_fwd(batch["tgt"], self.store.s(self.tgt_emb), self.b("bias"), x, B, Lt, H, shift=True,
@@ -744,10 +753,13 @@ class TransformerCore(object):
         return loss, per_sample, logits, dlogits
 
     def forward(self, batch, train=False, save=False, label_smooth=None):
+        if self.fixup and (train or save):
+            raise NotImplementedError("transformer_fixup has no training path: dropout and the saved activations of a "
+                                      "backward are not built")
         ls = self.hp.label_smooth if label_smooth is None else label_smooth
         # residual + LayerNorm inside the sub-layer output GEMMs (ZERO_HIP_SYNC_LN=0: a launch of their own)
         self._sync_ln = self.sync_ln_mode and self.eng.gemm_impl == 0 and self.H % 64 == 0 and \
-            self.H <= 1024 and self.F % 64 == 0 and self.eng.sync_ln_usable()
+            self.H <= 1024 and self.F % 64 == 0 and not self.fixup and self.eng.sync_ln_usable()
         pair_embeds = self.merge_small and "tgt" in batch
         if self._sync_ln and not pair_embeds:
             self.eng.ln_epoch_bump()          # (else the paired embedding launch below advances the epoch)

@@ -230,7 +230,7 @@ def _fuse_att_ok(core, hp, K):
     """The attention sub-layers of a cached decode step as one launch per (sentence, head) (zk_dec_cross / zk_dec_self)."""
     import os
     return (os.environ.get("ZERO_HIP_DECODE_FUSE_ATT", "1") != "0" and core.d == 64
-            and core.H in (128, 256, 512, 1024, 2048) and not core.fuse and not core.rela
+            and core.H in (128, 256, 512, 1024, 2048) and not core.fuse and not core.rela and not core.fixup
             and (not core.rpr or hp.max_relative_position <= 31)
             and (not core.aan or os.environ.get("ZERO_HIP_DECODE_FUSE_LN", "1") != "0") and not hp.use_ffn)
 
@@ -325,6 +325,10 @@ def make_infer_fns(params, model_name):
     if model_name == "transformer_rela" and hp.search_mode != "cache":
         raise NotImplementedError("transformer_rela decodes with search_mode=cache only: search_mode=dev re-runs the "
                                   "training-path decoder, which this model does not have here")
+
+    if model_name == "transformer_fixup" and hp.search_mode != "cache":
+        raise NotImplementedError("transformer_fixup decodes with search_mode=cache only: the re-encoding decode mode "
+                                  "(search_mode=dev re-runs the encoder and the whole prefix each step) is not built for it")
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)
@@ -543,6 +547,10 @@ def make_infer_fns(params, model_name):
             raise RuntimeError("decode step %d exceeds the allocated cache length %d" % (time, Tmax))
         if state.get("f32"):
             return _f32.step_cache(target, state, time, time_dev, hp)
+        if core.fixup:
+            # launch-per-op: projection, the softmax attention kernels, o_map, zk_fixup_residual (models/_fixup.py)
+            from zero_amd.models._fixup import Fixup
+            return Fixup(core, False).step(target, state, time, time_dev, hp)
         import os as _os
         zf = state["zero_flag"]
         fuse_head = True

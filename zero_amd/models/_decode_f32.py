@@ -62,7 +62,8 @@ class _Ops(object):
     def linear(self, x, scope, out, act=0):
         """func.py:14-65: out = x W + b (act 1: ReLU)."""
         W = self.w(scope + "/W_0_0")
-        self.gemm(x, W, out, x.rows, W.cols, W.rows, 0, self.core.store.w(scope + "/b_0"), act)
+        bias = None if self.core.fixup else self.core.store.w(scope + "/b_0")      # (fixup.py: every linear map is bias=False)
+        self.gemm(x, W, out, x.rows, W.cols, W.rows, 0, bias, act)
         return out
 
     def add_ln(self, x, y, scope, out):
@@ -133,6 +134,9 @@ class _Ops(object):
 
 def encode(core, hp, batch):
     """transformer.py:15-84 in fp32: -> (encoder output Mat [B*Ls, H], source mask fp32 [B, Ls])."""
+    if core.fixup:
+        from zero_amd.models._fixup import Fixup
+        return Fixup(core, True).encode(batch)
     o = _Ops(core)
     e, H = core.eng, core.H
     B, Ls = batch["B"], batch["Ls"]
@@ -273,6 +277,9 @@ def step_cache(target, state, time, time_dev, hp):
     BK, K, B, Ls, Tmax = state["BK"], state["K"], state["B"], state["Ls"], state["Tmax"]
     if time_dev is None and time >= Tmax:
         raise RuntimeError("decode step %d exceeds the allocated cache length %d" % (time, Tmax))
+    if core.fixup:
+        from zero_amd.models._fixup import Fixup
+        return Fixup(core, True).step(target, state, time, time_dev, hp)
     tdev = time_dev.data_ptr() if time_dev is not None else None
     t_host = 0 if time_dev is not None else time
     fold = o.fold

@@ -92,6 +92,9 @@ def check_members(total_params):
         if str(p.model_name).lower() == "transformer_rela":
             raise NotImplementedError("ensemble member %d is a transformer_rela: the ensemble step is built from the fused "
                                       "softmax attention launches, which this model does not use; composing it is not built" % i)
+        if str(p.model_name).lower() == "transformer_fixup":
+            raise NotImplementedError("ensemble member %d is a transformer_fixup: an untested member type (its step takes "
+                                      "the launch-per-op path, the ensemble step is built from the fused launches)" % i)
     if M > max_members():
         raise ZeroHipError("ensemble decoding combines at most %d members per step (zk_ensemble_logprob); got %d"
                            % (max_members(), M))

@@ -57,6 +57,45 @@ def _ffn_specs(prefix, H, F, with_ln=True):
     return v
 
 
+def _fixup_specs(params):
+    """transformer_fixup.py:16-88, 91-203 + modules/fixup.py in creation order.  No LayerNorm and no bias of a linear map
+    anywhere; per sub-layer a shift/offset [1] in front and a scale/scale [1] behind.  Kinds: "fx6" / "fx2" = the scope
+    initialiser times L^(-1/6) / L^(-1/2), L = 2 NE + 3 ND (fixup.py:39-40, 91-93); o_map, the FFN output and a separate
+    softmax_embedding start at zero (fixup.py:52, 185; transformer_fixup.py:199-201): "w_zeros" / "embed_zeros", which
+    initial_values draws like their non-zero kind and discards, so that every drawn matrix of this model is the matrix
+    `transformer` draws from the same seed times its factor."""
+    H, E, F = params.hidden_size, params.embed_size, params.filter_size
+    Vs, Vt = params.src_vocab.size(), params.tgt_vocab.size()
+    shared = params.shared_source_target_embedding
+
+    def att(prefix, maps, l):
+        p = prefix + "/dot_attention/"
+        return [(prefix + "/shift/offset", (1,), "zeros", l)] + \
+            [(p + m + "/W_0_0", (H, w), "fx6", l) for m, w in maps] + \
+            [(p + "o_map/W_0_0", (H, H), "w_zeros", l), (prefix + "/scale/scale", (1,), "ones", l)]
+
+    def ffn(prefix, l):
+        p = prefix + "/ffn_layer/"
+        return [(p + "shift/offset", (1,), "zeros", l), (p + "enlarge/W_0_0", (H, F), "fx2", l),
+                (p + "output/W_0_0", (F, H), "w_zeros", l), (p + "scale/scale", (1,), "ones", l)]
+    specs = [("embedding" if shared else "src_embedding", (Vs, E), "embed", None), ("bias", (E,), "w", None)]
+    for l in range(params.num_encoder_layer):
+        pre = "encoder/layer_%d" % l
+        specs += att(pre + "/self_attention", [("qkv_map", 3 * H)], l) + ffn(pre + "/feed_forward", l)
+    specs += [("encoder/shift/offset", (1,), "zeros", None), ("encoder/scale/scale", (1,), "ones", None)]
+    if not shared:
+        specs.append(("tgt_embedding", (Vt, E), "embed", None))
+    for l in range(params.num_decoder_layer):
+        pre = "decoder/layer_%d" % l
+        specs += att(pre + "/self_attention", [("qkv_map", 3 * H)], l)
+        specs += att(pre + "/cross_attention", [("q_map", H), ("k_map", H), ("v_map", H)], l)
+        specs += ffn(pre + "/feed_forward", l)
+    specs.append(("decoder/shift/offset", (1,), "zeros", None))
+    if not shared and not params.shared_target_softmax_embedding:
+        specs.append(("softmax_embedding", (Vt, E), "embed_zeros", None))
+    return specs
+
+
 def variable_specs(params, model_name):
     """[(name, logical_shape, kind, layer)] in the reference's creation order
     (transformer.py:16-33,88-102,184-192; transformer_aan.py:165-192;
@@ -67,6 +106,8 @@ def variable_specs(params, model_name):
     if H != E:
         raise ValueError("hidden_size must equal embed_size for the Transformer models "
                          "(embeddings are added to H-wide layers, transformer.py:29-31)")
+    if model_name == "transformer_fixup":
+        return _fixup_specs(params)
     d = H // params.num_heads
     rpr = model_name == "transformer_rpr"
     aan = model_name == "transformer_aan"
@@ -132,8 +173,11 @@ def initial_values(params, model_name, seed):
     transformer.py:38-44 deep_transformer_init)."""
     rng = np.random.default_rng(seed)
     out = OrderedDict()
+    # transformer_fixup: the depth-dependent factor of the input maps (modules/initializer.py:35-45 scale_initializer)
+    depth = 2 * params.num_encoder_layer + 3 * params.num_decoder_layer
+    fx = {"fx6": depth ** (-1.0 / 6.0) if depth else 1.0, "fx2": depth ** (-1.0 / 2.0) if depth else 1.0}
     for name, shape, kind, layer in variable_specs(params, model_name):
-        if kind == "embed":
+        if kind in ("embed", "embed_zeros"):
             v = rng.normal(0.0, params.hidden_size ** -0.5, size=shape)
         elif kind == "zeros":
             v = np.zeros(shape)
@@ -144,7 +188,7 @@ def initial_values(params, model_name, seed):
                             params.initializer_gain * (layer + 1) ** -0.5)
         else:
             v = _scope_init(rng, shape, params.initializer, params.initializer_gain)
-        out[name] = v.astype(np.float32)
+        out[name] = (v * (0.0 if kind.endswith("_zeros") else fx.get(kind, 1.0))).astype(np.float32)
     return out
 
 
@@ -159,7 +203,7 @@ class VariableStore(object):
         off = 0
         for name, shape, kind, _ in self.specs:
             pshape = tuple(shape)
-            if kind == "embed" or name.endswith("/embeddings"):
+            if kind in ("embed", "embed_zeros") or name.endswith("/embeddings"):
                 # (relative-position tables too: their zero rows make them GEMM operands with an 8-aligned
                 # contraction length as they are -- no padded copy per attention call)
                 pshape = ((shape[0] + 7) // 8 * 8, shape[1])
