@@ -1,0 +1,218 @@
+"""The launch trace of decoding: which library entry points the host code of a decode batch calls, in which order and
+with which scalar arguments.  Shared by tests/golden/make_decode_launch_trace.py (records the pinned file) and
+tests/test_gpu_decode_launch_trace.py (reproduces it); ``diff`` is checked on its own in
+tests/test_decode_trace_checker.py.
+
+A trace is ``{phase: [[entry point, [argument, ...]], ...], "graph_nodes": int}``.  An argument is recorded by the
+prototype table parsed from include/zero_hip.h (``lib.protos``): a pointer as None (NULL) or "nonnull", everything else
+by value.  Phases: ``encode`` (encoding_fn), ``step0`` / ``reorder`` / ``step1`` (two eager decoding_fn calls at
+time = 0, 1 with an identity reorder of the caches between them); ``graph_nodes`` is ``core._decode_step_launches``
+after one whole beam search of the same batch.
+
+Shapes: the smallest that take every arm -- H = 128, F = 256, 2 heads (head size 64: the fused attention launches
+apply), 2 + 2 layers, B = 5 sources of at most 9 tokens, beam 4.
+"""
+import ctypes
+import json
+import os
+
+import numpy as np
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "decode_launch_trace.json")
+MODELS = ("transformer", "transformer_aan", "transformer_rpr", "transformer_fuse", "transformer_l0drop", "transformer_rela",
+          "transformer_fixup")
+SWITCHES = ("ZERO_HIP_DECODE_FUSE_ATT", "ZERO_HIP_DECODE_FUSE_LN", "ZERO_HIP_F32_FUSE")
+PHASES = ("encode", "step0", "reorder", "step1")
+K = 4
+L0DROP_SEED = 43
+
+
+def _cases():
+    out = {}
+    for m in MODELS:
+        for dt in ("bfloat16", "float32"):
+            out["%s-%s" % (m, dt)] = dict(models=(m,), dtype=dt)
+    for m in ("transformer", "transformer_aan", "transformer_rpr"):
+        out["%s-bfloat16-fuse_att0" % m] = dict(models=(m,), env={"ZERO_HIP_DECODE_FUSE_ATT": "0"})
+    out["transformer_aan-bfloat16-fuse_ln0"] = dict(models=("transformer_aan",), env={"ZERO_HIP_DECODE_FUSE_LN": "0"})
+    out["transformer_aan-bfloat16-use_ffn"] = dict(models=("transformer_aan",), hp={"use_ffn": True})
+    for m in ("transformer", "transformer_aan"):
+        out["%s-float32-f32_fuse0" % m] = dict(models=(m,), dtype="float32", env={"ZERO_HIP_F32_FUSE": "0"})
+    out["transformer-bfloat16-head32"] = dict(models=("transformer",), hp={"hidden_size": 96, "embed_size": 96, "num_heads": 3})
+    out["ensemble-bfloat16"] = dict(models=("transformer", "transformer_aan"))
+    return out
+
+
+CASES = _cases()
+
+
+def _source(hp, seed):
+    from tests.common import make_batch
+    src, _ = make_batch(np.random.default_rng(seed), 5, 9, 11, hp.src_vocab.size(), hp.tgt_vocab.size())
+    return src
+
+
+def _params(hp, model, src, seed):
+    """Weights as the model tests of each variant build them (tests/test_gpu_decode_fuse.py::_model)."""
+    from oracle import ref_torch as rt
+    from tests.common import perturb
+    if model == "transformer_l0drop":
+        # a source_pruning pair that keeps some but not all positions of every sentence (6, 8, 3, 7 and 2 of them), with
+        # the margin make_fixture asserts: 0.61 from the threshold against a bf16-storage error of 0.057
+        from tests import l0drop_ref
+        Pn = dict(l0drop_ref.make_fixture(hp, src, L0DROP_SEED)["Pn"])
+    elif model == "transformer_rela":
+        from tests import rela_ref
+        Pn = rela_ref.init_params(hp, seed)
+    elif model == "transformer_fixup":
+        from tests import fixup_ref
+        Pn = dict(fixup_ref.init_params(hp, seed))
+    else:
+        Pn = perturb(rt.init_params(hp, model, seed=seed + 1), np.random.default_rng(seed))
+    Pn["tgt_embedding"] = (Pn["tgt_embedding"] * 6.0).astype(np.float32)
+    return Pn
+
+
+def _argument(ctype, value):
+    if ctype is ctypes.c_void_p:
+        if value is None or (isinstance(value, int) and value == 0):
+            return None
+        if isinstance(value, ctypes.c_void_p) and not value.value:
+            return None
+        return "nonnull"
+    if ctype is ctypes.c_float:
+        return float(value)
+    return int(value)
+
+
+class Recorder(object):
+    """Wraps ``_Lib.call`` (through ``patch.setattr``: a pytest monkeypatch) and files every call under the open phase."""
+
+    def __init__(self, patch):
+        from zero_amd import hip
+        self.phases = {}
+        self.open = None
+        inner = hip._Lib.call
+        rec = self
+
+        def call(lib, name, *args):
+            if rec.open is not None:
+                types = lib.protos[name][1]
+                assert len(types) == len(args), (name, len(types), len(args))
+                rec.phases[rec.open].append([name, [_argument(t, a) for t, a in zip(types, args)]])
+            return inner(lib, name, *args)
+        patch.setattr(hip._Lib, "call", call)
+
+    def phase(self, name):
+        rec = self
+
+        class _Phase(object):
+            def __enter__(self):
+                rec.phases[name] = []
+                rec.open = name
+
+            def __exit__(self, *a):
+                rec.open = None
+        return _Phase()
+
+
+def run_case(name, patch):
+    """Runs case ``name`` on the device -> its trace.  patch: a pytest monkeypatch (environment and ``_Lib.call``)."""
+    import torch
+    from tests.common import make_hp
+    from zero_amd import search
+    from zero_amd.models import model as registry, load_all
+    from zero_amd.models._factory import get_core, reset_cores
+    load_all()
+    case = CASES[name]
+    for k in SWITCHES:
+        patch.delenv(k, raising=False)
+    for k, v in case.get("env", {}).items():
+        patch.setenv(k, v)
+    models = case["models"]
+    hps, Pns = [], []
+    for i, m in enumerate(models):
+        hp = make_hp(m, beam_size=K, search_mode="cache", decode_dtype=case.get("dtype", "bfloat16"))
+        hp.override_from_dict(case.get("hp", {}))
+        if i == 0:
+            src = _source(hp, 21)
+        hps.append(hp)
+        Pns.append(_params(hp, m, src, 21 + i))
+    reset_cores()
+    if len(models) == 1:
+        core = get_core(hps[0], models[0], Pns[0])
+        enc, dec = registry.get_model(models[0]).infer_fn(hps[0])
+        hp0 = hps[0]
+    else:
+        from zero_amd.models import _ensemble
+        core = [get_core(_ensemble.member_params(hp, i), m, Pn) for i, (hp, Pn, m) in enumerate(zip(hps, Pns, models))][0]
+        enc, dec, hp0 = _ensemble.make_infer_fns([registry.get_model(m) for m in models], hps)
+    rng = np.random.default_rng(5)
+    BK = src.shape[0] * K
+    toks = [torch.from_numpy(rng.integers(3, hp0.tgt_vocab.size(), size=(BK,)).astype(np.int32)).to(core.eng.device)
+            for _ in range(2)]
+    ident = torch.arange(BK, dtype=torch.int32, device=core.eng.device)
+    rec = Recorder(patch)
+    with rec.phase("encode"):
+        state = enc(src)
+    with rec.phase("step0"):
+        _, state = dec(toks[0], state, 0)
+    with rec.phase("reorder"):
+        state.reorder(ident)
+    with rec.phase("step1"):
+        _, state = dec(toks[1], state, 1)
+    torch.cuda.synchronize()
+    core.__dict__.pop("_decode_step_launches", None)
+    out = search.beam_search({"source": src}, enc, dec, hp0)
+    assert out["steps"] >= 4, out["steps"]           # both parities were captured
+    trace = dict(rec.phases)
+    trace["graph_nodes"] = int(core.__dict__.get("_decode_step_launches", 0))
+    reset_cores()
+    return trace
+
+
+def diff(want, got):
+    """-> list of messages, empty if ``got`` reproduces ``want`` exactly: same phases, same entry points in the same
+    order, same pointer pattern and same scalar values."""
+    msgs = []
+    if sorted(want) != sorted(got):
+        return ["phases differ: %s against %s" % (sorted(want), sorted(got))]
+    for ph in sorted(want):
+        a, b = want[ph], got[ph]
+        if not isinstance(a, list):
+            if a != b:
+                msgs.append("%s: %r, recorded %r" % (ph, b, a))
+            continue
+        if [c[0] for c in a] != [c[0] for c in b]:
+            i = next((i for i, (x, y) in enumerate(zip(a, b)) if x[0] != y[0]), min(len(a), len(b)))
+            msgs.append("%s: launch %d is %s, recorded %s (%d launches, recorded %d)"
+                        % (ph, i, b[i][0] if i < len(b) else "missing", a[i][0] if i < len(a) else "nothing", len(b), len(a)))
+            continue
+        for i, (x, y) in enumerate(zip(a, b)):
+            if len(x[1]) != len(y[1]):
+                msgs.append("%s: launch %d (%s) has %d arguments, recorded %d" % (ph, i, x[0], len(y[1]), len(x[1])))
+                continue
+            for j, (u, v) in enumerate(zip(x[1], y[1])):
+                if type(u) is not type(v) or u != v:
+                    msgs.append("%s: launch %d (%s) argument %d is %r, recorded %r" % (ph, i, x[0], j, v, u))
+    return msgs
+
+
+def dump(traces, path=GOLDEN):
+    """One launch per line: the file stays readable in a diff."""
+    lines = []
+    for name in sorted(traces):
+        tr = traces[name]
+        body = []
+        for ph in PHASES:
+            calls = ",\n".join("   " + json.dumps(c, separators=(",", ":")) for c in tr[ph])
+            body.append('  "%s": [\n%s\n  ]' % (ph, calls))
+        body.append('  "graph_nodes": %d' % tr["graph_nodes"])
+        lines.append('"%s": {\n%s\n }' % (name, ",\n".join(body)))
+    with open(path, "w") as f:
+        f.write("{\n" + ",\n".join(lines) + "\n}\n")
+
+
+def load(path=GOLDEN):
+    with open(path) as f:
+        return json.load(f)

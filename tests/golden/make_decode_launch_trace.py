@@ -1,0 +1,39 @@
+# coding: utf-8
+"""The pinned launch trace of decoding (needs the GPU; run on the commit whose launches are to be pinned).
+
+For every case of tests/decode_trace.CASES -- the seven models in bf16 and in decode_dtype=float32, the forms selected by
+ZERO_HIP_DECODE_FUSE_ATT / ZERO_HIP_DECODE_FUSE_LN / ZERO_HIP_F32_FUSE / use_ffn, a head size of 32 (the launch-per-op
+path) and a two-member ensemble -- records every call of the library's entry points by encoding_fn, by two eager
+decoding_fn steps with a cache reorder between them, and the node count of the captured step graph of a whole beam
+search (tests/decode_trace.run_case).
+
+Writes tests/golden/decode_launch_trace.json (or the path given as the first argument), which
+tests/test_gpu_decode_launch_trace.py must reproduce exactly: a host-side change of decoding that adds, drops, reorders
+or re-parameterises a launch shows there.  A few seconds.
+"""
+import os
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+from tests import decode_trace as DT  # noqa: E402
+
+
+def main():
+    path = sys.argv[1] if len(sys.argv) > 1 else DT.GOLDEN
+    traces = {}
+    for name in DT.CASES:
+        with pytest.MonkeyPatch.context() as patch:
+            traces[name] = DT.run_case(name, patch)
+        print("%-40s %s, graph of %d nodes" % (name, " + ".join("%d" % len(traces[name][ph]) for ph in DT.PHASES),
+                                              traces[name]["graph_nodes"]), flush=True)
+    DT.dump(traces, path)
+    assert not any(DT.diff(traces[n], DT.load(path)[n]) for n in traces)
+    print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
+
+
+if __name__ == "__main__":
+    main()

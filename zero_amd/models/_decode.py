@@ -23,10 +23,17 @@ search_mode="dev" (transformer.py:277-281) recomputes the encoder and the whole 
 through the training-path decoder each step.
 """
 
+import collections
+import ctypes
+import os
+import threading
+
 import numpy as np
 import torch
 
 from zero_amd.func import Mat
+from zero_amd.hip import ZeroHipError
+from zero_amd.models._core import trim_columns
 from zero_amd.models._factory import get_core
 from zero_amd.models import _decode_f32 as _f32
 from zero_amd.models import _l0drop as _l0
@@ -40,8 +47,7 @@ F32 = torch.float32
 # inside a stream capture invalidated that capture on ROCm 7.x ("operation failed due to a previous error during
 # capture"), whereas a thread that only replays graphs beside a capturing one is fine.  The replay loop -- ~95 % of a
 # batch's time -- runs unlocked; a single-threaded caller never waits.
-import threading as _threading
-STARTUP_LOCK = _threading.RLock()
+STARTUP_LOCK = threading.RLock()
 
 
 def startup_begin():
@@ -79,9 +85,8 @@ def _graph_pointers(state, book):
         lay = state["decoder"]["state"]["layer_%d" % l]
         ptrs += [lay["mk"].ptr, lay["mv"].ptr]
     ptrs.append(core.store.master.data_ptr())
-    for nm in ("dc.aan.0", "dc.aan.1", "dc.k.0", "dc.k.1", "dc.v.0", "dc.v.1",
-               "dq.aan.0", "dq.aan.1", "dq.k.0", "dq.k.1", "dq.v.0", "dq.v.1", "dq.logits"):
-        b = e.bufs.get(nm)
+    for nm in ("aan.0", "aan.1", "k.0", "k.1", "v.0", "v.1", "logits"):
+        b = e.bufs.get(state.storage.prefix + nm)
         ptrs.append(b.data_ptr() if b is not None else 0)
     ptrs += [m.ptr for _, m in sorted(state.get("wt", {}).items())]
     if state.get("kbias") is not None:          # transformer_l0drop: the log-count bias of the cross-attention keys
@@ -98,15 +103,12 @@ def _destroy_graphs(core, graphs):
 
 def adopt_graphs(state, book, temperature, forbid_value, noise):
     """First step of a batch: take over the cached parity graphs of its shape, if they are still valid."""
-    import collections
-    import os
     core = state["_core"]
     e = core.eng
     # (zk_dec_group(-1) = the rows-per-workgroup geometry in force: graphs captured with several batches in flight --
     # 16 rows per workgroup -- must not be adopted by a single-stream decode, nor the reverse)
-    from zero_amd import hip as _hip
     key = (state["B"], state["K"], state["Ls"], state["Tmax"], book is not None, float(temperature),
-           float(forbid_value), bool(noise), int(_hip.lib().raw("zk_dec_group")(-1)), bool(state.get("f32")))
+           float(forbid_value), bool(noise), int(e.lib.raw("zk_dec_group")(-1)), bool(state.get("f32")))
     state["_gkey"] = key
     if os.environ.get("ZERO_HIP_DECODE_GRAPH_CACHE", "1") == "0":
         return
@@ -124,8 +126,6 @@ def adopt_graphs(state, book, temperature, forbid_value, noise):
 
 def retire_graphs(state):
     """End of a batch: complete parity graphs go to the shape cache of their core, everything else is destroyed."""
-    import collections
-    import os
     graphs = state.get("graphs") if hasattr(state, "get") else None
     if not graphs:
         return
@@ -162,7 +162,6 @@ class lanes_mode(object):
         self.n = int(n)
 
     def __enter__(self):
-        import os
         from zero_amd import hip
         rows = 16 if self.n > 1 else 0
         self.prev = hip.lib().raw("zk_dec_group")(rows)
@@ -173,71 +172,86 @@ class lanes_mode(object):
         hip.lib().raw("zk_dec_group")(self.prev)
 
 
+# Where a decode mode keeps its per-beam caches: the prefix of its engine buffers (a bf16 and an fp32 decode of one engine
+# never alias), the element type of the k / v caches and its size in bytes.  defer_aan: the step's input launch can take
+# over the beam reorder of the average-attention sums (zk_dec_embed: gather_src / gather_idx); the fp32 step has no such
+# launch and gathers at once.
+Storage = collections.namedtuple("Storage", "prefix dtype esz defer_aan")
+BF16_CACHES = Storage("dc.", torch.bfloat16, 2, True)
+F32_CACHES = Storage("dq.", F32, 4, False)
+
+
 class DecodeState(dict):
     """Nested-dict state with the cache plumbing the search needs."""
+
+    storage = BF16_CACHES
 
     def reorder(self, index_dev, time_dev=None, defer_aan=False):
         """Gather every per-beam cache by flat beam index [B*K] (device int32).  time_dev: the
         number of filled cache slots lives in device memory (hipGraph replay).  The caches of all
-        layers are slabs of one buffer, so each kind (aan / k / v) is ONE launch."""
+        layers are slabs of one buffer, so each kind (aan / k / v) is ONE launch.  defer_aan: leave the gather
+        of the average-attention sums to the step's input launch, where the storage has one (Storage.defer_aan)."""
         core = self["_core"]
-        e = core.eng
+        e, st = core.eng, self.storage
         BK, H, t = self["BK"], core.H, self["time_filled"]
         nl = core.hp.num_decoder_layer
         pp = self["_pp"]
         lay0 = self["decoder"]["state"]["layer_0"]
         if "aan" in lay0:
-            src = e.buf("dc.aan.%d" % pp, (nl, BK, H), F32)
-            dst = e.buf("dc.aan.%d" % (1 - pp), (nl, BK, H), F32)
-            if defer_aan:
-                # the decoder-input launch of the step does it (zk_dec_embed: gather_src / gather_idx)
+            src = e.buf(st.prefix + "aan.%d" % pp, (nl, BK, H), F32)
+            dst = e.buf(st.prefix + "aan.%d" % (1 - pp), (nl, BK, H), F32)
+            if defer_aan and st.defer_aan:
                 self["_aan_gather"] = (src, index_dev)
             else:
                 e.lib.call("zk_gather_rows_ex", src.data_ptr(), H * 4, index_dev.data_ptr(), dst.data_ptr(), H * 4,
                            nl * BK, H * 4, BK, e.stream)
         if "k" in lay0:
             Tmax = self["Tmax"]
+            row = Tmax * H * st.esz
             for nm in ("k", "v"):
-                src = e.buf("dc.%s.%d" % (nm, pp), (nl, BK, Tmax, H))
-                dst = e.buf("dc.%s.%d" % (nm, 1 - pp), (nl, BK, Tmax, H))
+                src = e.buf("%s%s.%d" % (st.prefix, nm, pp), (nl, BK, Tmax, H), st.dtype)
+                dst = e.buf("%s%s.%d" % (st.prefix, nm, 1 - pp), (nl, BK, Tmax, H), st.dtype)
                 if time_dev is not None:
-                    e.lib.call("zk_cache_rows", src.data_ptr(), Tmax * H * 2, index_dev.data_ptr(), dst.data_ptr(),
-                               Tmax * H * 2, nl * BK, H * 2, Tmax, time_dev.data_ptr(), 1, BK, e.stream)
+                    e.lib.call("zk_cache_rows", src.data_ptr(), row, index_dev.data_ptr(), dst.data_ptr(), row, nl * BK,
+                               H * st.esz, Tmax, time_dev.data_ptr(), 1, BK, e.stream)
                 else:
-                    e.lib.call("zk_gather_rows_ex", src.data_ptr(), Tmax * H * 2, index_dev.data_ptr(),
-                               dst.data_ptr(), Tmax * H * 2, nl * BK, t * H * 2, BK, e.stream)
+                    e.lib.call("zk_gather_rows_ex", src.data_ptr(), row, index_dev.data_ptr(), dst.data_ptr(), row,
+                               nl * BK, t * H * st.esz, BK, e.stream)
         self["_pp"] = 1 - pp
         self.bind_caches()
 
     def bind_caches(self):
         """Point every layer's cache entries at the current ping-pong half."""
         core = self["_core"]
-        e = core.eng
+        e, st = core.eng, self.storage
         BK, H, nl, pp = self["BK"], core.H, core.hp.num_decoder_layer, self["_pp"]
         for l in range(nl):
             lay = self["decoder"]["state"]["layer_%d" % l]
             if "aan" in lay:
-                lay["aan"] = e.buf("dc.aan.%d" % pp, (nl, BK, H), F32)[l]
+                lay["aan"] = e.buf(st.prefix + "aan.%d" % pp, (nl, BK, H), F32)[l]
             if "k" in lay:
                 for nm in ("k", "v"):
-                    lay[nm] = e.buf("dc.%s.%d" % (nm, pp), (nl, BK, self["Tmax"], H))[l]
+                    lay[nm] = e.buf("%s%s.%d" % (st.prefix, nm, pp), (nl, BK, self["Tmax"], H), st.dtype)[l]
 
 
-DecodeStateF32 = _f32.make_state_class(DecodeState)      # decode_dtype = float32: 4-byte caches, `dq.*` buffers
+def append_kv(e, qkv, lay, rows, H, Tmax, esz, time, time_dev):
+    """This step's keys and values (columns H .. 3H of the qkv rows) go to slot ``time`` of every row's k / v cache; with
+    time_dev the slot is read from device memory (hipGraph replay).  esz: bytes per element of qkv and of the caches."""
+    for nm, c0 in (("k", H), ("v", 2 * H)):
+        if time_dev is not None:
+            e.lib.call("zk_cache_rows", qkv.ptr + c0 * esz, 3 * H * esz, None, lay[nm].data_ptr(), Tmax * H * esz, rows,
+                       H * esz, Tmax, time_dev.data_ptr(), 0, 0, e.stream)
+        else:
+            e.lib.call("zk_gather_rows", qkv.ptr + c0 * esz, 3 * H * esz, None, lay[nm].data_ptr() + time * H * esz,
+                       Tmax * H * esz, rows, H * esz, e.stream)
 
 
 def _fuse_att_ok(core, hp, K):
     """The attention sub-layers of a cached decode step as one launch per (sentence, head) (zk_dec_cross / zk_dec_self)."""
-    import os
     return (os.environ.get("ZERO_HIP_DECODE_FUSE_ATT", "1") != "0" and core.d == 64
             and core.H in (128, 256, 512, 1024, 2048) and not core.fuse and not core.rela and not core.fixup
             and (not core.rpr or hp.max_relative_position <= 31)
             and (not core.aan or os.environ.get("ZERO_HIP_DECODE_FUSE_LN", "1") != "0") and not hp.use_ffn)
-
-
-def _fuse_tail():
-    import os
-    return True
 
 
 def search_tail(state, core, logits, noise, temperature, forbid_value):
@@ -253,7 +267,7 @@ def search_tail(state, core, logits, noise, temperature, forbid_value):
                    e.seed.data_ptr(), 7001, e.stream)
         e.lib.call("zk_seed_advance", e.seed.data_ptr(), 1, e.stream)
     fused_tail = False
-    if book is not None and _fuse_tail():
+    if book is not None:
         # merge of the chunked top-2K and the alive / finished bookkeeping in one launch
         ws = e.workspace(e.lib.query("zk_beam_topk_workspace", state["B"], state["K"], 2 * state["K"]))
         e.lib.ncalls += 1
@@ -317,227 +331,297 @@ def _cross_unfused(core, e, hp, state, lay, x, p, pre, l, time, time_dev):
     return x
 
 
+# ---- what a model variant refuses ----------------------------------------------------------------------------------
+def _l0drop_bf16_shape(core, hp, K):
+    if not _fuse_att_ok(core, hp, K):
+        return ("transformer_l0drop in bf16 decodes through the fused attention launch only "
+                "(ZERO_HIP_DECODE_FUSE_ATT not 0, a head size of 64 -- got %d -- and a hidden size that is a "
+                "power of two in 128 .. 2048 -- got %d); decode_dtype=float32 has none of these limits" % (core.d, core.H))
+
+
+def _rela_bf16_shape(core, hp, K):
+    if core.d % 8 != 0 or core.d > 128 or core.H > 2048:
+        return ("transformer_rela in bf16 needs a head size that is a multiple of 8 and at most 128 -- got %d -- "
+                "and a hidden size of at most 2048 -- got %d (zk_rela_attn reads keys 16 bytes at a time and "
+                "keeps four rows of H floats in LDS); decode_dtype=float32 takes any head size" % (core.d, core.H))
+
+
+# Per model name, what the variant does not do (a name that is not listed has no limit of its own):
+#   cache_only   the NotImplementedError text of a search_mode other than "cache"
+#   bf16_shape   (core, hp, K) -> the ValueError text of a shape its bf16 kernels do not take, or None
+#   member       (exception type, text with the member's index) of its refusal as an ensemble member
+VARIANT_LIMITS = {
+    "transformer_l0drop": dict(
+        cache_only="transformer_l0drop decodes with search_mode=cache only (the other mode re-runs the "
+                   "training-path decoder, which this model does not have here)",
+        bf16_shape=_l0drop_bf16_shape,
+        member=(ZeroHipError, "ensemble member %d is a transformer_l0drop: its pruned memory has a length of its own per "
+                              "batch, the members of an ensemble step share one shape")),
+    "transformer_rela": dict(
+        cache_only="transformer_rela decodes with search_mode=cache only: search_mode=dev re-runs the "
+                   "training-path decoder, which this model does not have here",
+        bf16_shape=_rela_bf16_shape,
+        member=(NotImplementedError, "ensemble member %d is a transformer_rela: the ensemble step is built from the fused "
+                                     "softmax attention launches, which this model does not use; composing it is not built")),
+    "transformer_fixup": dict(
+        cache_only="transformer_fixup decodes with search_mode=cache only: the re-encoding decode mode "
+                   "(search_mode=dev re-runs the encoder and the whole prefix each step) is not built for it",
+        member=(NotImplementedError, "ensemble member %d is a transformer_fixup: an untested member type (its step takes "
+                                     "the launch-per-op path, the ensemble step is built from the fused launches)")),
+}
+
+
+def check_search_mode(model_name, hp):
+    text = VARIANT_LIMITS.get(model_name, {}).get("cache_only")
+    if text is not None and hp.search_mode != "cache":
+        raise NotImplementedError(text)
+
+
+def check_bf16_shape(model_name, core, hp, K):
+    shape = VARIANT_LIMITS.get(model_name, {}).get("bf16_shape")
+    text = shape(core, hp, K) if shape is not None else None
+    if text is not None:
+        raise ValueError(text)
+
+
+def check_member(model_name, i):
+    exc, text = VARIANT_LIMITS.get(model_name, {}).get("member", (None, None))
+    if exc is not None:
+        raise exc(text % i)
+
+
+# ---- start-up of a batch -------------------------------------------------------------------------------------------
+# What a decode mode brings to the start-up: its cache storage, its encoder (batch -> (encoder output Mat, source mask)),
+# its linear op (x, scope, out) and its factory of named matrices (name, rows, cols).
+Mode = collections.namedtuple("Mode", "storage encode linear mat")
+
+
+def _mode(core, hp):
+    if _f32.wanted(hp):
+        # the fp32 mode: fp32 masters, activations and caches through zk_f32_* (models/_decode_f32.py)
+        o = _f32._Ops(core)
+        return Mode(F32_CACHES, lambda batch: _f32.encode(core, hp, batch), o.linear, o.mat)
+    e = core.eng
+    return Mode(BF16_CACHES, lambda batch: core.encode(batch, False, False), core._linear,
+                lambda name, rows, cols: e.mat("dc." + name, rows, cols))
+
+
+def _fused_weights(state, core, hp):
+    """bf16 only: state['wt'], the transposed projection weights of the fused attention launches -- left empty where they
+    do not apply, and the step then takes the launch-per-op path (_cross_unfused) instead of failing mid-decode.  The
+    fused launches keep a sentence's scores in LDS (64 bytes per key for 16 rows), and the whole workgroup state must
+    fit the 160 KiB of a CU."""
+    e, H, K = core.eng, core.H, state["K"]
+    keys = max(state["Ls"], state["Tmax"])
+    if _fuse_att_ok(core, hp, K) and keys <= 1024 and \
+            e.lib.query("zk_dec_attn_lds", H, keys, hp.max_relative_position if core.rpr else -1) <= 160 * 1024:
+        for l in range(hp.num_decoder_layer):
+            blocks = [(core.cross, ("q_map", "o_map"))]
+            if not core.aan:
+                blocks.append(("self_attention", ("qkv_map", "o_map")))
+            for blk, maps in blocks:
+                for m in maps:
+                    nm = "decoder/layer_%d/%s/dot_attention/%s/W_0_0" % (l, blk, m)
+                    state["wt"][nm] = _transposed(core, nm)
+    if core.l0drop and not state["wt"]:
+        raise ValueError("transformer_l0drop in bf16 decodes through the fused attention launch only: its workgroup "
+                         "keeps the scores of max(memory slots, cache positions) = %d keys in LDS, at most 1024 of them "
+                         "and within the 160 KiB of a CU at hidden size %d; decode_dtype=float32 has no such limit"
+                         % (keys, H))
+
+
+def build_state(core, hp, model_name, source, K, max_steps):
+    """encoding_fn of both decode modes: source batch -> DecodeState."""
+    e, H = core.eng, core.H
+    f32 = _f32.wanted(hp)
+    pad = max(1, int(os.environ.get("ZERO_HIP_DECODE_PAD_LEN", "8")))
+    # nothing here depends on the data: refuse before the encoder pass
+    if f32:
+        _f32.check_model(core)
+    else:
+        check_bf16_shape(model_name, core, hp, K)
+    mode = _mode(core, hp)
+    st = mode.storage
+    if pad > 1:
+        # Shape bucketing for the step-graph cache: the source is padded (id 0 = pad: masked in the encoder's
+        # self-attention and in every cross-attention, func.py:372-387) and the cache length rounded up to a multiple
+        # of `pad`, so that length-sorted batches fall into few shapes.  Masked keys contribute exact zeros to the
+        # softmax sums: hypotheses and scores are unchanged (tests/test_gpu_model.py).
+        src_np = trim_columns(np.asarray(source.cpu() if torch.is_tensor(source) else source))
+        src_np = np.pad(src_np, ((0, 0), (0, -src_np.shape[1] % pad)))
+        batch = core.upload(src_np, trim=False)
+        if max_steps is not None:
+            max_steps = -(-int(max_steps) // pad) * pad
+    else:
+        batch = core.upload(source)
+    B, Ls = batch["B"], batch["Ls"]
+    enc, smask = mode.encode(batch)
+    kbias = None
+    if core.l0drop:
+        # the pruned memory, its mask and its length stand in for the encoder output from here on (models/_l0drop.py)
+        enc_keep, mask_keep, Ls, kbias = _l0.prune(core, enc, smask, B, Ls, pad, f32)
+    else:
+        enc_keep = mode.mat("enc", B * Ls, H)
+        enc_keep.t.copy_(enc.t)
+        mask_keep = e.buf(st.prefix + "smask", (B, Ls), F32)
+        mask_keep.copy_(smask)
+    if max_steps is None:
+        src_len = (np.asarray(source.cpu() if torch.is_tensor(source) else source) != 0).sum(1)
+        max_steps = -(-(int(src_len.max()) + hp.decode_length + 2) // pad) * pad
+    BK = B * K
+    nl = hp.num_decoder_layer
+    state = DecodeState()
+    state.storage = st
+    state.update({"_core": core, "B": B, "K": K, "BK": BK, "Ls": Ls, "Tmax": max_steps, "encodes": enc_keep,
+                  "mask": mask_keep, "time_filled": 0, "decoder": {"state": {}}, "f32": f32, "wt": {}, "_pp": 0})
+    if kbias is not None:
+        state["kbias"] = kbias
+    for l in range(nl):
+        p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
+        kv = mode.mat("%d.kv" % l, B * Ls, 2 * H)
+        mode.linear(enc_keep, p + "k_map", kv.cols_slice(0, H))
+        mode.linear(enc_keep, p + "v_map", kv.cols_slice(H, 2 * H))
+        lay = {"mk": kv.cols_slice(0, H), "mv": kv.cols_slice(H, 2 * H)}
+        if core.aan or core.fuse:
+            lay["aan"] = None
+        else:
+            lay["k"] = lay["v"] = None
+        state["decoder"]["state"]["layer_%d" % l] = lay
+    if not f32:
+        _fused_weights(state, core, hp)
+    if core.aan or core.fuse:
+        e.zero(e.buf(st.prefix + "aan.0", (nl, BK, H), F32))
+        e.buf(st.prefix + "aan.1", (nl, BK, H), F32)
+    else:
+        for nm in ("k", "v"):
+            for half in (0, 1):
+                e.buf("%s%s.%d" % (st.prefix, nm, half), (nl, BK, max_steps, H), st.dtype)
+    state.bind_caches()
+    if f32:      # the launch-per-op form of the fp32 step (ZERO_HIP_F32_FUSE=0) tests for an all-pad input on its own
+        state["zero_flag"] = e.buf("dq.zflag", (1,), torch.int32)
+    return finish_state(state)
+
+
+def finish_state(state):
+    """The part of a batch's state that does not depend on the step's dtype: the packed host <-> device buffers of
+    the search and the graph table."""
+    core = state["_core"]
+    e = core.eng
+    B, K, BK = state["B"], state["K"], state["BK"]
+    # per-step scalars live in device memory ({time, float bits of the length penalty, EOS-ban id}):
+    # a captured decode-step graph reads the current values at replay time
+    # what the host hands to a (replayed) step -- last tokens, previous log-probs, beam reorder index and
+    # the per-step scalars {time, float bits of the length penalty, EOS-ban id} -- is ONE pinned buffer
+    # and one async copy; what comes back (top-2K scores and flat indices) is one copy as well
+    pack = e.buf("bs.pack", (3 * BK + 4,), torch.int32)
+    state["pack_dev"] = pack
+    pins = core.__dict__.setdefault("_decode_pins", {})       # pinned staging survives the batch (pinning ~0.2 ms)
+
+    def pinned(name, n):
+        t = pins.get(name)
+        if t is None or t.numel() < n:
+            t = pins[name] = torch.zeros(n + n // 4, dtype=torch.int32).pin_memory()
+        t[:n].zero_()
+        return t[:n]
+    state["pack_host"] = pinned("pack", 3 * BK + 4)
+    state["tok"] = pack[0:BK]
+    state["prev"] = pack[BK:2 * BK].view(torch.float32)
+    state["idx"] = pack[2 * BK:3 * BK]
+    state["stepbuf"] = pack[3 * BK:3 * BK + 4]
+    out = e.buf("bs.out", (2, B, 2 * K), torch.int32)
+    state["out_dev"] = out
+    state["out_host"] = pinned("out", 2 * B * 2 * K).view(2, B, 2 * K)
+    state["ts"] = out[0].view(torch.float32)
+    state["ti"] = out[1]
+    state["graphs"] = {}
+    # every launch argument of a step is static: the time step (cache slot, number of valid keys,
+    # relative-position origin) is read from device memory by the kernels
+    state["static_ok"] = True
+    return state
+
+
+# ---- the step-graph driver -----------------------------------------------------------------------------------------
+def _capture(state, core, body, check_realloc):
+    """body() captured into a hipGraph -> its executable, or None.  The python-side ping-pong bookkeeping runs during a
+    capture exactly as in an eager call.  A capture that fails (an allocation met it: a workspace grew, or another
+    thread allocated -- ROCm 7 invalidates captures across threads) must not cost the evaluation, and the training run
+    with it: the python-side flip of the aborted pass is undone and the caller runs the step eagerly."""
+    e = core.eng
+    pp0, gen0 = state["_pp"], e.realloc_gen
+    try:
+        gexec = e.graph_capture(body)
+        core._decode_step_launches = e.last_graph_nodes
+        if check_realloc and e.realloc_gen != gen0:
+            e.lib.call("zk_graph_destroy", gexec)
+            raise RuntimeError("buffer replaced during capture")
+        return gexec
+    except Exception:
+        torch.cuda.synchronize(e.device)
+        state["_pp"] = pp0
+        state.bind_caches()
+        return None
+
+
+def run_step(state, core, body, fast_capture):
+    """One decode step whose launch sequence ``body()`` is identical every step (per ping-pong parity): the first call
+    of a parity runs it eagerly (that sizes the scratch), the second captures it into a hipGraph, later calls redo the
+    python-side pointer flip and replay; a failed capture costs one eager step and the next step of the parity tries
+    again.  fast_capture: where a batch of at least this many beam rows has already been decoded from graphs on this
+    engine (core._decode_warm_rows), the step's scratch buffers exist, so capture straight away instead of spending an
+    eager pass first; if that capture does hit an allocation after all (a larger source length can grow a workspace),
+    take the eager route.  Releases the batch's start-up lock once both parity graphs exist."""
+    e = core.eng
+    graphs, parity = state["graphs"], state["_pp"]
+    g = graphs.get(parity)
+    if g is None and fast_capture and core.__dict__.get("_decode_warm_rows", 0) >= state["BK"]:
+        g = _capture(state, core, body, True)
+        if g is None:
+            core._decode_warm_rows = 0
+        else:
+            graphs[parity] = g
+            e.graph_launch(g)
+    elif g == "warm":
+        g = _capture(state, core, body, False)
+        if g is not None:
+            graphs[parity] = g
+            e.graph_launch(g)
+    elif g is not None:
+        state["_pp"] = 1 - state["_pp"]           # replay: redo the python-side pointer flip
+        state.bind_caches()
+        e.graph_launch(g)
+    if g is None:
+        graphs.setdefault(parity, "warm")
+        body()
+    if state.get("_startup_held") and _startup_settled(state):
+        startup_end(state)
+
+
 def make_infer_fns(params, model_name):
     hp = params
-    if model_name == "transformer_l0drop" and hp.search_mode != "cache":
-        raise NotImplementedError("transformer_l0drop decodes with search_mode=cache only (the other mode re-runs the "
-                                  "training-path decoder, which this model does not have here)")
-    if model_name == "transformer_rela" and hp.search_mode != "cache":
-        raise NotImplementedError("transformer_rela decodes with search_mode=cache only: search_mode=dev re-runs the "
-                                  "training-path decoder, which this model does not have here")
-
-    if model_name == "transformer_fixup" and hp.search_mode != "cache":
-        raise NotImplementedError("transformer_fixup decodes with search_mode=cache only: the re-encoding decode mode "
-                                  "(search_mode=dev re-runs the encoder and the whole prefix each step) is not built for it")
+    check_search_mode(model_name, hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)
-        e, H = core.eng, core.H
-        K = hp.beam_size if beam_size is None else beam_size
-        import os
-        pad = max(1, int(os.environ.get("ZERO_HIP_DECODE_PAD_LEN", "8")))
-        if core.l0drop and not _f32.wanted(hp) and not _fuse_att_ok(core, hp, K):
-            # nothing here depends on the data: refuse before the encoder pass
-            raise ValueError("transformer_l0drop in bf16 decodes through the fused attention launch only "
-                             "(ZERO_HIP_DECODE_FUSE_ATT not 0, a head size of 64 -- got %d -- and a hidden size that is a "
-                             "power of two in 128 .. 2048 -- got %d); decode_dtype=float32 has none of these limits"
-                             % (core.d, core.H))
-        if core.rela and not _f32.wanted(hp) and (core.d % 8 != 0 or core.d > 128 or core.H > 2048):
-            # nothing here depends on the data: refuse before the encoder pass
-            raise ValueError("transformer_rela in bf16 needs a head size that is a multiple of 8 and at most 128 -- got %d -- "
-                             "and a hidden size of at most 2048 -- got %d (zk_rela_attn reads keys 16 bytes at a time and "
-                             "keeps four rows of H floats in LDS); decode_dtype=float32 takes any head size"
-                             % (core.d, core.H))
-        if _f32.wanted(hp):
-            # the fp32 mode (round 5): fp32 masters, activations and caches through zk_f32_* (models/_decode_f32.py)
-            from zero_amd.models._core import trim_columns
-            return finish_state(_f32.encoding_state(core, hp, source, K, max_steps, DecodeStateF32, pad, trim_columns))
-        if pad > 1:
-            # Shape bucketing for the step-graph cache: the source is padded (id 0 = pad: masked in the encoder's
-            # self-attention and in every cross-attention, func.py:372-387) and the cache length rounded up to a multiple
-            # of `pad`, so that length-sorted batches fall into few shapes.  Masked keys contribute exact zeros to the
-            # softmax sums: hypotheses and scores are unchanged (tests/test_gpu_model.py).
-            from zero_amd.models._core import trim_columns
-            src_np = trim_columns(np.asarray(source.cpu() if torch.is_tensor(source) else source))
-            src_np = np.pad(src_np, ((0, 0), (0, -src_np.shape[1] % pad)))
-            batch = core.upload(src_np, trim=False)
-            if max_steps is not None:
-                max_steps = -(-int(max_steps) // pad) * pad
-        else:
-            batch = core.upload(source)
-        B, Ls = batch["B"], batch["Ls"]
-        enc, smask = core.encode(batch, False, False)
-        kbias = None
-        if core.l0drop:
-            # the pruned memory, its mask and its length stand in for the encoder output from here on (models/_l0drop.py)
-            enc_keep, mask_keep, Ls, kbias = _l0.prune(core, enc, smask, B, Ls, pad, False)
-        else:
-            enc_keep = e.mat("dc.enc", B * Ls, H)
-            enc_keep.t.copy_(enc.t)
-            mask_keep = e.buf("dc.smask", (B, Ls), F32)
-            mask_keep.copy_(smask)
-        if max_steps is None:
-            src_len = (np.asarray(source.cpu() if torch.is_tensor(source) else source) != 0).sum(1)
-            max_steps = -(-(int(src_len.max()) + hp.decode_length + 2) // pad) * pad
-        BK = B * K
-        state = DecodeState()
-        state.update({"_core": core, "B": B, "K": K, "BK": BK, "Ls": Ls, "Tmax": max_steps,
-                      "encodes": enc_keep, "mask": mask_keep, "time_filled": 0,
-                      "decoder": {"state": {}}})
-        if kbias is not None:
-            state["kbias"] = kbias
-        for l in range(hp.num_decoder_layer):
-            p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
-            kv = e.mat("dc%d.kv" % l, B * Ls, 2 * H)
-            core._linear(enc_keep, p + "k_map", kv.cols_slice(0, H))
-            core._linear(enc_keep, p + "v_map", kv.cols_slice(H, 2 * H))
-            lay = {"mk": kv.cols_slice(0, H), "mv": kv.cols_slice(H, 2 * H)}
-            if core.aan or core.fuse:
-                lay["aan"] = None
-            else:
-                lay["k"] = lay["v"] = None
-            state["decoder"]["state"]["layer_%d" % l] = lay
-        state["_pp"] = 0
-        nl = hp.num_decoder_layer
-        state["wt"] = {}
-        # (the fused launches keep a sentence's scores in LDS: 64 bytes per key for 16 rows)
-        # and the whole workgroup state must fit the 160 KiB of a CU: otherwise 'wt' stays empty and the step takes the
-        # launch-per-op path (_cross_unfused) instead of failing mid-decode
-        if _fuse_att_ok(core, hp, K) and max(Ls, max_steps) <= 1024 and \
-                e.lib.query("zk_dec_attn_lds", H, max(Ls, max_steps),
-                            hp.max_relative_position if core.rpr else -1) <= 160 * 1024:
-            for l in range(nl):
-                blocks = [(core.cross, ("q_map", "o_map"))]
-                if not core.aan:
-                    blocks.append(("self_attention", ("qkv_map", "o_map")))
-                for blk, maps in blocks:
-                    for m in maps:
-                        nm = "decoder/layer_%d/%s/dot_attention/%s/W_0_0" % (l, blk, m)
-                        state["wt"][nm] = _transposed(core, nm)
-        if core.l0drop and not state["wt"]:
-            raise ValueError("transformer_l0drop in bf16 decodes through the fused attention launch only: its workgroup "
-                             "keeps the scores of max(memory slots, cache positions) = %d keys in LDS, at most 1024 of them "
-                             "and within the 160 KiB of a CU at hidden size %d; decode_dtype=float32 has no such limit"
-                             % (max(Ls, max_steps), H))
-        if core.aan or core.fuse:
-            e.zero(e.buf("dc.aan.0", (nl, BK, H), F32))
-            e.buf("dc.aan.1", (nl, BK, H), F32)
-        else:
-            for nm in ("k", "v"):
-                for half in (0, 1):
-                    e.buf("dc.%s.%d" % (nm, half), (nl, BK, max_steps, H))
-        state.bind_caches()
-        state["zero_flag"] = e.buf("dc.zflag", (1,), torch.int32)
-        return finish_state(state)
-
-    def finish_state(state):
-        """The part of a batch's state that does not depend on the step's dtype: the packed host <-> device buffers of
-        the search and the graph table."""
-        core = state["_core"]
-        e = core.eng
-        B, K, BK = state["B"], state["K"], state["BK"]
-        # per-step scalars live in device memory ({time, float bits of the length penalty, EOS-ban id}):
-        # a captured decode-step graph reads the current values at replay time
-        # what the host hands to a (replayed) step -- last tokens, previous log-probs, beam reorder index and
-        # the per-step scalars {time, float bits of the length penalty, EOS-ban id} -- is ONE pinned buffer
-        # and one async copy; what comes back (top-2K scores and flat indices) is one copy as well
-        pack = e.buf("bs.pack", (3 * BK + 4,), torch.int32)
-        state["pack_dev"] = pack
-        pins = core.__dict__.setdefault("_decode_pins", {})       # pinned staging survives the batch (pinning ~0.2 ms)
-
-        def pinned(name, n):
-            t = pins.get(name)
-            if t is None or t.numel() < n:
-                t = pins[name] = torch.zeros(n + n // 4, dtype=torch.int32).pin_memory()
-            t[:n].zero_()
-            return t[:n]
-        state["pack_host"] = pinned("pack", 3 * BK + 4)
-        state["tok"] = pack[0:BK]
-        state["prev"] = pack[BK:2 * BK].view(torch.float32)
-        state["idx"] = pack[2 * BK:3 * BK]
-        state["stepbuf"] = pack[3 * BK:3 * BK + 4]
-        out = e.buf("bs.out", (2, B, 2 * K), torch.int32)
-        state["out_dev"] = out
-        state["out_host"] = pinned("out", 2 * B * 2 * K).view(2, B, 2 * K)
-        state["ts"] = out[0].view(torch.float32)
-        state["ti"] = out[1]
-        state["graphs"] = {}
-        # every launch argument of a step is static: the time step (cache slot, number of valid keys,
-        # relative-position origin) is read from device memory by the kernels
-        state["static_ok"] = True
-        return state
+        return build_state(core, hp, model_name, source, hp.beam_size if beam_size is None else beam_size, max_steps)
 
     def step_static(state, temperature, forbid_value):
-        _step_static(state, temperature, forbid_value)
-        if state.get("_startup_held") and _startup_settled(state):
-            startup_end(state)
-
-    def _step_static(state, temperature, forbid_value):
         """One whole decode step with every per-step value read from device memory: beam reorder of
         the caches (indices chosen by the previous step), the AAN decoder step, logits, fused
-        log-softmax + length penalty + top-2K.  The launch sequence is identical every step (per
-        ping-pong parity), so after one eager pass per parity it is captured into a hipGraph."""
+        log-softmax + length penalty + top-2K."""
         core = state["_core"]
         e = core.eng
-        parity = state["_pp"]
         book = state.get("book")          # device-resident search bookkeeping (search._beam_search_device)
         if "_gkey" not in state:
             adopt_graphs(state, book, temperature, forbid_value, hp.enable_noise_beam_search)
-        g = state["graphs"].get(parity)
 
         def body():
             sb = state["stepbuf"]
             if book is not None:
                 e.lib.call("zk_beam_dev_prepare", *book, e.stream)
-            import os
-            state.reorder(state["idx"], time_dev=sb[0:1],
-                          defer_aan=core.aan)
+            state.reorder(state["idx"], time_dev=sb[0:1], defer_aan=core.aan)
             logits, _ = _step_cache(state["tok"], state, None, time_dev=sb[0:1])
             search_tail(state, core, logits, hp.enable_noise_beam_search, temperature, forbid_value)
-        if g is None and core.__dict__.get("_decode_warm_rows", 0) >= state["BK"]:
-            # A batch of at least this many beam rows has already been decoded on this engine, so the step's
-            # scratch buffers exist: capture straight away instead of spending an eager pass first.  If the
-            # capture does hit an allocation after all (a larger source length can grow a workspace), undo
-            # the python-side ping-pong flip of the aborted pass and take the eager route below.
-            pp0, gen0 = state["_pp"], e.realloc_gen
-            try:
-                gexec = e.graph_capture(body)
-                core._decode_step_launches = e.last_graph_nodes
-                if e.realloc_gen != gen0:
-                    e.lib.call("zk_graph_destroy", gexec)
-                    raise RuntimeError("buffer replaced during capture")
-                state["graphs"][parity] = gexec
-                e.graph_launch(gexec)
-                return
-            except Exception:
-                torch.cuda.synchronize(e.device)
-                state["_pp"] = pp0
-                state.bind_caches()
-                core._decode_warm_rows = 0
-        if g is None:
-            state["graphs"][parity] = "warm"
-            body()
-        elif g == "warm":
-            # capture: python-side ping-pong bookkeeping runs during capture exactly as in an eager call.  A capture
-            # that fails (an allocation met it: a workspace grew, or another thread allocated -- ROCm 7 invalidates
-            # captures across threads) must not cost the evaluation, and the training run with it: undo the
-            # python-side flip and run this step eagerly; the next step of this parity tries again.
-            pp0 = state["_pp"]
-            try:
-                gexec = e.graph_capture(body)
-            except Exception:
-                torch.cuda.synchronize(e.device)
-                state["_pp"] = pp0
-                state.bind_caches()
-                body()
-                return
-            state["graphs"][parity] = gexec
-            core._decode_step_launches = e.last_graph_nodes
-            e.graph_launch(gexec)
-        else:
-            state["_pp"] = 1 - state["_pp"]           # replay: redo the python-side pointer flip
-            state.bind_caches()
-            e.graph_launch(g)
+        run_step(state, core, body, True)
 
     def _step_cache(target, state, time, time_dev=None):
         core = state["_core"]
@@ -551,13 +635,7 @@ def make_infer_fns(params, model_name):
             # launch-per-op: projection, the softmax attention kernels, o_map, zk_fixup_residual (models/_fixup.py)
             from zero_amd.models._fixup import Fixup
             return Fixup(core, False).step(target, state, time, time_dev, hp)
-        import os as _os
-        zf = state["zero_flag"]
-        fuse_head = True
-        if not fuse_head:
-            e.lib.call("zk_all_equal", target.data_ptr(), BK, hp.tgt_vocab.pad(), zf.data_ptr(), e.stream)
-        import os as _os
-        fuse_ln = core.aan and _os.environ.get("ZERO_HIP_DECODE_FUSE_LN", "1") != "0"
+        fuse_ln = core.aan and os.environ.get("ZERO_HIP_DECODE_FUSE_LN", "1") != "0"
         # an attention sub-layer (projection, attention, the head's share of the output projection) as ONE launch per
         # (sentence, head) with the previous LayerNorm as its prologue (zk_dec_cross / zk_dec_self)
         fuse_att = bool(state.get("wt")) and _fuse_att_ok(core, hp, K)
@@ -613,13 +691,12 @@ def make_infer_fns(params, model_name):
                        None, None, parts.data_ptr(), nh, BK * H, core.b(p + "o_map/b_0").data_ptr(), None, None, 1.0,
                        None, e.stream)
             return out
-        ffn_split = 4 if fuse_att else 0
 
         def ffn_parts(x_in, f, l):
             """feed-forward sub-layer up to the output projection, left as split-K partial products (zk_gemm_parts: 64
             workgroups instead of 16 on 128 rows); the LayerNorm that follows adds them and the bias.  Returns the
             arguments of the row-local LayerNorm form (ln_args / zk_ln_decode)."""
-            import ctypes
+            ffn_split = 4
             hh = e.mat("dc%d.ff.h" % l, BK, core.F)
             W2 = core.W(f + "/ffn_layer/output/W_0_0")
             parts = e.buf("dc.ff.parts.%d" % (l & 1), (ffn_split, BK, H), F32)
@@ -631,21 +708,17 @@ def make_infer_fns(params, model_name):
                         bias=core.b(f + "/ffn_layer/output/b_0").data_ptr(), **ln_scope(f))
         pend = None          # base model: the feed-forward LayerNorm of the previous layer, left to the next prologue
         x = e.mat("dc.x", BK, H)
-        if fuse_head:
-            # all-pad test + embedding + timing (+ the first layer's average-attention update) in one launch
-            lay0 = state["decoder"]["state"]["layer_0"]
-            aan0 = core.aan
-            gat = state.pop("_aan_gather", None)       # the beam reorder of the running sums, deferred to this launch
-            e.lib.call("zk_dec_embed", target.data_ptr(), hp.tgt_vocab.pad(), core.store.s(core.tgt_emb).data_ptr(),
-                       core.b("bias").data_ptr(), e.timing(Tmax + 1, H).data_ptr(), x.ptr, BK, H, float(H) ** 0.5,
-                       0 if time_dev is not None else time, time_dev.data_ptr() if time_dev is not None else None,
-                       lay0["aan"].data_ptr() if aan0 else None, e.mat("dc.cat", BK, 2 * H).ptr if aan0 else None,
-                       1.0 if time_dev is not None else 1.0 / float(time + 1),
-                       gat[0].data_ptr() if gat else None, gat[1].data_ptr() if gat else None,
-                       hp.num_decoder_layer if gat else 0, e.stream)
-        else:
-            e.embed_fwd(target, core.store.s(core.tgt_emb), core.b("bias"), x, BK, 1, H,
-                        pos0=0 if time_dev is not None else time, zero_flag=zf, pos0_dev=time_dev, max_pos=Tmax)
+        # all-pad test + embedding + timing (+ the first layer's average-attention update) in one launch
+        lay0 = state["decoder"]["state"]["layer_0"]
+        aan0 = core.aan
+        gat = state.pop("_aan_gather", None)       # the beam reorder of the running sums, deferred to this launch
+        e.lib.call("zk_dec_embed", target.data_ptr(), hp.tgt_vocab.pad(), core.store.s(core.tgt_emb).data_ptr(),
+                   core.b("bias").data_ptr(), e.timing(Tmax + 1, H).data_ptr(), x.ptr, BK, H, float(H) ** 0.5,
+                   0 if time_dev is not None else time, time_dev.data_ptr() if time_dev is not None else None,
+                   lay0["aan"].data_ptr() if aan0 else None, e.mat("dc.cat", BK, 2 * H).ptr if aan0 else None,
+                   1.0 if time_dev is not None else 1.0 / float(time + 1),
+                   gat[0].data_ptr() if gat else None, gat[1].data_ptr() if gat else None,
+                   hp.num_decoder_layer if gat else 0, e.stream)
         for l in range(hp.num_decoder_layer):
             pre = "decoder/layer_%d" % l
             lay = state["decoder"]["state"]["layer_%d" % l]
@@ -654,7 +727,7 @@ def make_infer_fns(params, model_name):
                 cat = e.mat("dc.cat", BK, 2 * H)
                 inv = 1.0 if time_dev is not None else 1.0 / float(time + 1)
                 tdev = time_dev.data_ptr() if time_dev is not None else None
-                if not (fuse_ln and l > 0 and not hp.use_ffn) and not (fuse_head and l == 0):
+                if not (fuse_ln and l > 0 and not hp.use_ffn) and l != 0:
                     # else the previous layer's last LayerNorm (or the input launch) did it
                     e.lib.call("zk_aan_decode", x.ptr, lay["aan"].data_ptr(), cat.ptr, BK, H, inv, tdev, e.stream)
                 if hp.use_ffn:           # transformer_aan.py:176-183
@@ -664,24 +737,12 @@ def make_infer_fns(params, model_name):
                     core._linear(ya, a + "/ffn_layer/enlarge", hh, act=1)
                     core._linear(hh, a + "/ffn_layer/output", cat.cols_slice(H, 2 * H))
                 z = e.mat("dc.z", BK, 2 * H)
-                gate_split = 1 if fuse_att else 0
-                if gate_split <= 1:
-                    core._linear(cat, a + "/z_project", z)
+                core._linear(cat, a + "/z_project", z)
                 g = e.mat("dc.y", BK, H)
                 if fuse_att:
                     # gate + residual + LayerNorm ride as the prologue of the encoder-decoder attention launch
                     xo = e.mat("dc%d.aa.o" % l, BK, H)
                     pend = dict(x=x.ptr, ybuf=g.ptr, out=xo.ptr, z=z.ptr, cat=cat.ptr, **ln_scope(a))
-                    if gate_split > 1:
-                        # z_project (K = 2H) as split-K partial products, summed (+ bias) by the prologue
-                        import ctypes
-                        Wz = core.W(a + "/z_project/W_0_0")
-                        zp = e.buf("dc.z.parts", (gate_split, BK, 2 * H), F32)
-                        n = ctypes.c_int(0)
-                        e.lib.call("zk_gemm_parts", cat.ptr, Wz.ptr, zp.data_ptr(), BK, 2 * H, 2 * H, cat.ld, Wz.ld, 0, 0,
-                                   gate_split, ctypes.byref(n), e.stream)
-                        pend.update(z=None, parts=zp.data_ptr(), nparts=n.value, stride=BK * 2 * H,
-                                    bias=core.b(a + "/z_project/b_0").data_ptr())
                     x = xo
                 elif fuse_ln:
                     # gate + residual + LayerNorm in one launch (zk_ln_decode)
@@ -708,13 +769,7 @@ def make_infer_fns(params, model_name):
                 p = pre + "/self_attention/dot_attention/"
                 qkv = e.mat("dc.qkv", BK, 3 * H)
                 core._linear(x, p + "qkv_map", qkv)
-                for nm, c0 in (("k", H), ("v", 2 * H)):
-                    if time_dev is not None:
-                        e.lib.call("zk_cache_rows", qkv.ptr + c0 * 2, 3 * H * 2, None, lay[nm].data_ptr(),
-                                   Tmax * H * 2, BK, H * 2, Tmax, time_dev.data_ptr(), 0, 0, e.stream)
-                    else:
-                        e.lib.call("zk_gather_rows", qkv.ptr + c0 * 2, 3 * H * 2, None,
-                                   lay[nm].data_ptr() + time * H * 2, Tmax * H * 2, BK, H * 2, e.stream)
+                append_kv(e, qkv, lay, BK, H, Tmax, 2, time, time_dev)
                 att = e.mat("dc.att", BK, H)
                 rk = core.store.s(p + "rpr_keys/embeddings") if core.rpr else None
                 rv = core.store.s(p + "rpr_values/embeddings") if core.rpr else None
@@ -746,14 +801,7 @@ def make_infer_fns(params, model_name):
                 # feed-forward sub-layer; its residual + LayerNorm is the prologue of the next layer's self-attention
                 f = pre + "/feed_forward"
                 xo = e.mat("dc%d.ff.o" % l, BK, H)
-                if ffn_split > 1:
-                    la = ffn_parts(x, f, l)
-                else:
-                    hh = e.mat("dc%d.ff.h" % l, BK, core.F)
-                    core._linear(x, f + "/ffn_layer/enlarge", hh, act=1)
-                    y = e.mat("dc%d.ff.y" % (l & 1), BK, H)
-                    core._linear(hh, f + "/ffn_layer/output", y)
-                    la = dict(x=x.ptr, ybuf=y.ptr, **ln_scope(f))
+                la = ffn_parts(x, f, l)
                 la.update(out=xo.ptr, xmat=xo)
                 if nxt is not None:
                     pend = la
@@ -761,12 +809,12 @@ def make_infer_fns(params, model_name):
                     e.lib.call("zk_ln_decode", *ln_args(la)[:5], BK, *ln_args(la)[5:], e.stream)
                     x = xo
                 continue
-            if fuse_ln and core.aan and not hp.use_ffn and (nxt is not None or ffn_split > 1):
+            if fuse_ln and core.aan and not hp.use_ffn and (nxt is not None or fuse_att):
                 # feed-forward sub-layer whose LayerNorm also prepares the next layer's average attention
                 # (cache += x; cat = [x | cache / (time + 1)]) in the same launch
                 f = pre + "/feed_forward"
                 xo = e.mat("dc%d.ff.o" % l, BK, H)
-                if ffn_split > 1:
+                if fuse_att:
                     la = ffn_parts(x, f, l)
                 else:
                     hh = e.mat("dc%d.ff.h" % l, BK, core.F)
@@ -807,7 +855,6 @@ def make_infer_fns(params, model_name):
         if hp.search_mode == "cache":
             return _step_cache(target, state, time)
         if _f32.wanted(hp):
-            from zero_amd.hip import ZeroHipError
             raise ZeroHipError("decode_dtype=float32 decodes with search_mode=cache only (the dev mode re-runs the bf16 "
                                "training-path decoder, transformer.py:277-281)")
         return _step_dev(target, state, time)

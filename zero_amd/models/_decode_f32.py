@@ -17,7 +17,8 @@ caches double-buffered and reordered by one row gather); buffers are named ``dq.
 the same engine never alias.
 """
 
-import numpy as np
+import os
+
 import torch
 
 from zero_amd.func import Mat
@@ -43,7 +44,6 @@ class _Ops(object):
         self.core, self.e = core, core.eng
         self.lib = core.eng.lib
         self.H, self.nh, self.d = core.H, core.nh, core.d
-        import os
         # round 6: row-local launches folded into their neighbours (ZERO_HIP_F32_FUSE=0: one launch per op, as in round 5 --
         # the two forms are compared in tests/test_gpu_decode_f32.py)
         self.fold = os.environ.get("ZERO_HIP_F32_FUSE", "1") != "0"
@@ -54,6 +54,26 @@ class _Ops(object):
     def w(self, name):
         t = self.core.store.w(name)              # fp32 master (physical shape)
         return Mat(t, t.shape[0], t.shape[1])
+
+    def embed(self, ids, rows, L, table, out, max_pos, pos0=0, pos_dev=None, zero_flag=None):
+        """func.py:341-369: out = table[ids] * sqrt(H) + bias + timing signal of the row's position (row % L + pos0, or
+        + *pos_dev); rows of a step whose ids are all pad (*zero_flag) are zero embeddings."""
+        st = self.core.store
+        tim = self.e.timing(max_pos + 1, self.H)
+        self.lib.call("zk_f32_embed", ids.data_ptr(), rows, L, st.w(table).data_ptr(), st.w("bias").data_ptr(),
+                      tim.data_ptr(), int(tim.shape[0]), out.ptr, self.H, float(self.H) ** 0.5, pos0, pos_dev,
+                      zero_flag.data_ptr() if zero_flag is not None else None, self.e.stream)
+        return out
+
+    def embed_step(self, ids, rows, out, max_pos, pos0, pos_dev, pad, aan=None, cat=None):
+        """embed() of one decode position with the all-pad test inside the launch; aan / cat: the first layer's average
+        attention from the embedded row (cache tensor, cat Mat) in the same launch."""
+        st = self.core.store
+        tim = self.e.timing(max_pos + 1, self.H)
+        self.lib.call("zk_f32_embed_step", ids.data_ptr(), rows, st.w(self.core.tgt_emb).data_ptr(), st.w("bias").data_ptr(),
+                      tim.data_ptr(), int(tim.shape[0]), out.ptr, self.H, float(self.H) ** 0.5, pos0, pos_dev, pad,
+                      aan.data_ptr() if aan is not None else None, cat.ptr if cat is not None else None, self.e.stream)
+        return out
 
     def gemm(self, A, B, C, M, N, K, tb=0, bias=None, act=0):
         self.lib.call("zk_f32_gemm", A.ptr, B.ptr, C.ptr, M, N, K, A.ld, B.ld, C.ld, tb,
@@ -77,9 +97,10 @@ class _Ops(object):
         return out
 
     def attn(self, q, k, v, out, B, Lq, Lk, bsq, bsk, bsv, kmask=None, ldmask=0, kv_group=1, nkeys_dev=None, rpr=None,
-             q_pos0=0, q_pos_dev=None, kbias=None):
+             q_pos0=0, q_pos_dev=None, kbias=None, max_rel=None):
         """rpr: attention scope prefix (".../dot_attention/") whose rpr_keys / rpr_values tables take part, or None.
-        kbias: fp32 [.., ldmask] added to the scores (transformer_l0drop's log counts: zk_f32_attn_kb), or None."""
+        kbias: fp32 [.., ldmask] added to the scores (transformer_l0drop's log counts: zk_f32_attn_kb), or None.
+        max_rel: the clipping distance handed to the kernel (default: the model's max_relative_position)."""
         rk = rv = None
         if rpr is not None:
             rk = self.core.store.w(rpr + "rpr_keys/embeddings").data_ptr()
@@ -87,7 +108,7 @@ class _Ops(object):
         head = (q.ptr, k.ptr, v.ptr, out.ptr, B, self.nh, Lq, Lk, self.d, q.ld, k.ld, v.ld, out.ld, int(bsq), int(bsk), int(bsv),
                 int(Lq * out.ld), kmask.data_ptr() if kmask is not None else None, int(ldmask))
         tail = (int(kv_group), float(self.d) ** -0.5, zdtype.inf(), nkeys_dev.data_ptr() if nkeys_dev is not None else None,
-                rk, rv, int(self.core.hp.max_relative_position), int(q_pos0),
+                rk, rv, int(self.core.hp.max_relative_position if max_rel is None else max_rel), int(q_pos0),
                 q_pos_dev.data_ptr() if q_pos_dev is not None else None, self.e.stream)
         if kbias is not None:
             self.lib.call("zk_f32_attn_kb", *head, kbias.data_ptr(), *tail)
@@ -138,14 +159,11 @@ def encode(core, hp, batch):
         from zero_amd.models._fixup import Fixup
         return Fixup(core, True).encode(batch)
     o = _Ops(core)
-    e, H = core.eng, core.H
+    H = core.H
     B, Ls = batch["B"], batch["Ls"]
     T = B * Ls
     smask = batch["smask"]
-    x = o.mat("enc.x0", T, H)
-    e.lib.call("zk_f32_embed", batch["src"].data_ptr(), T, Ls, core.store.w(core.src_emb).data_ptr(),
-               core.store.w("bias").data_ptr(), e.timing(Ls + 1, H).data_ptr(), int(e.timing(Ls + 1, H).shape[0]), x.ptr, H,
-               float(H) ** 0.5, 0, None, None, e.stream)
+    x = o.embed(batch["src"], T, Ls, core.src_emb, o.mat("enc.x0", T, H), Ls)
     for l in range(hp.num_encoder_layer):
         pre = "encoder/layer_%d" % l
         p = pre + "/self_attention/dot_attention/"
@@ -165,112 +183,10 @@ def encode(core, hp, batch):
     return x, smask
 
 
-def make_state_class(base):
-    class DecodeStateF32(base):
-        """models/_decode.DecodeState with 4-byte cache elements and ``dq.*`` buffers."""
-
-        def reorder(self, index_dev, time_dev=None, defer_aan=False):
-            core = self["_core"]
-            e = core.eng
-            BK, H, t = self["BK"], core.H, self["time_filled"]
-            nl = core.hp.num_decoder_layer
-            pp = self["_pp"]
-            lay0 = self["decoder"]["state"]["layer_0"]
-            if "aan" in lay0:
-                src = e.buf("dq.aan.%d" % pp, (nl, BK, H), F32)
-                dst = e.buf("dq.aan.%d" % (1 - pp), (nl, BK, H), F32)
-                e.lib.call("zk_gather_rows_ex", src.data_ptr(), H * 4, index_dev.data_ptr(), dst.data_ptr(), H * 4,
-                           nl * BK, H * 4, BK, e.stream)
-            if "k" in lay0:
-                Tmax = self["Tmax"]
-                for nm in ("k", "v"):
-                    src = e.buf("dq.%s.%d" % (nm, pp), (nl, BK, Tmax, H), F32)
-                    dst = e.buf("dq.%s.%d" % (nm, 1 - pp), (nl, BK, Tmax, H), F32)
-                    if time_dev is not None:
-                        e.lib.call("zk_cache_rows", src.data_ptr(), Tmax * H * 4, index_dev.data_ptr(), dst.data_ptr(),
-                                   Tmax * H * 4, nl * BK, H * 4, Tmax, time_dev.data_ptr(), 1, BK, e.stream)
-                    else:
-                        e.lib.call("zk_gather_rows_ex", src.data_ptr(), Tmax * H * 4, index_dev.data_ptr(),
-                                   dst.data_ptr(), Tmax * H * 4, nl * BK, t * H * 4, BK, e.stream)
-            self["_pp"] = 1 - pp
-            self.bind_caches()
-
-        def bind_caches(self):
-            core = self["_core"]
-            e = core.eng
-            BK, H, nl, pp = self["BK"], core.H, core.hp.num_decoder_layer, self["_pp"]
-            for l in range(nl):
-                lay = self["decoder"]["state"]["layer_%d" % l]
-                if "aan" in lay:
-                    lay["aan"] = e.buf("dq.aan.%d" % pp, (nl, BK, H), F32)[l]
-                if "k" in lay:
-                    for nm in ("k", "v"):
-                        lay[nm] = e.buf("dq.%s.%d" % (nm, pp), (nl, BK, self["Tmax"], H), F32)[l]
-    return DecodeStateF32
-
-
-def encoding_state(core, hp, source, K, max_steps, state_cls, pad, trim_columns):
-    """encoding_fn of the fp32 mode: the state nest of models/_decode.py with fp32 tensors."""
-    check_model(core)
-    o = _Ops(core)
-    e, H = core.eng, core.H
-    if pad > 1:
-        src_np = trim_columns(np.asarray(source.cpu() if torch.is_tensor(source) else source))
-        src_np = np.pad(src_np, ((0, 0), (0, -src_np.shape[1] % pad)))
-        batch = core.upload(src_np, trim=False)
-        if max_steps is not None:
-            max_steps = -(-int(max_steps) // pad) * pad
-    else:
-        batch = core.upload(source)
-    B, Ls = batch["B"], batch["Ls"]
-    enc, smask = encode(core, hp, batch)
-    kbias = None
-    if core.l0drop:
-        # the pruned memory, its mask and its length stand in for the encoder output from here on (models/_l0drop.py)
-        from zero_amd.models import _l0drop
-        enc_keep, mask_keep, Ls, kbias = _l0drop.prune(core, enc, smask, B, Ls, pad, True)
-    else:
-        enc_keep = o.mat("enc", B * Ls, H)
-        enc_keep.t.copy_(enc.t)
-        mask_keep = e.buf("dq.smask", (B, Ls), F32)
-        mask_keep.copy_(smask)
-    if max_steps is None:
-        src_len = (np.asarray(source.cpu() if torch.is_tensor(source) else source) != 0).sum(1)
-        max_steps = -(-(int(src_len.max()) + hp.decode_length + 2) // pad) * pad
-    BK = B * K
-    state = state_cls()
-    state.update({"_core": core, "B": B, "K": K, "BK": BK, "Ls": Ls, "Tmax": max_steps, "encodes": enc_keep,
-                  "mask": mask_keep, "time_filled": 0, "decoder": {"state": {}}, "f32": True, "wt": {}})
-    if kbias is not None:
-        state["kbias"] = kbias
-    nl = hp.num_decoder_layer
-    for l in range(nl):
-        p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
-        kv = o.mat("%d.kv" % l, B * Ls, 2 * H)
-        o.linear(enc_keep, p + "k_map", kv.cols_slice(0, H))
-        o.linear(enc_keep, p + "v_map", kv.cols_slice(H, 2 * H))
-        lay = {"mk": kv.cols_slice(0, H), "mv": kv.cols_slice(H, 2 * H)}
-        if core.aan or core.fuse:
-            lay["aan"] = None
-        else:
-            lay["k"] = lay["v"] = None
-        state["decoder"]["state"]["layer_%d" % l] = lay
-    state["_pp"] = 0
-    if core.aan or core.fuse:
-        e.zero(e.buf("dq.aan.0", (nl, BK, H), F32))
-        e.buf("dq.aan.1", (nl, BK, H), F32)
-    else:
-        for nm in ("k", "v"):
-            for half in (0, 1):
-                e.buf("dq.%s.%d" % (nm, half), (nl, BK, max_steps, H), F32)
-    state.bind_caches()
-    state["zero_flag"] = e.buf("dq.zflag", (1,), torch.int32)
-    return state
-
-
 def step_cache(target, state, time, time_dev, hp):
     """One cached decoder step in fp32 (transformer.py:88-196 with cache / transformer_aan.py:165-260): -> logits Mat
     fp32 [B*K, Vpad].  time_dev: the step counter lives in device memory (hipGraph replay)."""
+    from zero_amd.models._decode import append_kv
     core = state["_core"]
     o = _Ops(core)
     e, H = core.eng, core.H
@@ -284,20 +200,17 @@ def step_cache(target, state, time, time_dev, hp):
     t_host = 0 if time_dev is not None else time
     fold = o.fold
     x = o.mat("x", BK, H)
-    tim = e.timing(Tmax + 1, H)
     nl = hp.num_decoder_layer
     cat = o.mat("cat", BK, 2 * H) if core.aan else None
     aan_in_ln = fold and core.aan           # a layer's average attention is computed by the launch that produces its input
     if fold:
         lay0 = state["decoder"]["state"]["layer_0"]
-        e.lib.call("zk_f32_embed_step", target.data_ptr(), BK, core.store.w(core.tgt_emb).data_ptr(),
-                   core.store.w("bias").data_ptr(), tim.data_ptr(), int(tim.shape[0]), x.ptr, H, float(H) ** 0.5, t_host, tdev,
-                   hp.tgt_vocab.pad(), lay0["aan"].data_ptr() if aan_in_ln else None, cat.ptr if aan_in_ln else None, e.stream)
+        o.embed_step(target, BK, x, Tmax, t_host, tdev, hp.tgt_vocab.pad(), lay0["aan"] if aan_in_ln else None,
+                     cat if aan_in_ln else None)
     else:
         zf = state["zero_flag"]
         e.lib.call("zk_all_equal", target.data_ptr(), BK, hp.tgt_vocab.pad(), zf.data_ptr(), e.stream)
-        e.lib.call("zk_f32_embed", target.data_ptr(), BK, 1, core.store.w(core.tgt_emb).data_ptr(), core.store.w("bias").data_ptr(),
-                   tim.data_ptr(), int(tim.shape[0]), x.ptr, H, float(H) ** 0.5, t_host, tdev, zf.data_ptr(), e.stream)
+        o.embed(target, BK, 1, core.tgt_emb, x, Tmax, t_host, tdev, zf)
     for l in range(nl):
         pre = "decoder/layer_%d" % l
         lay = state["decoder"]["state"]["layer_%d" % l]
@@ -325,13 +238,7 @@ def step_cache(target, state, time, time_dev, hp):
             p = pre + "/self_attention/dot_attention/"
             qkv = o.mat("qkv", BK, 3 * H)
             o.linear(x, p + "qkv_map", qkv)
-            for nm, c0 in (("k", H), ("v", 2 * H)):
-                if time_dev is not None:
-                    e.lib.call("zk_cache_rows", qkv.ptr + c0 * 4, 3 * H * 4, None, lay[nm].data_ptr(), Tmax * H * 4, BK,
-                               H * 4, Tmax, tdev, 0, 0, e.stream)
-                else:
-                    e.lib.call("zk_gather_rows", qkv.ptr + c0 * 4, 3 * H * 4, None, lay[nm].data_ptr() + time * H * 4,
-                               Tmax * H * 4, BK, H * 4, e.stream)
+            append_kv(e, qkv, lay, BK, H, Tmax, 4, time, time_dev)
             att = o.mat("att", BK, H)
             kc, vc = Mat(lay["k"], BK * Tmax, H), Mat(lay["v"], BK * Tmax, H)
             # one query per beam row over the positions 0 .. time of ITS cache (no padding mask on the target side,

@@ -86,15 +86,7 @@ def check_members(total_params):
     if M == 0:
         raise ZeroHipError("ensemble decoding needs at least one member (got none)")
     for i, p in enumerate(total_params):
-        if str(p.model_name).lower() == "transformer_l0drop":
-            raise ZeroHipError("ensemble member %d is a transformer_l0drop: its pruned memory has a length of its own per "
-                               "batch, the members of an ensemble step share one shape" % i)
-        if str(p.model_name).lower() == "transformer_rela":
-            raise NotImplementedError("ensemble member %d is a transformer_rela: the ensemble step is built from the fused "
-                                      "softmax attention launches, which this model does not use; composing it is not built" % i)
-        if str(p.model_name).lower() == "transformer_fixup":
-            raise NotImplementedError("ensemble member %d is a transformer_fixup: an untested member type (its step takes "
-                                      "the launch-per-op path, the ensemble step is built from the fused launches)" % i)
+        _dec.check_member(str(p.model_name).lower(), i)
     if M > max_members():
         raise ZeroHipError("ensemble decoding combines at most %d members per step (zk_ensemble_logprob); got %d"
                            % (max_members(), M))
@@ -184,18 +176,11 @@ def make_infer_fns(total_graphs, total_params):
         return combine(get_core(hp0, names[0]), logits, logits[0].rows), state
 
     def step_static(state, temperature, forbid_value):
-        _step_static(state, temperature, forbid_value)
-        if state.get("_startup_held") and _dec._startup_settled(state):
-            _dec.startup_end(state)
-
-    def _step_static(state, temperature, forbid_value):
-        """One whole ensemble step with every per-step value read from device memory (models/_decode.py _step_static):
+        """One whole ensemble step with every per-step value read from device memory (models/_decode.py step_static):
         bookkeeping head, every member's cache reorder, every member's decoder step, the combine, the search tail.  One
         eager pass per ping-pong parity sizes every member's scratch, the second is captured, the rest are replays."""
         core = state["_core"]
         e = core.eng
-        parity = state["_pp"]
-        g = state["graphs"].get(parity)
 
         def body():
             sb = state["stepbuf"]
@@ -207,27 +192,7 @@ def make_infer_fns(total_graphs, total_params):
                       for dec, m in zip(decs, state["members"])]
             _dec.search_tail(state, core, combine(core, logits, state["BK"]), hp0.enable_noise_beam_search, temperature,
                              forbid_value)
-        if g is None:
-            state["graphs"][parity] = "warm"
-            body()
-        elif g == "warm":
-            # as for a single model: a capture that fails (an allocation met it) costs one eager step, not the batch
-            pp0 = state["_pp"]
-            try:
-                gexec = e.graph_capture(body)
-            except Exception:
-                torch.cuda.synchronize(e.device)
-                state["_pp"] = pp0
-                state.bind_caches()
-                body()
-                return
-            state["graphs"][parity] = gexec
-            core._decode_step_launches = e.last_graph_nodes
-            e.graph_launch(gexec)
-        else:
-            state["_pp"] = 1 - state["_pp"]           # replay: redo the python-side pointer flip
-            state.bind_caches()
-            e.graph_launch(g)
+        _dec.run_step(state, core, body, False)
 
     decoding_fn.step_static = step_static
     return encoding_fn, decoding_fn, hp0

@@ -21,7 +21,7 @@ device, so captured step graphs stay valid across a weight reload.
 import torch
 
 from zero_amd.func import Mat
-from zero_amd.utils import dtype as zdtype
+from zero_amd.models import _decode_f32 as _f32
 
 F32 = torch.float32
 BF16 = torch.bfloat16
@@ -35,6 +35,7 @@ class Fixup(object):
         self.st = F32 if f32 else BF16
         self.esz = 4 if f32 else 2
         self.pre = "dq.fx." if f32 else "fx."          # (`dq.*`: a bf16 and an fp32 decode of one engine never alias)
+        self.ops = _f32._Ops(core) if f32 else None    # the zk_f32_* launches of the fp32 mode
 
     # ---- buffers and operands
     def mat(self, name, rows, cols):
@@ -62,7 +63,7 @@ class Fixup(object):
 
     def gemm(self, A, B, C, M, N, K, tb):
         if self.f32:
-            self.lib.call("zk_f32_gemm", A.ptr, B.ptr, C.ptr, M, N, K, A.ld, B.ld, C.ld, tb, None, 0, self.e.stream)
+            self.ops.gemm(A, B, C, M, N, K, tb)
         else:
             self.e.gemm(A, B, C, M, N, K, 0, tb)
 
@@ -80,10 +81,9 @@ class Fixup(object):
         if self.f32:
             if causal:
                 raise NotImplementedError("transformer_fixup: the fp32 mode has no causal attention (it decodes from caches)")
-            self.lib.call("zk_f32_attn", q.ptr, k.ptr, v.ptr, out.ptr, B, nh, Lq, Lk, d, q.ld, k.ld, v.ld, out.ld, int(bsq),
-                          int(bsk), int(bsv), int(Lq * out.ld), kmask.data_ptr() if kmask is not None else None,
-                          Lk if kmask is not None else 0, int(kv_group), float(d) ** -0.5, zdtype.inf(),
-                          time_dev.data_ptr() if (cached and time_dev is not None) else None, None, None, 0, 0, None, e.stream)
+            # (no relative positions: no tables, a clipping distance of 0, the query at position 0)
+            self.ops.attn(q, k, v, out, B, Lq, Lk, bsq, bsk, bsv, kmask=kmask, ldmask=Lk if kmask is not None else 0,
+                          kv_group=kv_group, nkeys_dev=time_dev if cached else None, max_rel=0)
             return
         if cached:
             e.attn_fwd(q, k, v, out, None, B, nh, 1, Lk, d, kmask=None, causal=False, q_pos0=0 if time_dev is not None else time,
@@ -139,11 +139,7 @@ class Fixup(object):
             smask = e.buf("smask", (B, Ls), F32)
             e.make_mask(batch["src"], smask, T)
         if self.f32:
-            x0 = self.mat("enc.x0", T, H)
-            tim = e.timing(Ls + 1, H)
-            self.lib.call("zk_f32_embed", batch["src"].data_ptr(), T, Ls, core.store.w(core.src_emb).data_ptr(),
-                          core.store.w("bias").data_ptr(), tim.data_ptr(), int(tim.shape[0]), x0.ptr, H, float(H) ** 0.5, 0,
-                          None, None, e.stream)
+            x0 = self.ops.embed(batch["src"], T, Ls, core.src_emb, self.mat("enc.x0", T, H), Ls)
         else:
             x0 = e.mat("enc.x0", T, H)
             if not core.__dict__.get("_embeds_done"):      # (forward(): both embeddings went out as one launch)
@@ -191,19 +187,17 @@ class Fixup(object):
     def step(self, target, state, time, time_dev, hp):
         """One cached decoder step (transformer_fixup.py:91-203 with state['decoder']) -> (logits Mat fp32 [B*K, Vpad],
         state).  time_dev: the step counter lives in device memory (hipGraph replay)."""
+        from zero_amd.models._decode import append_kv
         core, e, H = self.core, self.e, self.H
         BK, K, Ls, Tmax = state["BK"], state["K"], state["Ls"], state["Tmax"]
         tdev = time_dev.data_ptr() if time_dev is not None else None
         t_host = 0 if time_dev is not None else time
-        esz = self.esz
-        tim = e.timing(Tmax + 1, H)
         x0 = self.mat("dc.x0", BK, H)
         # the first-step zero embedding and the timing signal: the launches of the other models
         if self.f32:
-            self.lib.call("zk_f32_embed_step", target.data_ptr(), BK, core.store.w(core.tgt_emb).data_ptr(),
-                          core.store.w("bias").data_ptr(), tim.data_ptr(), int(tim.shape[0]), x0.ptr, H, float(H) ** 0.5, t_host,
-                          tdev, hp.tgt_vocab.pad(), None, None, e.stream)
+            self.ops.embed_step(target, BK, x0, Tmax, t_host, tdev, hp.tgt_vocab.pad())
         else:
+            tim = e.timing(Tmax + 1, H)
             self.lib.call("zk_dec_embed", target.data_ptr(), hp.tgt_vocab.pad(), core.store.s(core.tgt_emb).data_ptr(),
                           core.b("bias").data_ptr(), tim.data_ptr(), x0.ptr, BK, H, float(H) ** 0.5, t_host, tdev, None, None,
                           1.0, None, None, 0, e.stream)
@@ -212,13 +206,7 @@ class Fixup(object):
         def self_attn(l, p, XS):
             lay = layers["layer_%d" % l]
             qkv = self.linear(XS, p + "qkv_map", self.mat("dc.qkv", BK, 3 * H))
-            for nm, c0 in (("k", H), ("v", 2 * H)):         # the cache append of the other models
-                if time_dev is not None:
-                    self.lib.call("zk_cache_rows", qkv.ptr + c0 * esz, 3 * H * esz, None, lay[nm].data_ptr(), Tmax * H * esz, BK,
-                                  H * esz, Tmax, tdev, 0, 0, e.stream)
-                else:
-                    self.lib.call("zk_gather_rows", qkv.ptr + c0 * esz, 3 * H * esz, None, lay[nm].data_ptr() + time * H * esz,
-                                  Tmax * H * esz, BK, H * esz, e.stream)
+            append_kv(e, qkv, lay, BK, H, Tmax, self.esz, time, time_dev)
             att = self.mat("dc.att", BK, H)
             self.attn(qkv.cols_slice(0, H), Mat(lay["k"], BK * Tmax, H), Mat(lay["v"], BK * Tmax, H), att, BK, 1,
                       Tmax if time_dev is not None else time + 1, 3 * H, Tmax * H, Tmax * H, time=time, time_dev=time_dev,
