@@ -602,6 +602,37 @@ int zk_f32_embed_step(const int* ids, int rows, const float* table, const float*
                       zk_stream_t stream);
 int zk_f32_gemm_legacy(int on);
 
+/* ---- the fp32 scorer (hp.score_dtype = "float32"; zero_amd/csrc/zk_f32_seq.hip, zero_amd/models/_score_f32.py): the
+ * training-path forward of transformer.py:15-216 on fp32 masters, activations and accumulation.  It runs on the zk_f32_*
+ * entry points above plus three full-sequence kernels:
+ *   zk_f32_attn_seq     func.py:218-256 for Lq >= 1 query rows per sentence, operands as zk_f32_attn (ld* row strides, bs*
+ *                       sentence strides in elements, head h at columns h d ..; kmask fp32 [B, ldmask] may be NULL:
+ *                       + (1 - kmask) * (-mask_inf), func.py:372-387, finite -- a fully masked row comes out uniform;
+ *                       rpr_k / rpr_v may be NULL, modules/rpr.py:10-75: logits += q . r_k[clip(i - j, -max_rel, max_rel)
+ *                       + max_rel], o += sum_j p_j r_v[...], i = q_pos0 + row).  causal != 0 (func.py:388-391, the
+ *                       decoder's self-attention, transformer.py:128-137): keys j > i take no part -- probability exactly 0,
+ *                       which is what the reference's additive -1e8 gives in fp32 -- and key tiles above a row block are not
+ *                       visited; causal together with kmask is refused (transformer.py:136 puts no padding mask on the
+ *                       target side).  One workgroup per block of 32 query rows of a (sentence, head); keys and values
+ *                       staged in LDS in tiles of 64, once per block; online softmax, fp32 throughout; LDS use does not
+ *                       depend on Lk.  d % 4 == 0, d <= 128, key rows 16-byte aligned.  B = 0 returns 0.
+ *   zk_f32_cumavg       transformer_aan.py:92-108 on the training path: out[b, t] = (add[b, t] +) the running mean of x[b, 0..t]
+ *                       per channel, summed in position order.  use_mask 1 (aan_mask, func.py:392-400): padded positions
+ *                       neither count nor contribute and average to zero; use_mask 0 (transformer_aan.py:102-107): every x
+ *                       contributes, the divisor is the number of valid positions so far (1 where that is 0).  x / add / out
+ *                       are row windows (ldx / lda / ldo elements): out may be the right half of z_project's [x | avg]
+ *                       input; add (may be NULL) is the cross-attention output of transformer_fuse (func.py:258-275).
+ *   zk_f32_embed_shift  transformer.py:88-112: row i of a sentence of L rows = table[ids[i - 1]] * scale + bias, row 0 = zeros;
+ *                       + timing[i] on every row (func.py:341-369). */
+int zk_f32_attn_seq(const float* q, const float* k, const float* v, float* out, int B, int nh, int Lq, int Lk, int d, int ldq,
+                    int ldk, int ldv, int ldo, long bsq, long bsk, long bsv, long bso, const float* kmask, int ldmask,
+                    float scale, float mask_inf, const float* rpr_k, const float* rpr_v, int max_rel, int q_pos0, int causal,
+                    zk_stream_t stream);
+int zk_f32_cumavg(const float* x, int ldx, const float* mask, const float* add, int lda, float* out, int ldo, int B, int L,
+                  int H, int use_mask, zk_stream_t stream);
+int zk_f32_embed_shift(const int* ids, int rows, int L, const float* table, const float* bias, const float* timing,
+                       int timing_rows, float* out, int H, float scale, zk_stream_t stream);
+
 /* ---- transformer_l0drop at inference (models/transformer_l0drop.py:16-135, 244-273; modules/l0norm.py:75-96, 166-177)
  * A learned hard-concrete gate drops encoder outputs; cross-attention runs over the kept ones plus ONE slot (index 0, a
  * zero key / value) that carries the number of dropped positions as its softmax weight.

@@ -58,6 +58,9 @@ _DEFAULTS = [
     # build-specific (round 5): "bfloat16" = the product decode path; "float32" = fp32 masters / activations / accumulation
     # through zk_f32_* (zero_amd/models/_decode_f32.py): rounds where the reference's default dtype rounds
     ("decode_dtype", "bfloat16"),
+    # build-specific: "bfloat16" = score_fn runs the bf16 training-path forward; "float32" (same spellings as decode_dtype) =
+    # the fp32 scorer (zero_amd/models/_score_f32.py).  decode_dtype does not select it: it keeps meaning decoding only
+    ("score_dtype", "bfloat16"),
     ("l0_norm_reg_scalar", 1.0), ("l0_norm_start_reg_ramp_up", 0),
     ("l0_norm_end_reg_ramp_up", 10000), ("l0_norm_warm_up", True),
 ]

@@ -120,10 +120,17 @@ def build(model_name):
         params = copy.copy(params)
         params = closing_dropout(params)
         params.label_smooth = 0.0
+        from zero_amd.models import _score_f32
+        f32 = _score_f32.wanted(params)      # (score_dtype; decode_dtype keeps meaning decoding only)
+        if f32 and model_name == "transformer_fixup":
+            raise NotImplementedError("transformer_fixup has no score_dtype=float32 path: its fp32 residual-stream scorer "
+                                      "is not built (score it with score_dtype=bfloat16)")
         core = get_core(params, model_name, initializer)
         if _n_sentences(features) == 0:
             return {"score": torch.zeros(0, dtype=torch.float32, device=core.store.device)}
         batch = features if "B" in features else core.upload(features["source"], features["target"])
+        if f32:
+            return {"score": _score_f32.score(core, params, batch)}
         _, per_sample, _ = core.forward(batch, train=False, save=False, label_smooth=0.0)
         return {"score": per_sample}
 
