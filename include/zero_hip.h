@@ -716,6 +716,49 @@ int zk_fixup_relu_shift(const void* h, int ldh, const float* offset, void* out, 
 int zk_f32_fixup_relu_shift(const float* h, int ldh, const float* offset, float* out, int ldo, int rows, int F,
                             zk_stream_t stream);
 
+/* ---- rnnsearch at inference (models/rnnsearch.py; rnns/rnn.py, rnns/atr.py:32-60; func.py:107-161): zk_rnn.hip.
+ * bf16 forms: GEMM operands (U, p, the projected memory, the memory, the copies) are bf16, arithmetic fp32;
+ * zk_f32_* forms: fp32 throughout.  Strides in elements.  -1 and a message on a bad argument, nothing launched.
+ *   zk_rnn_atr_step   ONE time step of ONE ATR cell (twin gates) for R rows, with the mask carry of rnns/rnn.py:41-49:
+ *                       q = h U + b;  i = sigmoid(p + q);  f = sigmoid(p - q);  o = i p + f h;  out = m o + (1 - m) h
+ *                     h = h_prev[idx[r]] (idx NULL: row r; h_prev NULL: the zero state); h_prev fp32 [n_prev, H], row
+ *                     stride ldh; index values are clamped to 0 .. n_prev - 1.  U [H, H] (bf16 shadow / fp32 master),
+ *                     b fp32 [H], p [R, H] the precomputed input projection.  mask NULL or fp32, the value of row r at
+ *                     mask[r ldm].  out: the fp32 state (stride ldo, so a scan can write into [B, Ls, H] at its
+ *                     position); out_copy (may be NULL): the same in the storage type.  The state is fp32 in both forms;
+ *                     in the bf16 form only the matrix-core operand is a rounded copy of h.  out must not overlap
+ *                     h_prev (every column tile reads whole rows of it): refused.  bf16 form: H % 8 == 0, H <= 4096.
+ *   zk_add_attn       additive attention of one decode step for R = (sentences x kv_group) beam rows:
+ *                       logit_j = v . tanh(qa + pm_j) + (1 - kmask_j) * -neg;  a = softmax_j;  ctx = sum_j a_j mem_j
+ *                     qa [R, M]; pm, mem [R / kv_group, Ls, M] (row stride ld*, sentence stride bs*): read once for the
+ *                     kv_group rows of a sentence; v fp32 [M]; kmask NULL or fp32 [R / kv_group, ldmask] (1 = valid).
+ *                     ctx fp32 [R, M]; ctx_copy (may be NULL) the same in the storage type.  Any Ls (online softmax over
+ *                     tiles of 64 keys); M <= 2048; bf16 form: M, ldpm, bspm multiples of 8.
+ *   zk_rnn_embed      out[r] = table[ids[r]] + bias (no scale, no timing signal); zeros where pad >= 0 and EVERY id of
+ *                     the launch equals pad (rnnsearch.py:101-103).  table [V, E] of the storage type, bias fp32.
+ *   zk_rnn_bias_tanh  y = tanh(x + bias) for fp32 rows x (bias may be NULL); input row r is written to the output rows
+ *                     r rep .. r rep + rep - 1 of out_f32 (fp32) and / or out_copy (storage type). */
+int zk_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const void* U, int ldu, const float* b,
+                    const void* p, int ldp, const float* mask, int ldm, float* out, int ldo, void* out_copy, int ldc, int R,
+                    int H, zk_stream_t stream);
+int zk_f32_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const float* U, int ldu, const float* b,
+                        const float* p, int ldp, const float* mask, int ldm, float* out, int ldo, float* out_copy, int ldc,
+                        int R, int H, zk_stream_t stream);
+int zk_add_attn(const void* qa, int ldq, const void* pm, int ldpm, long bspm, const void* mem, int ldmem, long bsmem,
+                const float* v, const float* kmask, int ldmask, float* ctx, int ldo, void* ctx_copy, int ldc, int R,
+                int kv_group, int Ls, int M, float neg, zk_stream_t stream);
+int zk_f32_add_attn(const float* qa, int ldq, const float* pm, int ldpm, long bspm, const float* mem, int ldmem, long bsmem,
+                    const float* v, const float* kmask, int ldmask, float* ctx, int ldo, float* ctx_copy, int ldc, int R,
+                    int kv_group, int Ls, int M, float neg, zk_stream_t stream);
+int zk_rnn_embed(const int* ids, int rows, const void* table, int V, const float* bias, void* out, int ldo, int E, int pad,
+                 zk_stream_t stream);
+int zk_f32_rnn_embed(const int* ids, int rows, const float* table, int V, const float* bias, float* out, int ldo, int E,
+                     int pad, zk_stream_t stream);
+int zk_rnn_bias_tanh(const float* x, int ldx, const float* bias, float* out_f32, int ldo, void* out_copy, int ldc, int rows,
+                     int cols, int rep, zk_stream_t stream);
+int zk_f32_rnn_bias_tanh(const float* x, int ldx, const float* bias, float* out_f32, int ldo, float* out_copy, int ldc,
+                         int rows, int cols, int rep, zk_stream_t stream);
+
 /* hipGraph plumbing: capture a sequence of the calls above once, replay per step */
 int zk_graph_begin(zk_stream_t stream);
 int zk_graph_end(zk_stream_t stream, void** exec_out);

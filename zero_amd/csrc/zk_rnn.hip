@@ -1,0 +1,533 @@
+// zk_rnn.hip -- the recurrent family at inference: `rnnsearch` (models/rnnsearch.py; rnns/rnn.py, rnns/atr.py,
+// func.py:107-161 additive_attention).  bf16 forms (bf16 GEMM operands, fp32 arithmetic) and fp32 forms (zk_f32_*).
+//
+// ATR cell (rnns/atr.py:32-60, twin gates) for one time step of R rows, with the mask carry of rnns/rnn.py:41-49:
+//     q = h_prev U + b      i = sigmoid(p + q)      f = sigmoid(p - q)      h = i p + f h_prev
+//     out = m h + (1 - m) h_prev
+// p is the input projection (x W, computed for the whole sequence by one GEMM), h_prev the fp32 state, optionally
+// gathered by a row index (the beam reorder of a decode step) or absent (the zero state).  The state is fp32 in BOTH
+// forms: nothing re-normalises a recurrent state, so a bf16 state would lose every update below half an ulp of h and
+// the loss would compound over the sequence.  In the bf16 form only the MFMA operand is a rounded copy of h_prev;
+// f h_prev and the carry use the fp32 value.  out_copy is the state in the storage type: the operand of the next GEMM.
+//
+// Grid of zk_rnn_atr_step: one workgroup (4 waves) per 16 output columns and 64 rows, wave w owns rows 16 w .. 16 w + 15.
+// Why: R is 32 .. 128 rows and H about 1000, so one step is ~0.25 GFLOP against 2 MB of U -- the launch is a latency
+// chain, not a throughput problem.  16-column tiles give H / 16 = 63 workgroups for H = 1000 (two for R = 128), each of
+// which streams a 32-row-stride slab of U ONCE (H x 16 bf16 = 32 KB) into a transposed LDS image [16][K + 8] so that the
+// B fragments are 16-byte LDS reads; wider tiles would halve the number of CUs that pull U, narrower ones waste the
+// MFMA's 16 columns.  The A fragments (h_prev rows, fp32 -> bf16) come straight from global memory: every wave reads
+// its own 16 rows once.  Edge tiles in rows, columns and K are zero-filled.  v_mfma_f32_16x16x32_bf16 fragment maps
+// (zk_attn_dev.h frag / mfma16): A lane l = row l & 15, k = 8 (l >> 4) + j; B the same with the column; D column l & 15,
+// row 4 (l >> 4) + reg.
+// Grid of zk_f32_rnn_atr_step: one workgroup per 64 columns and 32 rows; lane = column (coalesced rows of U), wave w owns
+// rows 8 w .. 8 w + 7 whose h_prev chunk [32][64] sits in LDS (broadcast reads); k ascending, fused multiply-adds.
+//
+// Additive attention of one decode step (func.py:107-161; one head, rnns/rnn.py:131-136):
+//     logit_j = v . tanh(qa + pm_j) + (1 - mask_j) * -inf_const        a = softmax_j        c = sum_j a_j mem_j
+// (feed_logits/b_0 shifts a whole row and drops out of the softmax).  One workgroup per block of up to ADD_RB beam rows
+// that share one source sentence (kv_group rows per sentence): projected memory pm and memory mem are read once for the
+// block.  Keys in tiles of 64 with an online softmax, so any Ls:
+//   phase A   wave w forms the logits of the keys 16 w .. 16 w + 15 of the tile, lanes over the channels (16-byte loads);
+//   phase B   wave r rescales row r: new running maximum, p_j = exp(logit_j - max), running sum;
+//   phase C   thread c adds sum_j p_j mem_j[c] to its accumulators (coalesced rows of mem).
+// A masked key's logit is about -inf_const, its weight exp(-inf_const - max) is exactly 0.  tanhf saturates to +-1.
+#include <float.h>
+#include <math.h>
+#include "zk_common.h"
+
+typedef __bf16 rbf16x8_t __attribute__((ext_vector_type(8)));
+typedef float rf32x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float rnn_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+// ---------------------------------------------------------------- ATR step, bf16 form
+#define ATR_BN 16          // output columns per workgroup
+#define ATR_BM 64          // rows per workgroup (16 per wave)
+
+__global__ void __launch_bounds__(256) k_rnn_atr_step(const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                      const int* __restrict__ idx, const bf16_t* __restrict__ U, int ldu,
+                                                      const float* __restrict__ b, const bf16_t* __restrict__ p, int ldp,
+                                                      const float* __restrict__ mask, int ldm, float* __restrict__ out,
+                                                      int ldo, bf16_t* __restrict__ out_copy, int ldc, int R, int H,
+                                                      int vec_a) {
+  extern __shared__ __align__(16) unsigned char atr_lds[];
+  bf16_t* sU = reinterpret_cast<bf16_t*>(atr_lds);            // [ATR_BN][KS]: U[:, n0 .. n0 + 15] transposed
+  const int Kr = (H + 31) / 32 * 32, KS = Kr + 8;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
+  rf32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+  if (h_prev != nullptr) {
+    for (int k = threadIdx.x; k < Kr; k += 256) {
+      uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = lo;
+      if (k < H) {                                             // (H % 8 == 0: a group of 8 columns is inside or outside)
+        const bf16_t* up = U + (size_t)k * ldu + n0;
+        if (n0 < H) lo = *reinterpret_cast<const uint4*>(up);
+        if (n0 + 8 < H) hi = *reinterpret_cast<const uint4*>(up + 8);
+      }
+      const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        sU[(2 * c) * KS + k] = (bf16_t)(w[c] & 0xffffu);
+        sU[(2 * c + 1) * KS + k] = (bf16_t)(w[c] >> 16);
+      }
+    }
+    __syncthreads();
+    if (r0 < R) {                                              // wave-uniform: the MFMA runs with all 64 lanes
+      const int row = r0 + (lane & 15);
+      const bool valid = row < R;
+      int src = valid ? (idx != nullptr ? idx[row] : row) : 0;
+      src = min(max(src, 0), n_prev - 1);
+      const float* hp = h_prev + (size_t)src * ldh;
+      const bf16_t* bt = sU + (lane & 15) * KS + (lane >> 4) * 8;
+      for (int kk = 0; kk < Kr; kk += 32) {
+        const int k = kk + (lane >> 4) * 8;
+        float a[8];
+        if (vec_a) {
+          float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
+          if (valid && k < H) {
+            x0 = *reinterpret_cast<const float4*>(hp + k);
+            x1 = *reinterpret_cast<const float4*>(hp + k + 4);
+          }
+          a[0] = x0.x; a[1] = x0.y; a[2] = x0.z; a[3] = x0.w; a[4] = x1.x; a[5] = x1.y; a[6] = x1.z; a[7] = x1.w;
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) a[e] = (valid && k + e < H) ? hp[k + e] : 0.f;
+        }
+        const uint4 af = pack8(a);
+        const uint4 bf = *reinterpret_cast<const uint4*>(bt + kk);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(rbf16x8_t, af), __builtin_bit_cast(rbf16x8_t, bf),
+                                                      acc, 0, 0, 0);
+      }
+    }
+  }
+  const int col = n0 + (lane & 15);
+  if (col >= H) return;
+  const float bias = b[col];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = r0 + (lane >> 4) * 4 + r;
+    if (row >= R) continue;
+    float hv = 0.f;
+    if (h_prev != nullptr) {
+      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
+      hv = h_prev[(size_t)src * ldh + col];
+    }
+    const float q = acc[r] + bias;
+    const float pv = bf2f(p[(size_t)row * ldp + col]);
+    float h = rnn_sigmoid(pv + q) * pv + rnn_sigmoid(pv - q) * hv;
+    if (mask != nullptr) {
+      const float m = mask[(size_t)row * ldm];
+      h = m * h + (1.f - m) * hv;
+    }
+    out[(size_t)row * ldo + col] = h;
+    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = f2bf(h);
+  }
+}
+
+// ---------------------------------------------------------------- ATR step, fp32 form
+#define ATRF_BN 64
+#define ATRF_BM 32
+
+__global__ void __launch_bounds__(256) k_f32_rnn_atr_step(const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                          const int* __restrict__ idx, const float* __restrict__ U, int ldu,
+                                                          const float* __restrict__ b, const float* __restrict__ p, int ldp,
+                                                          const float* __restrict__ mask, int ldm, float* __restrict__ out,
+                                                          int ldo, float* __restrict__ out_copy, int ldc, int R, int H) {
+  __shared__ float sh[ATRF_BM][64];                            // h_prev[rows of the block][k chunk]
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int col = blockIdx.x * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  if (h_prev != nullptr) {
+    const int lr = threadIdx.x >> 3, lk = (threadIdx.x & 7) * 8;       // this thread stages row lr, 8 values from lk
+    const int grow = r0 + lr;
+    int src = grow < R ? (idx != nullptr ? idx[grow] : grow) : 0;
+    src = min(max(src, 0), n_prev - 1);
+    const float* hp = h_prev + (size_t)src * ldh;
+    for (int k0 = 0; k0 < H; k0 += 64) {
+      __syncthreads();
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sh[lr][lk + e] = (grow < R && k0 + lk + e < H) ? hp[k0 + lk + e] : 0.f;
+      __syncthreads();
+      const int kn = min(64, H - k0);
+      if (col < H) {
+        for (int kk = 0; kk < kn; ++kk) {
+          const float u = U[(size_t)(k0 + kk) * ldu + col];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] = fmaf(sh[wave * 8 + j][kk], u, acc[j]);
+        }
+      }
+    }
+  }
+  if (col >= H) return;
+  const float bias = b[col];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = r0 + wave * 8 + j;
+    if (row >= R) continue;
+    float hv = 0.f;
+    if (h_prev != nullptr) {
+      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
+      hv = h_prev[(size_t)src * ldh + col];
+    }
+    const float q = acc[j] + bias;
+    const float pv = p[(size_t)row * ldp + col];
+    float h = rnn_sigmoid(pv + q) * pv + rnn_sigmoid(pv - q) * hv;
+    if (mask != nullptr) {
+      const float m = mask[(size_t)row * ldm];
+      h = m * h + (1.f - m) * hv;
+    }
+    out[(size_t)row * ldo + col] = h;
+    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = h;
+  }
+}
+
+// true when some row [a + r lda, + w) (r < ra) shares an element with some row [b + s ldb, + w) (s < rb)
+static bool rnn_rows_overlap(const float* a, long lda, long ra, const float* b, long ldb, long rb, long w) {
+  if (a == nullptr || b == nullptr || ra <= 0 || rb <= 0 || w <= 0) return false;
+  const uintptr_t a0 = (uintptr_t)a, a1 = (uintptr_t)(a + (ra - 1) * lda + w);
+  const uintptr_t b0 = (uintptr_t)b, b1 = (uintptr_t)(b + (rb - 1) * ldb + w);
+  if (a1 <= b0 || b1 <= a0) return false;
+  if (lda != ldb || lda < w) return true;                      // different pitches: the enclosing ranges decide
+  const long bytes = (long)((intptr_t)a0 - (intptr_t)b0);
+  if (bytes % 4 != 0) return true;
+  // equal pitch: row r of a sits delta + (r - s) ld elements from row s of b; the two candidates nearest to zero
+  const long delta = bytes / 4, ld = lda;
+  long m = delta % ld;
+  if (m < 0) m += ld;
+  const long d_lo = -(delta - m) / ld;                         // delta + d_lo ld = m          (0 <= m < ld)
+  const long cand[2][2] = {{d_lo, m}, {d_lo - 1, m - ld}};
+  for (int i = 0; i < 2; ++i) {
+    const long d = cand[i][0], diff = cand[i][1];
+    if (d >= -(rb - 1) && d <= ra - 1 && diff < w && -diff < w) return true;
+  }
+  return false;
+}
+
+#define ATR_CHECK_COMMON(NAME)                                                                                              \
+  ZK_CHECK_ARG(U != nullptr && b != nullptr && p != nullptr && out != nullptr, NAME ": U, b, p and out are required");      \
+  ZK_CHECK_ARG(R >= 0 && H >= 1, NAME ": bad shape (R=%d H=%d)", R, H);                                                     \
+  ZK_CHECK_ARG(ldu >= H && ldp >= H && ldo >= H && (out_copy == nullptr || ldc >= H) && (h_prev == nullptr || ldh >= H),    \
+               NAME ": a leading dimension is smaller than H=%d (ldh=%d ldu=%d ldp=%d ldo=%d ldc=%d)", H, ldh, ldu, ldp,    \
+               ldo, ldc);                                                                                                   \
+  ZK_CHECK_ARG(h_prev == nullptr || (idx != nullptr ? n_prev >= 1 : n_prev >= R),                                           \
+               NAME ": h_prev has n_prev=%d rows (R=%d without an index, at least 1 with one)", n_prev, R);                 \
+  ZK_CHECK_ARG(mask == nullptr || ldm >= 1, NAME ": the mask stride must be at least 1 (ldm=%d)", ldm);                     \
+  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, h_prev, ldh, n_prev, H),                                                      \
+               NAME ": out overlaps h_prev (every column tile reads whole rows of h_prev while others write out)")
+
+// ---------------------------------------------------------------- additive attention
+#define ADD_RB 4           // beam rows per workgroup (1 when a sentence has a single row)
+#define ADD_CC 8           // 256-channel chunks a thread accumulates: M <= 2048
+
+template <bool F32, int NV>
+__device__ __forceinline__ void add_load(const void* base, size_t elem, float (&f)[NV]) {
+  if constexpr (!F32) {
+    unpack8(*reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(base) + elem), f);
+  } else if constexpr (NV == 4) {
+    const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + elem);
+    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+  } else {
+    f[0] = reinterpret_cast<const float*>(base)[elem];
+  }
+}
+template <bool F32>
+__device__ __forceinline__ float add_load1(const void* base, size_t elem) {
+  return F32 ? reinterpret_cast<const float*>(base)[elem] : bf2f(reinterpret_cast<const bf16_t*>(base)[elem]);
+}
+
+template <bool F32, int NV, int RB>
+__global__ void __launch_bounds__(256) k_add_attn(const void* __restrict__ qa, int ldq, const void* __restrict__ pm, int ldpm,
+                                                  long bspm, const void* __restrict__ mem, int ldmem, long bsmem,
+                                                  const float* __restrict__ v, const float* __restrict__ kmask, int ldmask,
+                                                  float* __restrict__ ctx, int ldo, void* __restrict__ ctx_copy, int ldc,
+                                                  int kv_group, int Ls, int M, float neg, int blocks_per_mem) {
+  extern __shared__ float add_sm[];
+  float* sq = add_sm;                               // [RB][M]: the projected queries
+  float* sv = sq + (size_t)RB * M;                  // [M]: feed_logits/W_0_0
+  float* sw = sv + M;                               // [RB][64]: logits, then weights of one key tile
+  float* st = sw + RB * 64;                         // [3][RB]: running maximum, running sum, rescale factor of the tile
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int bk = blockIdx.x / blocks_per_mem;
+  const int g0 = (blockIdx.x % blocks_per_mem) * RB;
+  const int nrows = min(RB, kv_group - g0);
+  for (int r = 0; r < RB; ++r) {
+    const size_t row = (size_t)(bk * kv_group + g0 + r) * ldq;
+    for (int c = threadIdx.x; c < M; c += 256) sq[r * M + c] = r < nrows ? add_load1<F32>(qa, row + c) : 0.f;
+  }
+  for (int c = threadIdx.x; c < M; c += 256) sv[c] = v[c];
+  if (threadIdx.x < RB) {
+    st[threadIdx.x] = -FLT_MAX;
+    st[RB + threadIdx.x] = 0.f;
+    st[2 * RB + threadIdx.x] = 0.f;
+  }
+  __syncthreads();
+
+  float acc[RB][ADD_CC];
+#pragma unroll
+  for (int r = 0; r < RB; ++r)
+#pragma unroll
+    for (int cc = 0; cc < ADD_CC; ++cc) acc[r][cc] = 0.f;
+
+  for (int j0 = 0; j0 < Ls; j0 += 64) {             // (uniform trip counts: every wave meets every barrier)
+    for (int jj = 0; jj < 16; ++jj) {
+      const int slot = wave * 16 + jj, j = j0 + slot;
+      float s[RB];
+#pragma unroll
+      for (int r = 0; r < RB; ++r) s[r] = -FLT_MAX;
+      if (j < Ls) {                                 // wave-uniform: the reductions run with all 64 lanes
+#pragma unroll
+        for (int r = 0; r < RB; ++r) s[r] = 0.f;
+        const size_t krow = (size_t)bk * bspm + (size_t)j * ldpm;
+        for (int c = lane * NV; c < M; c += 64 * NV) {
+          float pf[NV];
+          add_load<F32, NV>(pm, krow + c, pf);
+#pragma unroll
+          for (int e = 0; e < NV; ++e) {
+            const float vv = sv[c + e];
+#pragma unroll
+            for (int r = 0; r < RB; ++r) s[r] = fmaf(vv, tanhf(sq[r * M + c + e] + pf[e]), s[r]);
+          }
+        }
+        const float madd = kmask != nullptr ? (1.f - kmask[(size_t)bk * ldmask + j]) * -neg : 0.f;
+#pragma unroll
+        for (int r = 0; r < RB; ++r) s[r] = wave_sum(s[r]) + madd;
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) sw[r * 64 + slot] = s[r];
+      }
+    }
+    __syncthreads();
+    if (wave < RB) {                                // wave r owns row r of the block
+      const float s = sw[wave * 64 + lane];
+      const bool valid = j0 + lane < Ls;
+      const float m_old = st[wave];
+      const float m_new = fmaxf(m_old, wave_max(s));
+      const float pj = valid ? expf(s - m_new) : 0.f;
+      const float psum = wave_sum(pj);
+      const float alpha = expf(m_old - m_new);      // (the first tile: exp(-FLT_MAX - m) = 0 scales the empty sums)
+      const float l_old = st[RB + wave];
+      sw[wave * 64 + lane] = pj;
+      if (lane == 0) {
+        st[wave] = m_new;
+        st[RB + wave] = l_old * alpha + psum;
+        st[2 * RB + wave] = alpha;
+      }
+    }
+    __syncthreads();
+    const int jn = min(64, Ls - j0);
+#pragma unroll
+    for (int cc = 0; cc < ADD_CC; ++cc) {
+      const int c = cc * 256 + threadIdx.x;
+      if (c < M) {
+#pragma unroll
+        for (int r = 0; r < RB; ++r) acc[r][cc] *= st[2 * RB + r];
+        const size_t mcol = (size_t)bk * bsmem + c;
+        for (int jj = 0; jj < jn; ++jj) {
+          const float mf = add_load1<F32>(mem, mcol + (size_t)(j0 + jj) * ldmem);
+#pragma unroll
+          for (int r = 0; r < RB; ++r) acc[r][cc] = fmaf(sw[r * 64 + jj], mf, acc[r][cc]);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int r = 0; r < RB; ++r) {
+    if (r >= nrows) continue;
+    const float inv = 1.f / st[RB + r];
+    const size_t row = (size_t)(bk * kv_group + g0 + r);
+#pragma unroll
+    for (int cc = 0; cc < ADD_CC; ++cc) {
+      const int c = cc * 256 + threadIdx.x;
+      if (c < M) {
+        const float o = acc[r][cc] * inv;
+        ctx[row * ldo + c] = o;
+        if (ctx_copy != nullptr) {
+          if (F32) reinterpret_cast<float*>(ctx_copy)[row * ldc + c] = o;
+          else reinterpret_cast<bf16_t*>(ctx_copy)[row * ldc + c] = f2bf(o);
+        }
+      }
+    }
+  }
+}
+
+template <bool F32, int NV>
+static int add_attn_launch(const void* qa, int ldq, const void* pm, int ldpm, long bspm, const void* mem, int ldmem, long bsmem,
+                           const float* v, const float* kmask, int ldmask, float* ctx, int ldo, void* ctx_copy, int ldc, int R,
+                           int kv_group, int Ls, int M, float neg, hipStream_t stream) {
+  const int rb = kv_group > 1 ? ADD_RB : 1;
+  const size_t lds = ((size_t)rb * M + M + rb * 64 + 3 * rb) * sizeof(float);
+  const long per_mem = (kv_group + rb - 1) / rb;
+  const long blocks = (long)(R / kv_group) * per_mem;
+  if (blocks > 0x7fffffffL) return zk_set_error(-1, "zk_add_attn: %ld workgroups exceed the grid", blocks);
+  if (rb == 1)
+    hipLaunchKernelGGL((k_add_attn<F32, NV, 1>), dim3((unsigned)blocks), dim3(256), lds, stream, qa, ldq, pm, ldpm, bspm, mem,
+                       ldmem, bsmem, v, kmask, ldmask, ctx, ldo, ctx_copy, ldc, kv_group, Ls, M, neg, (int)per_mem);
+  else
+    hipLaunchKernelGGL((k_add_attn<F32, NV, ADD_RB>), dim3((unsigned)blocks), dim3(256), lds, stream, qa, ldq, pm, ldpm, bspm,
+                       mem, ldmem, bsmem, v, kmask, ldmask, ctx, ldo, ctx_copy, ldc, kv_group, Ls, M, neg, (int)per_mem);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+#define ADD_CHECK_COMMON(NAME)                                                                                              \
+  ZK_CHECK_ARG(qa != nullptr && pm != nullptr && mem != nullptr && v != nullptr && ctx != nullptr,                          \
+               NAME ": qa, pm, mem, v and ctx are required");                                                               \
+  ZK_CHECK_ARG(R >= 0 && kv_group >= 1 && R % kv_group == 0 && Ls >= 1 && M >= 1 && M <= 256 * ADD_CC,                      \
+               NAME ": bad shape (R=%d kv_group=%d Ls=%d M=%d; R must be a multiple of kv_group, M at most %d)", R,         \
+               kv_group, Ls, M, 256 * ADD_CC);                                                                              \
+  ZK_CHECK_ARG(kmask == nullptr || ldmask >= Ls, NAME ": mask rows of ldmask=%d elements are shorter than Ls=%d", ldmask,   \
+               Ls);                                                                                                         \
+  ZK_CHECK_ARG(ldq >= M && ldpm >= M && ldmem >= M && ldo >= M && (ctx_copy == nullptr || ldc >= M),                        \
+               NAME ": a leading dimension is smaller than M=%d (ldq=%d ldpm=%d ldmem=%d ldo=%d ldc=%d)", M, ldq, ldpm,     \
+               ldmem, ldo, ldc)
+
+// ---------------------------------------------------------------- row-local launches
+// out[r] = table[ids[r]] + bias, or zeros where EVERY id of the launch equals pad (models/rnnsearch.py:101-103); pad < 0:
+// no such rule (the encoder input, rnnsearch.py:28-29).  No sqrt(H) scale, no timing signal.
+template <bool F32>
+__global__ void __launch_bounds__(256) k_rnn_embed(const int* __restrict__ ids, int rows, const void* __restrict__ table,
+                                                   int V, const float* __restrict__ bias, void* __restrict__ out, int ldo, int E,
+                                                   int pad) {
+  int other = 0;
+  if (pad >= 0)
+    for (int i = threadIdx.x; i < rows; i += 256) other |= ids[i] != pad;
+  const bool zero = pad >= 0 && !__syncthreads_or(other);
+  const int r = blockIdx.x;
+  const int id = min(max(ids[r], 0), V - 1);
+  for (int c = threadIdx.x; c < E; c += 256) {
+    const float x = zero ? 0.f : add_load1<F32>(table, (size_t)id * E + c) + bias[c];
+    if (F32) reinterpret_cast<float*>(out)[(size_t)r * ldo + c] = x;
+    else reinterpret_cast<bf16_t*>(out)[(size_t)r * ldo + c] = f2bf(x);
+  }
+}
+
+// y = tanh(x + bias) for fp32 rows x (a GEMM's fp32 output); input row r goes to the output rows r rep .. r rep + rep - 1
+// (the beam tiling of decoder_initializer); out_f32 and / or out_copy (storage type)
+template <bool F32>
+__global__ void __launch_bounds__(256) k_rnn_bias_tanh(const float* __restrict__ x, int ldx, const float* __restrict__ bias,
+                                                       float* __restrict__ out_f32, int ldo, void* __restrict__ out_copy, int ldc,
+                                                       int cols, int rep) {
+  const int r = blockIdx.x;
+  for (int c = threadIdx.x; c < cols; c += 256) {
+    const float y = tanhf(x[(size_t)r * ldx + c] + (bias != nullptr ? bias[c] : 0.f));
+    for (int k = 0; k < rep; ++k) {
+      const size_t ro = (size_t)r * rep + k;
+      if (out_f32 != nullptr) out_f32[ro * ldo + c] = y;
+      if (out_copy != nullptr) {
+        if (F32) reinterpret_cast<float*>(out_copy)[ro * ldc + c] = y;
+        else reinterpret_cast<bf16_t*>(out_copy)[ro * ldc + c] = f2bf(y);
+      }
+    }
+  }
+}
+
+template <bool F32>
+static int rnn_embed_launch(const char* name, const int* ids, int rows, const void* table, int V, const float* bias, void* out,
+                            int ldo, int E, int pad, hipStream_t stream) {
+  if (!(ids != nullptr && table != nullptr && bias != nullptr && out != nullptr))
+    return zk_set_error(-1, "%s: ids, table, bias and out are required", name);
+  if (!(rows >= 0 && V >= 1 && E >= 1 && ldo >= E)) return zk_set_error(-1, "%s: bad shape (rows=%d V=%d E=%d ldo=%d)", name, rows, V, E, ldo);
+  if (rows == 0) return 0;
+  hipLaunchKernelGGL(k_rnn_embed<F32>, dim3((unsigned)rows), dim3(256), 0, stream, ids, rows, table, V, bias, out, ldo, E, pad);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+template <bool F32>
+static int rnn_bias_tanh_launch(const char* name, const float* x, int ldx, const float* bias, float* out_f32, int ldo,
+                                void* out_copy, int ldc, int rows, int cols, int rep, hipStream_t stream) {
+  if (!(x != nullptr && (out_f32 != nullptr || out_copy != nullptr))) return zk_set_error(-1, "%s: x and an output are required", name);
+  if (!(rows >= 0 && cols >= 1 && rep >= 1 && ldx >= cols && (out_f32 == nullptr || ldo >= cols) &&
+        (out_copy == nullptr || ldc >= cols)))
+    return zk_set_error(-1, "%s: bad shape (rows=%d cols=%d rep=%d ldx=%d ldo=%d ldc=%d)", name, rows, cols, rep, ldx, ldo, ldc);
+  if (rows == 0) return 0;
+  hipLaunchKernelGGL(k_rnn_bias_tanh<F32>, dim3((unsigned)rows), dim3(256), 0, stream, x, ldx, bias, out_f32, ldo, out_copy, ldc,
+                     cols, rep);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" {
+
+int zk_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const void* U, int ldu, const float* b,
+                    const void* p, int ldp, const float* mask, int ldm, float* out, int ldo, void* out_copy, int ldc, int R,
+                    int H, hipStream_t stream) {
+  ATR_CHECK_COMMON("zk_rnn_atr_step");
+  ZK_CHECK_ARG(H % 8 == 0 && H <= 4096 && ldu % 8 == 0 && (((uintptr_t)U) & 15) == 0,
+               "zk_rnn_atr_step: the bf16 form needs H a multiple of 8 and at most 4096 and 16-byte aligned rows of U (H=%d "
+               "ldu=%d); zk_f32_rnn_atr_step takes any H", H, ldu);
+  if (R == 0) return 0;
+  const int Kr = (H + 31) / 32 * 32;
+  const size_t lds = (size_t)ATR_BN * (Kr + 8) * sizeof(bf16_t);
+  const int vec_a = h_prev != nullptr && ldh % 4 == 0 && (((uintptr_t)h_prev) & 15) == 0;
+  hipLaunchKernelGGL(k_rnn_atr_step, dim3((unsigned)((H + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)), dim3(256),
+                     lds, stream, h_prev, ldh, n_prev, idx, reinterpret_cast<const bf16_t*>(U), ldu, b,
+                     reinterpret_cast<const bf16_t*>(p), ldp, mask, ldm, out, ldo, reinterpret_cast<bf16_t*>(out_copy), ldc, R, H,
+                     vec_a);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_f32_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const float* U, int ldu, const float* b,
+                        const float* p, int ldp, const float* mask, int ldm, float* out, int ldo, float* out_copy, int ldc,
+                        int R, int H, hipStream_t stream) {
+  ATR_CHECK_COMMON("zk_f32_rnn_atr_step");
+  ZK_CHECK_ARG(!rnn_rows_overlap(out_copy, ldc, R, h_prev, ldh, n_prev, H), "zk_f32_rnn_atr_step: out_copy overlaps h_prev");
+  if (R == 0) return 0;
+  hipLaunchKernelGGL(k_f32_rnn_atr_step, dim3((unsigned)((H + ATRF_BN - 1) / ATRF_BN), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
+                     dim3(256), 0, stream, h_prev, ldh, n_prev, idx, U, ldu, b, p, ldp, mask, ldm, out, ldo, out_copy, ldc, R, H);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_add_attn(const void* qa, int ldq, const void* pm, int ldpm, long bspm, const void* mem, int ldmem, long bsmem,
+                const float* v, const float* kmask, int ldmask, float* ctx, int ldo, void* ctx_copy, int ldc, int R,
+                int kv_group, int Ls, int M, float neg, hipStream_t stream) {
+  ADD_CHECK_COMMON("zk_add_attn");
+  ZK_CHECK_ARG(M % 8 == 0 && ldpm % 8 == 0 && bspm % 8 == 0 && (((uintptr_t)pm) & 15) == 0,
+               "zk_add_attn: the bf16 form reads the projected memory 16 bytes at a time: M, ldpm and bspm multiples of 8 and "
+               "an aligned pm (M=%d ldpm=%d bspm=%ld); zk_f32_add_attn takes any M", M, ldpm, bspm);
+  if (R == 0) return 0;
+  return add_attn_launch<false, 8>(qa, ldq, pm, ldpm, bspm, mem, ldmem, bsmem, v, kmask, ldmask, ctx, ldo, ctx_copy, ldc, R,
+                                   kv_group, Ls, M, neg, stream);
+}
+
+int zk_f32_add_attn(const float* qa, int ldq, const float* pm, int ldpm, long bspm, const float* mem, int ldmem, long bsmem,
+                    const float* v, const float* kmask, int ldmask, float* ctx, int ldo, float* ctx_copy, int ldc, int R,
+                    int kv_group, int Ls, int M, float neg, hipStream_t stream) {
+  ADD_CHECK_COMMON("zk_f32_add_attn");
+  if (R == 0) return 0;
+  const bool vec = M % 4 == 0 && ldpm % 4 == 0 && bspm % 4 == 0 && (((uintptr_t)pm) & 15) == 0;
+  if (vec)
+    return add_attn_launch<true, 4>(qa, ldq, pm, ldpm, bspm, mem, ldmem, bsmem, v, kmask, ldmask, ctx, ldo, ctx_copy, ldc, R,
+                                    kv_group, Ls, M, neg, stream);
+  return add_attn_launch<true, 1>(qa, ldq, pm, ldpm, bspm, mem, ldmem, bsmem, v, kmask, ldmask, ctx, ldo, ctx_copy, ldc, R,
+                                  kv_group, Ls, M, neg, stream);
+}
+
+int zk_rnn_embed(const int* ids, int rows, const void* table, int V, const float* bias, void* out, int ldo, int E, int pad,
+                 hipStream_t stream) {
+  return rnn_embed_launch<false>("zk_rnn_embed", ids, rows, table, V, bias, out, ldo, E, pad, stream);
+}
+
+int zk_f32_rnn_embed(const int* ids, int rows, const float* table, int V, const float* bias, float* out, int ldo, int E,
+                     int pad, hipStream_t stream) {
+  return rnn_embed_launch<true>("zk_f32_rnn_embed", ids, rows, table, V, bias, out, ldo, E, pad, stream);
+}
+
+int zk_rnn_bias_tanh(const float* x, int ldx, const float* bias, float* out_f32, int ldo, void* out_copy, int ldc, int rows,
+                     int cols, int rep, hipStream_t stream) {
+  return rnn_bias_tanh_launch<false>("zk_rnn_bias_tanh", x, ldx, bias, out_f32, ldo, out_copy, ldc, rows, cols, rep, stream);
+}
+
+int zk_f32_rnn_bias_tanh(const float* x, int ldx, const float* bias, float* out_f32, int ldo, float* out_copy, int ldc,
+                         int rows, int cols, int rep, hipStream_t stream) {
+  return rnn_bias_tanh_launch<true>("zk_f32_rnn_bias_tanh", x, ldx, bias, out_f32, ldo, out_copy, ldc, rows, cols, rep, stream);
+}
+
+}  // extern "C"

@@ -637,6 +637,41 @@ class Engine(object):
         name = "zk_f32_fixup_relu_shift" if h.t.dtype == torch.float32 else "zk_fixup_relu_shift"
         self.lib.call(name, h.ptr, h.ld, hip.ptr(offset), out.ptr, out.ld, h.rows, h.cols, self.stream)
 
+    # ---- rnnsearch (zk_rnn.hip); the bf16 or the fp32 form by the dtype of the storage-type operand
+    def rnn_atr_step(self, h_prev, U, b, p, out, out_copy=None, idx=None, mask=None):
+        """rnns/atr.py:32-60 + the carry of rnns/rnn.py:41-49, one time step of one cell: out = carry(mask,
+        ATR(h_prev[idx], p), h_prev[idx]).  h_prev: fp32 Mat [n_prev, H] or None (zero state); idx: int32 device tensor
+        [R] or None; U: Mat [H, H] and p: Mat [R, H] of the storage type; b: fp32 [H]; mask: fp32 Mat [R, 1] (ld = the
+        stride between rows) or None; out: fp32 Mat [R, H]; out_copy: storage-type Mat [R, H] or None."""
+        name = "zk_f32_rnn_atr_step" if p.t.dtype == torch.float32 else "zk_rnn_atr_step"
+        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
+        self.lib.call(name, *mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx), U.ptr, U.ld,
+                      b.data_ptr(), p.ptr, p.ld, *mp(mask), out.ptr, out.ld, *mp(out_copy), out.rows, out.cols, self.stream)
+
+    def add_attn(self, qa, pm, mem, v, kmask, ctx, ctx_copy, kv_group, Ls):
+        """func.py:107-161 for one decode step (zk_add_attn / zk_f32_add_attn): qa Mat [R, M]; pm, mem Mats [R / kv_group *
+        Ls, M] (projected memory, memory) of the storage type; v fp32 [M]; kmask fp32 [R / kv_group, Ls] or None; ctx fp32
+        Mat [R, M]; ctx_copy storage-type Mat or None."""
+        name = "zk_f32_add_attn" if pm.t.dtype == torch.float32 else "zk_add_attn"
+        self.lib.call(name, qa.ptr, qa.ld, pm.ptr, pm.ld, Ls * pm.ld, mem.ptr, mem.ld, Ls * mem.ld, v.data_ptr(),
+                      hip.ptr(kmask), Ls, ctx.ptr, ctx.ld, ctx_copy.ptr if ctx_copy is not None else None,
+                      ctx_copy.ld if ctx_copy is not None else 0, qa.rows, kv_group, Ls, qa.cols, float(zdtype.inf()),
+                      self.stream)
+
+    def rnn_embed(self, ids, rows, table, bias, out, pad=-1):
+        """out[r] = table[ids[r]] + bias (models/rnnsearch.py:28-29, 93-94); pad >= 0: zeros when every id is pad
+        (rnnsearch.py:101-103).  table: [V, E] tensor of out's dtype; out: Mat [rows, E]."""
+        name = "zk_f32_rnn_embed" if out.t.dtype == torch.float32 else "zk_rnn_embed"
+        self.lib.call(name, ids.data_ptr(), rows, table.data_ptr(), int(table.shape[0]), bias.data_ptr(), out.ptr, out.ld,
+                      out.cols, int(pad), self.stream)
+
+    def rnn_bias_tanh(self, x, bias, out_f32=None, out_copy=None, rep=1, f32=False):
+        """tanh(x + bias) of an fp32 Mat x; input row r -> output rows r rep .. r rep + rep - 1 of out_f32 (fp32 Mat) and /
+        or out_copy (Mat of the storage type: fp32 when f32)."""
+        name = "zk_f32_rnn_bias_tanh" if f32 else "zk_rnn_bias_tanh"
+        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
+        self.lib.call(name, x.ptr, x.ld, hip.ptr(bias), *mp(out_f32), *mp(out_copy), x.rows, x.cols, int(rep), self.stream)
+
     def attn_bwd(self, q, k, v, out, dout, lse, dq, dk, dv, B, nh, Lq, Lk, d, kmask=None, causal=False,
                  rpr_k=None, rpr_v=None, drpr_k=None, drpr_v=None, max_rel=0, drop_p=0.0, sid=0, impl=None,
                  defer_tables=None, oproj=None):

@@ -77,6 +77,9 @@ STEP_GRAPH_CACHE = 24        # shapes per core; least recently used goes first
 
 
 def _graph_pointers(state, book):
+    own = getattr(state, "graph_pointers", None)      # a state that is not a Transformer layer stack names its own
+    if own is not None:
+        return tuple(own()) + (tuple(book) if book is not None else ())
     core = state["_core"]
     e = core.eng
     ptrs = [state["pack_dev"].data_ptr(), state["out_dev"].data_ptr(), state["mask"].data_ptr(),
@@ -368,6 +371,12 @@ VARIANT_LIMITS = {
                    "(search_mode=dev re-runs the encoder and the whole prefix each step) is not built for it",
         member=(NotImplementedError, "ensemble member %d is a transformer_fixup: an untested member type (its step takes "
                                      "the launch-per-op path, the ensemble step is built from the fused launches)")),
+    "rnnsearch": dict(
+        cache_only="rnnsearch decodes with search_mode=cache only: search_mode=dev re-runs the encoder and the "
+                   "training-path decoder over the whole prefix each step, which is not built for it",
+        member=(NotImplementedError, "ensemble member %d is a rnnsearch: the ensemble step is built from the Transformer's "
+                                     "fused attention launches and shares per-layer caches between members; composing a "
+                                     "recurrent member is not built")),
 }
 
 

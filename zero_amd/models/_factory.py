@@ -64,8 +64,16 @@ def current_lane():
     return getattr(_LANE, "idx", 0)
 
 
+def _core_class(model_name):
+    if model_name == "rnnsearch":
+        from zero_amd.models._rnnsearch import RnnSearchCore
+        return RnnSearchCore
+    return TransformerCore
+
+
 def get_core(params, model_name, initializer=None):
-    """One TransformerCore per (scope, device, lane): AUTO_REUSE of transformer.py:222-226."""
+    """One core (TransformerCore, or the model's own class) per (scope, device, lane): AUTO_REUSE of
+    transformer.py:222-226."""
     dev = "cuda:%d" % torch.cuda.current_device() if torch.cuda.is_available() else "cpu"
     ln = current_lane()
     key = (params.scope_name or "model", model_name, dev) + ((ln,) if ln else ())
@@ -77,7 +85,7 @@ def get_core(params, model_name, initializer=None):
                 store = get_store(params, model_name, dev)
                 if isinstance(initializer, dict):
                     store.load(initializer)
-                core = TransformerCore(params, model_name, store, dev)
+                core = _core_class(model_name)(params, model_name, store, dev)
                 _CORES[key] = core
     else:
         core.hp = params

@@ -96,12 +96,52 @@ def _fixup_specs(params):
     return specs
 
 
+def _rnnsearch_specs(params):
+    """models/rnnsearch.py:16-133 + rnns/rnn.py + rnns/atr.py + func.py:107-161 in creation order (cell "atr",
+    layer_norm off).  An ATR cell `s` owns fetch_state_<s>/hide_x/W_0_0 (the input projection, no bias) and
+    cell_<s>/hide_h/{W_0_0, b_0} (the recurrent map); a cond_rnn creates both input projections in front of its scan and
+    the recurrent maps inside it.  M: the width of the memory (H for the context-aware encoder, else [forward, backward]).
+    Embeddings are plain tf.get_variable calls under the scope: the scope initialiser draws them ("embed_w": padded rows
+    like "embed"), and `bias` is ONE variable shared by both embedding lookups."""
+    H, E = params.hidden_size, params.embed_size
+    Vs, Vt = params.src_vocab.size(), params.tgt_vocab.size()
+    shared = params.shared_source_target_embedding
+    M = H if params.caencoder else 2 * H
+
+    def fetch(pre, s, width):
+        return [(pre + "fetch_state_%s/hide_x/W_0_0" % s, (width, H), "w")]
+
+    def cell(pre, s):
+        return [(pre + "cell_%s/hide_h/W_0_0" % s, (H, H), "w"), (pre + "cell_%s/hide_h/b_0" % s, (H,), "zeros")]
+    v = [("embedding" if shared else "src_embedding", (Vs, E), "embed_w"), ("bias", (E,), "w")]
+    v += fetch("encoder/forward/", "atr", E) + cell("encoder/forward/", "atr")
+    b = "encoder/backward/"
+    if params.caencoder:
+        v += fetch(b, "atr_lower", E) + fetch(b, "atr_higher", H) + cell(b, "atr_lower") + cell(b, "atr_higher")
+    else:
+        v += fetch(b, "atr", E) + cell(b, "atr")
+    v += [("decoder_initializer/atr_init/W_0_0", (M, H), "w"), ("decoder_initializer/atr_init/b_0", (H,), "zeros")]
+    if not shared:
+        v.append(("tgt_embedding", (Vt, E), "embed_w"))
+    d = "decoder/"
+    v += fetch(d, "atr_lower", E) + [(d + "context_att/W_0_0", (M, M), "w")] + cell(d, "atr_lower")
+    v += [(d + "attention/feed_query/W_0_0", (H, M), "w"), (d + "attention/feed_query/b_0", (M,), "zeros"),
+          (d + "attention/feed_logits/W_0_0", (M, 1), "w"), (d + "attention/feed_logits/b_0", (1,), "zeros")]
+    v += fetch(d, "atr_higher", M) + cell(d, "atr_higher")
+    v += [("pre_logits/W_0_0", (H + M + E, E), "w"), ("pre_logits/b_0", (E,), "zeros")]
+    if not shared and not params.shared_target_softmax_embedding:
+        v.append(("softmax_embedding", (Vt, E), "embed_w"))
+    return [(n, s, k, None) for n, s, k in v]
+
+
 def variable_specs(params, model_name):
     """[(name, logical_shape, kind, layer)] in the reference's creation order
     (transformer.py:16-33,88-102,184-192; transformer_aan.py:165-192;
     transformer_rpr.py:54-55,144-146,167-169; transformer_fuse.py:131-160; transformer_l0drop.py:250: the
     source_pruning pair is created by the decoder after its embedding lookup and before its first layer;
     transformer_rela.py:48,134,154 + modules/rela.py:34-84: `transformer` plus post/{scale,gate} per attention scope)."""
+    if model_name == "rnnsearch":       # (the one family whose embeddings are not H wide: before the H == E test)
+        return _rnnsearch_specs(params)
     H, E, F = params.hidden_size, params.embed_size, params.filter_size
     if H != E:
         raise ValueError("hidden_size must equal embed_size for the Transformer models "
@@ -179,6 +219,8 @@ def initial_values(params, model_name, seed):
     for name, shape, kind, layer in variable_specs(params, model_name):
         if kind in ("embed", "embed_zeros"):
             v = rng.normal(0.0, params.hidden_size ** -0.5, size=shape)
+        elif kind == "embed_w":           # rnnsearch.py:24-25, 89-90, 130-131: the scope initialiser
+            v = _scope_init(rng, shape, params.initializer, params.initializer_gain)
         elif kind == "zeros":
             v = np.zeros(shape)
         elif kind == "ones":
@@ -203,7 +245,7 @@ class VariableStore(object):
         off = 0
         for name, shape, kind, _ in self.specs:
             pshape = tuple(shape)
-            if kind in ("embed", "embed_zeros") or name.endswith("/embeddings"):
+            if kind in ("embed", "embed_zeros", "embed_w") or name.endswith("/embeddings"):
                 # (relative-position tables too: their zero rows make them GEMM operands with an 8-aligned
                 # contraction length as they are -- no padded copy per attention call)
                 pshape = ((shape[0] + 7) // 8 * 8, shape[1])
