@@ -22,8 +22,10 @@ B, nh, L, d = 64, 8, 64, 64
 H = nh * d
 T = B * L
 bf = lambda *s: (torch.randn(*s, device="cuda") * 0.3).to(torch.bfloat16)
-MARKS = {0: "start", 1: "prologue loads issued (oproj: chunk loop starts)", 2: "oproj product done", 3: "operand tiles stored",
-         4: "first barrier passed", 5: "phase 1 (P, dS) computed", 6: "barrier", 7: "dS / P^T (+ transposed operands) stored, barrier",
+# 1: oproj only (mask words, lse, tiles and the whole first chunk issued); 6: rpr only (the plain / oproj kernels write dS^T and
+# P^T into tiles nobody reads in phase 1, without a barrier in front); 7 in the rpr kernel: + dS and the transposed operands
+MARKS = {0: "start", 1: "every load of the prologue and the first chunk issued", 2: "oproj product done", 3: "operand tiles stored",
+         4: "first barrier passed", 5: "phase 1 (P, dS) computed", 6: "barrier", 7: "dS^T / P^T stored, barrier",
          8: "dQ / dK / dV products", 11: "bucket sums", 12: "table products", 9: "outputs staged, barrier", 10: "stores issued"}
 ORDER = [0, 1, 2, 3, 4, 5, 6, 7, 8, 11, 12, 9, 10]
 

@@ -368,7 +368,7 @@ __device__ __forceinline__ void proj_heads_tile(unsigned char* smem, const bf16_
   // ---- epilogue through the LDS (the ring is dead): PRO fp32 tiles, then every thread stores 16-byte row pieces
   // [straight from the registers -- 48 two-byte stores per lane -- the launch was 5 us LONGER than with three gemm_tile calls]
   // and leaves the SAME bf16 values where the attention tile of this workgroup expects its operands (tQ / tK: [row][ALD];
-  // tVt: [physical channel][key] as store_trans writes it; rows >= M zero as load_direct / load_trans return them): the
+  // tVt: [physical channel][key] as store_trans writes it; rows >= M zero as store_direct / store_trans leave them): the
   // attention starts from the LDS -- no store acknowledgement, no load round trip between the projection and the attention
   // (2.3 us of the launch, profiles/r06_attn_out_ln_timeline_*).  The global copies (the backward reads them) are stored
   // by the CALLER from pk[] (this thread's row m0 + tid / 8, columns p nslab + n0 + (tid % 8) 8 .. +7; rows >= M: none)

@@ -221,7 +221,8 @@ __device__ __forceinline__ void stage_trans(bf16_t* dst, const bf16_t* src, int 
 __device__ __forceinline__ int chan_of_phys(int q) { return (q & 7) * 8 + (q >> 3); }
 // The same staging in two halves -- all global loads of a prologue are issued before the first LDS store, so
 // their latencies overlap instead of adding up (one stage_* call after another measured ~1500 cycles each).
-// Branch-free: rows past the end are clamped for the address and zeroed by a select.
+// Branch-free, and nothing between two loads touches a loaded VALUE (a select on one makes the compiler wait for it in
+// the middle of the queue): rows past the end are clamped for the ADDRESS here and zeroed at the LDS store.
 struct DirectRegs { uint4 v[2]; };
 template <bool FRESH = false>
 __device__ __forceinline__ void load_direct(DirectRegs& R, const bf16_t* src, int ld, int row0, int nrows, int tid) {
@@ -229,11 +230,26 @@ __device__ __forceinline__ void load_direct(DirectRegs& R, const bf16_t* src, in
   for (int it = 0; it < 2; ++it) {
     const int t = tid + it * 256;
     const int r = row0 + (t >> 3), c = (t & 7) * 8;
-    const uint4 v = zk_ld16<FRESH>(src + (size_t)min(r, nrows - 1) * ld + c);
-    R.v[it] = r < nrows ? v : make_uint4(0u, 0u, 0u, 0u);
+    R.v[it] = zk_ld16<FRESH>(src + (size_t)min(r, nrows - 1) * ld + c);
   }
 }
-__device__ __forceinline__ void store_direct(bf16_t* dst, const DirectRegs& R, int tid) {
+// all 64 rows exist (the W_o slabs): no clamp
+__device__ __forceinline__ void load_direct64(DirectRegs& R, const bf16_t* src, int ld, int tid) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int t = tid + it * 256;
+    R.v[it] = zk_ld16<false>(src + (size_t)(t >> 3) * ld + (t & 7) * 8);
+  }
+}
+// tile rows >= nlive (= the matrix's rows - row0 of the load) are stored as zeros
+__device__ __forceinline__ void store_direct(bf16_t* dst, const DirectRegs& R, int tid, int nlive) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int t = tid + it * 256;
+    *reinterpret_cast<uint4*>(dst + (t >> 3) * ALD + (t & 7) * 8) = (t >> 3) < nlive ? R.v[it] : make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+__device__ __forceinline__ void store_direct64(bf16_t* dst, const DirectRegs& R, int tid) {
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int t = tid + it * 256;
@@ -247,19 +263,57 @@ __device__ __forceinline__ void load_trans(TransRegs& R, const bf16_t* src, int 
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int r = row0 + rq * 4 + u;
-    const uint4 v = zk_ld16<FRESH>(src + (size_t)min(r, nrows - 1) * ld + dc * 8);
-    R.v[u] = r < nrows ? v : make_uint4(0u, 0u, 0u, 0u);
+    R.v[u] = zk_ld16<FRESH>(src + (size_t)min(r, nrows - 1) * ld + dc * 8);
   }
 }
-__device__ __forceinline__ void store_trans(bf16_t* dst, const TransRegs& R, int t128) {
+// tile rows (columns of dst) >= nlive are stored as zeros
+__device__ __forceinline__ void store_trans(bf16_t* dst, const TransRegs& R, int t128, int nlive) {
   const int dc = t128 & 7, rq = t128 >> 3;
+  uint4 v[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) v[u] = rq * 4 + u < nlive ? R.v[u] : make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     uint2 o;
-    o.x = half_of4(R.v[0], i) | (half_of4(R.v[1], i) << 16);
-    o.y = half_of4(R.v[2], i) | (half_of4(R.v[3], i) << 16);
+    o.x = half_of4(v[0], i) | (half_of4(v[1], i) << 16);
+    o.y = half_of4(v[2], i) | (half_of4(v[3], i) << 16);
     *reinterpret_cast<uint2*>(dst + (i * 8 + dc) * ALD + rq * 4) = o;
   }
+}
+// Transposed fragment of a row-major [k][ALD] tile -- what frag() would return from the tile's transpose: for lane
+// (n = lane & 15, g = lane >> 4) the 8 elements t[kk*32 + 8g + e][c0 + n], e = 0 .. 7, as two ds_read_b64_tr_b16 of a
+// 4 (k) x 16 (columns) block each (zk_gemm2_dev.h load_frag<R, true>, semantics probed by zk_probe_tr16): lane 4q + p of a
+// 16-lane group supplies the address of the block's row q, columns 4p .. 4p+3, and receives its own column of the 4 rows.
+// EXEC must be all ones (never under a lane-dependent branch) and every lane's address in bounds and 8-byte aligned: the
+// tile is [64][ALD] with 144-byte rows, the highest address read is row 63, columns 60 .. 63.
+// Banks ((byte address / 4) % 64 per 32-lane half): the half's 8 rows 8g + q start at dword 36 (8g + q) -> banks
+// 0, 36, 8, 44 | 32, 4, 40, 12, eight consecutive banks each: no bank is hit more than twice (2-way, like the row reads).
+typedef short attn_v4s_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint4 frag_tr(const bf16_t* t, int c0, int kk, int lane) {
+  const int p = lane & 15;
+  const bf16_t* a = t + (kk * 32 + (lane >> 4) * 8 + (p >> 2)) * ALD + c0 + (p & 3) * 4;
+  const attn_v4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_v4s_t*)a);
+  const attn_v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) attn_v4s_t*)(a + 4 * ALD));
+  typedef short attn_v8s_t __attribute__((ext_vector_type(8)));
+  const attn_v8s_t both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(uint4, both);
+}
+// The key-mask words of the 16 key columns a lane owns in each of N key tiles (index clamped), loaded FIRST in a prologue
+// (four bytes each: every later wait covers them) and turned into the additive bias by kmask_bias behind the prologue's
+// last load.  Branch-free -- a load under `if (kmask != nullptr)` made the compiler wait for it at the end of the branch:
+// without a mask the lanes read one word of q, which kmask_bias ignores.
+template <int N>
+__device__ __forceinline__ void kmask_load(float (&m)[N], const AttnArgs& a, int bk, int lane) {
+  const bool has = a.kmask != nullptr;
+  const float* row = has ? a.kmask + (size_t)bk * a.ldmask : reinterpret_cast<const float*>(a.q);
+#pragma unroll
+  for (int t = 0; t < N; ++t) m[t] = row[has ? min(t * 16 + (lane & 15), a.Lk - 1) : 0];
+}
+template <int N>
+__device__ __forceinline__ void kmask_bias(float (&m)[N], const AttnArgs& a) {
+  const bool has = a.kmask != nullptr;
+#pragma unroll
+  for (int t = 0; t < N; ++t) m[t] = (has && m[t] == 0.f) ? -a.mask_inf : 0.f;
 }
 // [64 rows][64 channels] bf16 tile in LDS (row stride ALD) -> global rows [0, nrows), 16 bytes per thread and store
 __device__ __forceinline__ void store_tile_rows(const bf16_t* tile, bf16_t* dst, size_t ld, int nrows, int tid) {
@@ -322,9 +376,12 @@ __device__ __forceinline__ void attn_fwd_tile(unsigned char* smem, const AttnArg
 
   // the loads that do not depend on anything computed here are issued together: Q, the first K tile, the first
   // V tile (kept in registers until P is ready) and the key mask -- one memory round trip instead of four
+  // (the mask words first, compared behind the last load: nothing in between waits for a loaded value)
   DirectRegs rQ, rK;
   [[maybe_unused]] DirectRegs rRk;
   TransRegs rVt;
+  float kbias[NKT * 4];
+  kmask_load(kbias, a, b / a.kv_group, lane);
   if (PRE == 0) load_direct<FRESH>(rQ, qb, a.ldq, i0, a.Lq, tid);
   if (PRE != 3) {
     load_direct<FRESH>(rK, kb, a.ldk, 0, a.Lk, tid);
@@ -336,18 +393,13 @@ __device__ __forceinline__ void attn_fwd_tile(unsigned char* smem, const AttnArg
     load_direct(rRk, a.rpr_k, AD, 0, nrel, tid);
     if (tid >= 128) load_trans(rVt, a.rpr_v, AD, 0, nrel, tid - 128);
   }
-  float kbias[NKT * 4];
-#pragma unroll
-  for (int t = 0; t < NKT * 4; ++t) {
-    const int j = t * 16 + (lane & 15);
-    kbias[t] = (a.kmask != nullptr && a.kmask[(size_t)(b / a.kv_group) * a.ldmask + min(j, a.Lk - 1)] == 0.f) ? -a.mask_inf : 0.f;
-  }
-  if (PRE == 0) store_direct(sQ, rQ, tid);
-  if (PRE != 3) store_direct(sK, rK, tid);
+  if (PRE == 0) store_direct(sQ, rQ, tid, a.Lq - i0);
+  if (PRE != 3) store_direct(sK, rK, tid, a.Lk);
   if (RPR) {
-    store_direct(sRk, rRk, tid);                          // [r][channel], rows >= nrel zero
-    if (tid >= 128) store_trans(sRvT, rVt, tid - 128);    // [physical channel][r]
+    store_direct(sRk, rRk, tid, nrel);                          // [r][channel], rows >= nrel zero
+    if (tid >= 128) store_trans(sRvT, rVt, tid - 128, nrel);    // [physical channel][r]
   }
+  kmask_bias(kbias, a);
   f32x4_t S[NKT * 4];
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt) {
@@ -474,7 +526,7 @@ __device__ __forceinline__ void attn_fwd_tile(unsigned char* smem, const AttnArg
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt) {
     __syncthreads();   // sK readers done / sP complete
-    if (kt == 0) { if (PRE != 3 && tid < 128) store_trans(sK, rVt, tid); }
+    if (kt == 0) { if (PRE != 3 && tid < 128) store_trans(sK, rVt, tid, a.Lk); }
     else stage_trans<FRESH>(sK, vb, a.ldv, kt * 64, a.Lk, tid);
     __syncthreads();
     const bf16_t* sVt = PRE == 3 ? vt_pre : sK;
@@ -512,20 +564,22 @@ __device__ __forceinline__ void attn_fwd_tile(unsigned char* smem, const AttnArg
 // shapes of the north star (L = 64) a whole (batch, head) problem is one 64x64 tile, so one
 // workgroup computes P and dS once (wave w owns query rows 16w..16w+15) and all three gradients
 // follow from LDS: dQ = dS K, dK = dS^T Q, dV = P^T dO.  The operand tiles of the first phase are
-// dead by then and their LDS is reused for dS, P^T and dS^T (7 tiles = 64.5 KB -> 2 workgroups/CU).
+// stay where they are -- dQ, dK and dV read K, Q and dO by columns with the transposing LDS read -- next to dS^T and P^T
+// (7 tiles = 64.5 KB -> 2 workgroups/CU: four operands, dS^T, P^T and one more slab buffer of the OPROJ prologue).
 #define ATTN_BWD64_LDS_BYTES (7 * TQ * ALD * 2 + TQ * 4)
 // RPR: the relative-position terms of modules/rpr.py:10-75 inside the tile (tables in LDS): G = Q.Rk^T and Gd = dO.Rv^T
 // by MFMA, gathered into the scores / dP; the bucket sums of dS and P stay in LDS; dQ += dsb.Rk; and the table
 // gradients dRk = dsb^T Q, dRv = pb^T dO of this (sentence, head) go to `rpr_part` (fp32 [B*nh][2][64][64], summed by
 // the caller) -- instead of four grouped-GEMM launches and two reductions around the kernel.  Six more bf16 tiles and
 // two fp32 tiles: one workgroup per CU.
-#define ATTN_BWD64_RPR_LDS_BYTES (ATTN_BWD64_LDS_BYTES + 6 * TQ * ALD * 2 + 2 * TQ * GLD * 4)
+#define ATTN_BWD64_RPR_LDS_BYTES (ATTN_BWD64_LDS_BYTES + 5 * TQ * ALD * 2 + 2 * TQ * GLD * 4)
 // OPROJ: the gradient of the attention output is not read but COMPUTED here from the gradient of the output projection's
 // result: dO_h = dY . W_o[h*64 .. h*64+63, :]^T  (dY [rows, n], W_o [H, n] row-major, n = op.n a multiple of 128) -- the
 // 64 x 64 x n product of this (sentence, head) and nothing more, so the dgrad GEMM launch of o_map (and the dO matrix in HBM)
 // disappears.  W_o's 64 rows go through LDS in slabs of 128 columns (two of the tiles that are idle until the prologue ends,
 // double-buffered); the dY fragments of a wave's 16 rows come straight from global memory (no other wave needs them).
 struct AttnOProj { const bf16_t* dy; int lddy; const bf16_t* w; int ldw; int n; };
+template <int V> struct zk_int_c { static constexpr int value = V; };
 template <bool RPR = false, bool OPROJ = false>
 __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const AttnArgs& a, const bf16_t* __restrict__ o, int ldo,
                                                       const bf16_t* __restrict__ dout, int lddo,
@@ -535,18 +589,21 @@ __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const
                                                       bf16_t* __restrict__ dv, int lddv, int h, int b,
                                                       float* __restrict__ rpr_part = nullptr,
                                                       const AttnOProj op = AttnOProj()) {
-  bf16_t* sQ = reinterpret_cast<bf16_t*>(smem);      // phase 2: dS   [query][key]
-  bf16_t* sK = sQ + TQ * ALD;                          // phase 2: P^T  [key][query]
-  bf16_t* sV = sK + TQ * ALD;                          // phase 2: dS^T [key][query]
+  // ONE row-major image per operand: S and dP read Q, K, V, dO by rows (frag), dQ, dK and dV read K, Q and dO by columns
+  // (frag_tr, the transposing LDS read) -- no transposed copies.  Tiles 4 .. 6 hold the W_o slabs of the OPROJ prologue
+  // (with tile 3), then dS^T and P^T (written while other waves still read the operands: no barrier in front), then --
+  // with the operands dead -- the staged outputs.
+  bf16_t* sQ = reinterpret_cast<bf16_t*>(smem);
+  bf16_t* sK = sQ + TQ * ALD;
+  bf16_t* sV = sK + TQ * ALD;
   bf16_t* sdO = sV + TQ * ALD;
-  bf16_t* sKt = sdO + TQ * ALD;
-  bf16_t* sQt = sKt + TQ * ALD;
-  bf16_t* sdOt = sQt + TQ * ALD;
-  float* sL = reinterpret_cast<float*>(sdOt + TQ * ALD);
+  bf16_t* sdSt = sdO + TQ * ALD;                       // phase 2: dS^T [key][query]
+  bf16_t* sPt = sdSt + TQ * ALD;                       // phase 2: P^T  [key][query]
+  bf16_t* sT6 = sPt + TQ * ALD;
+  float* sL = reinterpret_cast<float*>(sT6 + TQ * ALD);
   [[maybe_unused]] bf16_t* sRk = reinterpret_cast<bf16_t*>(smem + ATTN_BWD64_LDS_BYTES);   // key table   [r][channel]
   [[maybe_unused]] bf16_t* sRv = sRk + TQ * ALD;                                            // value table [r][channel]
-  [[maybe_unused]] bf16_t* sRkT = sRv + TQ * ALD;                                           // key table   [phys channel][r]
-  [[maybe_unused]] bf16_t* sSB = sRkT + TQ * ALD;                                           // bucket sums of dS  [query][r]
+  [[maybe_unused]] bf16_t* sSB = sRv + TQ * ALD;                                               // bucket sums of dS  [query][r]
   [[maybe_unused]] bf16_t* sSBt = sSB + TQ * ALD;                                           //                    [r][query]
   [[maybe_unused]] bf16_t* sPBt = sSBt + TQ * ALD;                                          // bucket sums of P   [r][query]
   [[maybe_unused]] float* sG = reinterpret_cast<float*>(sPBt + TQ * ALD);                   // Q.Rk^T  [query][GLD]
@@ -559,128 +616,108 @@ __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const
   const bf16_t* dob = dout + (size_t)b * a.Lq * lddo + h * AD;
   const uint64_t seed = a.thr ? *a.seed : 0;
 
-  // every global load of the prologue first (tiles, the O / dO rows of D_i, lse, the key mask), then the LDS stores
+  // Every global load of the prologue is issued before anything waits for a loaded value: lse and the key-mask words
+  // first (tiny, covered by every later wait; compared behind the chunk loop), then the tiles, then (OPROJ) the first
+  // chunk.  No load sits under a lane-dependent branch and no select touches a loaded value in between: rows past the
+  // end are clamped for the address and zeroed at the LDS store.
+  // D_i = sum_j P_ij dP_ij is taken from the P and dP this workgroup computes anyway (whole rows live in one tile),
+  // not from rowsum(dO o O) over the stored bf16 O: no O / dO row loads, and sum_j dS_ij = 0 holds to fp32 rounding
+  // (with the bf16 O the rows of dS kept a common offset ~2^-9 |dO.O| that leaked mean(K) into dQ -- 30 % of the
+  // tiny q_map / k_map gradients of the 12-layer-encoder configuration, tests/test_gpu_fullsize.py)
   ZK_AT(0);
+  const int dr = tid >> 2, dpart = tid & 3;
+  const float lse_r = lse[((size_t)b * a.nh + h) * a.Lq + min(dr, a.Lq - 1)];
+  float kbias4[4];
+  kmask_load(kbias4, a, b, lane);
   DirectRegs rQ, rdO, rK, rV;
-  TransRegs t0, t1;
   load_direct(rQ, qb, a.ldq, 0, a.Lq, tid);
   if (!OPROJ) load_direct(rdO, dob, lddo, 0, a.Lq, tid);
   load_direct(rK, kb, a.ldk, 0, a.Lk, tid);
   load_direct(rV, vb, a.ldv, 0, a.Lk, tid);
-  if (tid < 128) {
-    load_trans(t0, kb, a.ldk, 0, a.Lk, tid);
-  } else {
-    load_trans(t0, qb, a.ldq, 0, a.Lq, tid - 128);
-    if (!OPROJ) load_trans(t1, dob, lddo, 0, a.Lq, tid - 128);
-  }
   // OPROJ: dO rows 16w .. 16w+15 of this head = dY rows x W_o[h*64 .., :]^T in slabs of 128 columns.  The loads of the first
-  // 512-column chunk are issued HERE, behind the tile loads and in front of everything that waits for a loaded value (the
-  // key-mask compare below waits for the whole queue: with the chunk issued behind it the product started one memory
-  // round trip late, ATTNTRACE).  Q, K, V go to their tiles before the first slab (their registers are needed); the four
-  // tiles of the second phase (dO, K^T, Q^T, dO^T) are idle until the product is done: slab s uses tiles 3 + 2(s&1),
-  // 4 + 2(s&1), one barrier per slab.
+  // 512-column chunk follow the tile loads at once.  Q, K, V go to their tiles before the first slab (their registers
+  // are needed); tiles 3 .. 6 are idle until the product is done: slab s uses tiles 3 + 2(s&1), 4 + 2(s&1), one barrier
+  // per slab.
   [[maybe_unused]] f32x4_t dOa[4];
-  [[maybe_unused]] DirectRegs wr[8];
-  [[maybe_unused]] uint4 av[16];
   [[maybe_unused]] const bf16_t* wrow = OPROJ ? op.w + (size_t)h * AD * op.ldw : nullptr;
   [[maybe_unused]] const bf16_t* ap =
       OPROJ ? op.dy + ((size_t)b * a.Lq + min(w * 16 + (lane & 15), a.Lq - 1)) * op.lddy + (lane >> 4) * 8 : nullptr;
-  auto oproj_issue = [&](int c0) {
-    const int nsl = min(4, (op.n - c0) >> 7);
+  // One chunk of NSL slabs (512 columns, less at the end of a row): EVERY load of the chunk in flight before the first slab
+  // is multiplied (one slab of prefetch distance measured +7.4 us per launch: each slab then waits out most of a cold
+  // L2 / HBM latency).  NSL and FIRST are compile-time constants so that the loads and their uses are one straight line:
+  // the counted wait in front of slab s then covers the tiles and slabs 0 .. s only (with a runtime slab count the
+  // compiler's wait in front of the Q store assumed the shortest chunk and waited for all but five loads of a full one).
+  auto oproj_chunk = [&](int c0, auto nsl_c, auto first_c) {
+    constexpr int NSL = decltype(nsl_c)::value;
+    DirectRegs wr[2 * NSL];
+    uint4 av[4 * NSL];
 #pragma unroll
-    for (int sl = 0; sl < 4; ++sl) {
-      if (sl < nsl) {
-        load_direct(wr[2 * sl], wrow + c0 + sl * 128, op.ldw, 0, AD, tid);
-        load_direct(wr[2 * sl + 1], wrow + c0 + sl * 128 + 64, op.ldw, 0, AD, tid);
+    for (int sl = 0; sl < NSL; ++sl) {
+      load_direct64(wr[2 * sl], wrow + c0 + sl * 128, op.ldw, tid);
+      load_direct64(wr[2 * sl + 1], wrow + c0 + sl * 128 + 64, op.ldw, tid);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) av[4 * sl + u] = zk_ld16<false>(ap + c0 + sl * 128 + u * 32);
+      for (int u = 0; u < 4; ++u) av[4 * sl + u] = zk_ld16<false>(ap + c0 + sl * 128 + u * 32);
+    }
+    if (decltype(first_c)::value) {
+      ZK_AT(1);
+      store_direct(sQ, rQ, tid, a.Lq);
+      store_direct(sK, rK, tid, a.Lk);
+      store_direct(sV, rV, tid, a.Lk);
+    }
+#pragma unroll
+    for (int sl = 0; sl < NSL; ++sl) {
+      bf16_t* w0 = sdO + (sl & 1) * 2 * TQ * ALD;
+      bf16_t* w1 = w0 + TQ * ALD;
+      store_direct64(w0, wr[2 * sl], tid);
+      store_direct64(w1, wr[2 * sl + 1], tid);
+      __syncthreads();
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) {
+        dOa[nb] = mfma16(av[4 * sl + 0], frag(w0, nb * 16, 0, lane), dOa[nb]);
+        dOa[nb] = mfma16(av[4 * sl + 1], frag(w0, nb * 16, 1, lane), dOa[nb]);
+        dOa[nb] = mfma16(av[4 * sl + 2], frag(w1, nb * 16, 0, lane), dOa[nb]);
+        dOa[nb] = mfma16(av[4 * sl + 3], frag(w1, nb * 16, 1, lane), dOa[nb]);
       }
+    }
+  };
+  auto oproj_dispatch = [&](int c0, auto first_c) {
+    switch (min(4, (op.n - c0) >> 7)) {
+      case 4: oproj_chunk(c0, zk_int_c<4>(), first_c); break;
+      case 3: oproj_chunk(c0, zk_int_c<3>(), first_c); break;
+      case 2: oproj_chunk(c0, zk_int_c<2>(), first_c); break;
+      default: oproj_chunk(c0, zk_int_c<1>(), first_c); break;
     }
   };
   if (OPROJ) {
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) dOa[nb] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    oproj_issue(0);
-  }
-  // D_i = sum_j P_ij dP_ij is taken from the P and dP this workgroup computes anyway (whole rows live in one tile),
-  // not from rowsum(dO o O) over the stored bf16 O: no O / dO row loads, and sum_j dS_ij = 0 holds to fp32 rounding
-  // (with the bf16 O the rows of dS kept a common offset ~2^-9 |dO.O| that leaked mean(K) into dQ -- 30 % of the
-  // tiny q_map / k_map gradients of the 12-layer-encoder configuration, tests/test_gpu_fullsize.py)
-  const int dr = tid >> 2, dpart = tid & 3;
-  const int drc = min(dr, a.Lq - 1);
-  const float lse_r = lse[((size_t)b * a.nh + h) * a.Lq + drc];
-  float kbias4[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    const int j = nt * 16 + (lane & 15);
-    kbias4[nt] = (a.kmask != nullptr && a.kmask[(size_t)b * a.ldmask + min(j, a.Lk - 1)] == 0.f) ? -a.mask_inf : 0.f;
-  }
-  if (OPROJ) {
-    ZK_AT(1);
-    // chunks of 512 columns with EVERY load of the chunk in flight before the first slab is multiplied (one slab of
-    // prefetch distance measured +7.4 us per launch: each slab then waits out most of a cold L2 / HBM latency)
-    for (int c0 = 0; c0 < op.n; c0 += 512) {
-      const int nsl = min(4, (op.n - c0) >> 7);
-      if (c0 > 0) oproj_issue(c0);
-      else {
-        store_direct(sQ, rQ, tid);
-        store_direct(sK, rK, tid);
-        store_direct(sV, rV, tid);
-      }
-#pragma unroll
-      for (int sl = 0; sl < 4; ++sl) {
-        if (sl < nsl) {
-          bf16_t* w0 = sdO + (sl & 1) * 2 * TQ * ALD;
-          bf16_t* w1 = w0 + TQ * ALD;
-          store_direct(w0, wr[2 * sl], tid);
-          store_direct(w1, wr[2 * sl + 1], tid);
-          __syncthreads();
-#pragma unroll
-          for (int nb = 0; nb < 4; ++nb) {
-            dOa[nb] = mfma16(av[4 * sl + 0], frag(w0, nb * 16, 0, lane), dOa[nb]);
-            dOa[nb] = mfma16(av[4 * sl + 1], frag(w0, nb * 16, 1, lane), dOa[nb]);
-            dOa[nb] = mfma16(av[4 * sl + 2], frag(w1, nb * 16, 0, lane), dOa[nb]);
-            dOa[nb] = mfma16(av[4 * sl + 3], frag(w1, nb * 16, 1, lane), dOa[nb]);
-          }
-        }
-      }
-    }
+    oproj_dispatch(0, zk_int_c<1>());
+    for (int c0 = 512; c0 < op.n; c0 += 512) oproj_dispatch(c0, zk_int_c<0>());
     ZK_AT(2);
-    __syncthreads();                     // the slabs are dead: the transposed tiles and dO may land
+    __syncthreads();                     // the slabs are dead: dO may land
   } else {
-    store_direct(sQ, rQ, tid);
-    store_direct(sdO, rdO, tid);
-    store_direct(sK, rK, tid);
-    store_direct(sV, rV, tid);
-  }
-  if (tid < 128) {
-    store_trans(sKt, t0, tid);
-  } else {
-    store_trans(sQt, t0, tid - 128);
-    if (!OPROJ) store_trans(sdOt, t1, tid - 128);
+    store_direct(sQ, rQ, tid, a.Lq);
+    store_direct(sdO, rdO, tid, a.Lq);
+    store_direct(sK, rK, tid, a.Lk);
+    store_direct(sV, rV, tid, a.Lk);
   }
   if (OPROJ) {
-    // dO (rounded to bf16 like the GEMM's output was) as [query][channel] and [phys channel][query]; rows >= Lq are 0
+    // dO (rounded to bf16 like the GEMM's output was) as [query][channel]; rows >= Lq are 0
     const int r0 = w * 16 + (lane >> 4) * 4;
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
       const int c = nb * 16 + (lane & 15);
-      uint32_t hv[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        hv[r] = (r0 + r < a.Lq) ? (uint32_t)f2bf(dOa[nb][r]) : 0u;
-        sdO[(r0 + r) * ALD + c] = (bf16_t)hv[r];
-      }
-      *reinterpret_cast<uint2*>(sdOt + ((c & 7) * 8 + (c >> 3)) * ALD + r0) = make_uint2(hv[0] | (hv[1] << 16), hv[2] | (hv[3] << 16));
+      for (int r = 0; r < 4; ++r) sdO[(r0 + r) * ALD + c] = (r0 + r < a.Lq) ? f2bf(dOa[nb][r]) : (bf16_t)0;
     }
   }
   if (dpart == 0) sL[dr] = (dr < a.Lq) ? lse_r : 0.f;
+  kmask_bias(kbias4, a);
   ZK_AT(3);
   if (RPR) {
     const int nrel = 2 * a.max_rel + 1;
     stage_direct(sRk, a.rpr_k, AD, 0, nrel, tid);
     stage_direct(sRv, a.rpr_v, AD, 0, nrel, tid);
-    stage_trans(sRkT, a.rpr_k, AD, 0, nrel, tid);
     for (int e = tid; e < 3 * TQ * ALD / 8; e += 256)          // bucket tiles: rows / buckets that are never emitted
       reinterpret_cast<uint4*>(sSB)[e] = make_uint4(0u, 0u, 0u, 0u);
   }
@@ -759,11 +796,8 @@ __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const
       for (int r = 0; r < 4; ++r) dsv[nt][r] = pu[nt][r] * (dpv[nt][r] - Di[r]) * a.scale;
   }
   ZK_AT(5);
-  __syncthreads();                     // every wave is done reading sQ / sK / sV / sdO
-  ZK_AT(6);
-  bf16_t* sdS = sQ;
-  bf16_t* sPt = sK;
-  bf16_t* sdSt = sV;
+  // P^T and dS^T in the layout the accumulators have (4 consecutive queries of key row j per lane: one 8-byte store per key
+  // tile), into tiles nobody reads in phase 1; dQ takes dS by columns of dS^T
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) {
     const int j = nt * 16 + (lane & 15);
@@ -772,21 +806,19 @@ __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const
     pp.y = (uint32_t)f2bf(pv[nt][2]) | ((uint32_t)f2bf(pv[nt][3]) << 16);
     dd.x = (uint32_t)f2bf(dsv[nt][0]) | ((uint32_t)f2bf(dsv[nt][1]) << 16);
     dd.y = (uint32_t)f2bf(dsv[nt][2]) | ((uint32_t)f2bf(dsv[nt][3]) << 16);
-    *reinterpret_cast<uint2*>(sPt + j * ALD + rloc) = pp;       // 4 consecutive queries of key row j
+    *reinterpret_cast<uint2*>(sPt + j * ALD + rloc) = pp;
     *reinterpret_cast<uint2*>(sdSt + j * ALD + rloc) = dd;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sdS[(rloc + r) * ALD + j] = f2bf(dsv[nt][r]);
   }
   __syncthreads();
   if (RPR) {
-    rpr_bucket_wave(a, 2 * a.max_rel + 1, 0, w, lane, [&](int row, int j) { return bf2f(sdS[row * ALD + j]); },
+    rpr_bucket_wave(a, 2 * a.max_rel + 1, 0, w, lane, [&](int row, int j) { return bf2f(sdSt[j * ALD + row]); },
                     [&](int row, int r, float v) { const bf16_t x = f2bf(v); sSB[row * ALD + r] = x; sSBt[r * ALD + row] = x; });
     rpr_bucket_wave(a, 2 * a.max_rel + 1, 0, w, lane, [&](int row, int j) { return bf2f(sPt[j * ALD + row]); },
                     [&](int row, int r, float v) { sPBt[r * ALD + row] = f2bf(v); });
     __syncthreads();                     // the transposed bucket tiles are read across waves
   }
   if (a.dsb != nullptr) {   // bucket sums for the relative-position table products (see AttnArgs)
-    rpr_bucket_rows(a, a.dsb, b, h, 0, w, lane, [&](int row, int j) { return bf2f(sdS[row * ALD + j]); });
+    rpr_bucket_rows(a, a.dsb, b, h, 0, w, lane, [&](int row, int j) { return bf2f(sdSt[j * ALD + row]); });
     rpr_bucket_rows(a, a.pb, b, h, 0, w, lane, [&](int row, int j) { return bf2f(sPt[j * ALD + row]); });
   }
   // ---- phase 2: wave w -> dQ rows 16w.. (queries) and dK / dV rows 16w.. (keys)
@@ -800,14 +832,14 @@ __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const
   }
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
-    const uint4 da = frag(sdS, w * 16, kk, lane);
+    const uint4 da = frag_tr(sdSt, w * 16, kk, lane);    // dS rows (queries) x keys
     const uint4 pa = frag(sPt, w * 16, kk, lane);
     const uint4 dt = frag(sdSt, w * 16, kk, lane);
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
-      dQ[nb] = mfma16(da, frag(sKt, nb * 16, kk, lane), dQ[nb]);
-      dV[nb] = mfma16(pa, frag(sdOt, nb * 16, kk, lane), dV[nb]);
-      dK[nb] = mfma16(dt, frag(sQt, nb * 16, kk, lane), dK[nb]);
+      dQ[nb] = mfma16(da, frag_tr(sK, nb * 16, kk, lane), dQ[nb]);
+      dV[nb] = mfma16(pa, frag_tr(sdO, nb * 16, kk, lane), dV[nb]);
+      dK[nb] = mfma16(dt, frag_tr(sQ, nb * 16, kk, lane), dK[nb]);
     }
   }
   ZK_AT(8);
@@ -822,9 +854,9 @@ __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const
       const uint4 pt = frag(sPBt, w * 16, kk, lane);      // pb^T  rows (r) x queries
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) {
-        dQ[nb] = mfma16(sb, frag(sRkT, nb * 16, kk, lane), dQ[nb]);
-        tk[nb] = mfma16(st, frag(sQt, nb * 16, kk, lane), tk[nb]);
-        tv[nb] = mfma16(pt, frag(sdOt, nb * 16, kk, lane), tv[nb]);
+        dQ[nb] = mfma16(sb, frag_tr(sRk, nb * 16, kk, lane), dQ[nb]);
+        tk[nb] = mfma16(st, frag_tr(sQ, nb * 16, kk, lane), tk[nb]);
+        tv[nb] = mfma16(pt, frag_tr(sdO, nb * 16, kk, lane), tv[nb]);
       }
     }
     // this wave's 16 rows of the two [r][channel] partials through LDS (sG / sGd are dead since phase 1; a wave only
@@ -832,7 +864,7 @@ __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const
     float* pk = rpr_part + ((size_t)b * a.nh + h) * 2 * TQ * AD;
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
-      const int c = chan_of_phys(nb * 16 + (lane & 15));
+      const int c = nb * 16 + (lane & 15);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         sG[(rloc + r) * GLD + c] = tk[nb][r];
@@ -851,13 +883,13 @@ __device__ __forceinline__ void attn_bwd_fused64_tile(unsigned char* smem, const
       }
     }
   }
-  // results through LDS ([row][channel] tiles over the transposed operands, which are dead now) so that every
+  // results through LDS ([row][channel] tiles over dS^T, P^T and tile 6, which are dead now) so that every
   // thread stores 16 bytes instead of 48 scattered 2-byte elements
   __syncthreads();
-  bf16_t* oQ = sKt; bf16_t* oK = sQt; bf16_t* oV = sdOt;
+  bf16_t* oQ = sdSt; bf16_t* oK = sPt; bf16_t* oV = sT6;
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
-    const int c = chan_of_phys(nb * 16 + (lane & 15));
+    const int c = nb * 16 + (lane & 15);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = rloc + r;     // query row for dQ, key row for dK / dV
@@ -910,8 +942,13 @@ __device__ __forceinline__ void attn_bwd_rpr64_tile(unsigned char* smem, const A
   const uint64_t seed = a.thr ? *a.seed : 0;
   const int nrel = 2 * a.max_rel + 1;
 
-  // ---- prologue: every global load first
+  // ---- prologue: every global load first (lse and the key mask in front, compared behind the last load); the halves of
+  // the workgroup that transpose different tiles load through a selected pointer, not under a branch
   ZK_AT(0);
+  const int dr = tid >> 2, dpart = tid & 3;
+  const float lse_r = lse[((size_t)b * a.nh + h) * a.Lq + min(dr, a.Lq - 1)];
+  float kbias4[4];
+  kmask_load(kbias4, a, b, lane);
   DirectRegs rQ, rdO, rK, rV, rRk, rRv;
   TransRegs t0, t1;
   load_direct(rQ, qb, a.ldq, 0, a.Lq, tid);
@@ -920,28 +957,17 @@ __device__ __forceinline__ void attn_bwd_rpr64_tile(unsigned char* smem, const A
   load_direct(rV, vb, a.ldv, 0, a.Lk, tid);
   load_direct(rRk, a.rpr_k, AD, 0, nrel, tid);
   load_direct(rRv, a.rpr_v, AD, 0, nrel, tid);
-  if (tid < 128) {
-    load_trans(t0, kb, a.ldk, 0, a.Lk, tid);
-    load_trans(t1, a.rpr_k, AD, 0, nrel, tid);
-  } else {
-    load_trans(t0, qb, a.ldq, 0, a.Lq, tid - 128);
-    load_trans(t1, dob, lddo, 0, a.Lq, tid - 128);
-  }
-  const int dr = tid >> 2, dpart = tid & 3;
-  const float lse_r = lse[((size_t)b * a.nh + h) * a.Lq + min(dr, a.Lq - 1)];
-  float kbias4[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) {
-    const int j = nt * 16 + (lane & 15);
-    kbias4[nt] = (a.kmask != nullptr && a.kmask[(size_t)b * a.ldmask + min(j, a.Lk - 1)] == 0.f) ? -a.mask_inf : 0.f;
-  }
-  store_direct(T0, rQ, tid);
-  store_direct(T3, rdO, tid);
-  store_direct(T1, rK, tid);
-  store_direct(T2, rV, tid);
-  store_direct(T4, rRk, tid);
-  store_direct(T5, rRv, tid);
+  const bool lo128 = tid < 128;        // K^T and Rk^T; the other half Q^T and dO^T
+  load_trans(t0, lo128 ? kb : qb, lo128 ? a.ldk : a.ldq, 0, lo128 ? a.Lk : a.Lq, tid & 127);
+  load_trans(t1, lo128 ? a.rpr_k : dob, lo128 ? AD : lddo, 0, lo128 ? nrel : a.Lq, tid & 127);
+  store_direct(T0, rQ, tid, a.Lq);
+  store_direct(T3, rdO, tid, a.Lq);
+  store_direct(T1, rK, tid, a.Lk);
+  store_direct(T2, rV, tid, a.Lk);
+  store_direct(T4, rRk, tid, nrel);
+  store_direct(T5, rRv, tid, nrel);
   if (dpart == 0) sL[dr] = (dr < a.Lq) ? lse_r : 0.f;
+  kmask_bias(kbias4, a);
   ZK_AT(3);
   __syncthreads();
   ZK_AT(4);
@@ -1050,13 +1076,8 @@ __device__ __forceinline__ void attn_bwd_rpr64_tile(unsigned char* smem, const A
 #pragma unroll
     for (int r = 0; r < 4; ++r) sdS[(rloc + r) * ALD + j] = (bf16_t)((r & 1) ? ((r & 2 ? dd.y : dd.x) >> 16) : ((r & 2 ? dd.y : dd.x) & 0xffffu));
   }
-  if (tid < 128) {
-    store_trans(sKt, t0, tid);
-    store_trans(sRkT, t1, tid);
-  } else {
-    store_trans(sQt, t0, tid - 128);
-    store_trans(sdOt, t1, tid - 128);
-  }
+  store_trans(lo128 ? sKt : sQt, t0, tid & 127, lo128 ? a.Lk : a.Lq);
+  store_trans(lo128 ? sRkT : sdOt, t1, tid & 127, lo128 ? nrel : a.Lq);
   __syncthreads();
   ZK_AT(7);
   // ---- phase 2a: wave w -> dQ rows 16w.. (queries) and dK / dV rows 16w.. (keys)
