@@ -17,42 +17,16 @@ usage: python scripts/ensemble_bench.py [--sentences 256] [--repeats 3] [--dtype
 import argparse
 import json
 import os
-import subprocess
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-V = 32000
+import _benchlib as BL  # noqa: E402
+
+V = BL.V
 ROWS = 128
-
-
-def _params(args, i):
-    from zero_amd.config import transformer_base_params, SyntheticVocab
-    hp = transformer_base_params(model_name="transformer_aan", scope_name="ensbench%d" % i, beam_size=4, decode_alpha=0.6,
-                                 decode_length=50, eval_batch_size=32)
-    hp.src_vocab = SyntheticVocab(V)
-    hp.tgt_vocab = SyntheticVocab(V)
-    hp.decode_dtype = args.dtype
-    hp.random_seed = 1234 + i            # members of identical shape, different weights
-    return hp
-
-
-def _batches(args, hp):
-    import numpy as np
-    rng = np.random.default_rng(1234)
-    lens = np.clip(np.rint(rng.normal(28, 14, args.sentences)), 4, 100).astype(int)
-    order = np.argsort(lens, kind="stable")                     # length-sorted batches (data.py:69-73)
-    out = []
-    for b0 in range(0, args.sentences, hp.eval_batch_size):
-        idx = order[b0:b0 + hp.eval_batch_size]
-        src = np.zeros((len(idx), int(lens[idx].max()) + 1), dtype=np.int64)
-        for r, i in enumerate(idx):
-            src[r, :lens[i]] = rng.integers(3, V, lens[i])
-            src[r, lens[i]] = 2
-        out.append(src)
-    return out
 
 
 def leg_decode(args, M):
@@ -63,8 +37,9 @@ def leg_decode(args, M):
     from zero_amd.search import beam_search
     load_all()
     graph = registry.get_model("transformer_aan")
-    hps = [_params(args, i) for i in range(max(M, 1))]
-    batches = _batches(args, hps[0])
+    # members of identical shape, different weights
+    hps = [BL.decode_hp("transformer_aan", "ensbench%d" % i, args.dtype, random_seed=1234 + i) for i in range(max(M, 1))]
+    batches = BL.sorted_batches(V, args.sentences, hps[0].eval_batch_size)
 
     def one_pass():
         steps = sent = 0
@@ -136,21 +111,11 @@ def main():
         res = leg_kernel(args) if args.leg == "kernel" else leg_decode(args, int(args.leg))
         print("LEG " + json.dumps(res))
         return 0
-    legs = {}
-    for leg in ("0", "1", "2", "4", "kernel"):
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--sentences", str(args.sentences), "--repeats",
-               str(args.repeats), "--kernel-iters", str(args.kernel_iters), "--dtype", args.dtype]
-        try:
-            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=args.leg_timeout, text=True)
-        except subprocess.TimeoutExpired:
-            print("ensemble_bench: leg %s exceeded %d s; stopping" % (leg, args.leg_timeout), file=sys.stderr)
-            return 124
-        lines = [l for l in p.stdout.splitlines() if l.startswith("LEG ")]
-        if p.returncode != 0 or not lines:
-            sys.stderr.write(p.stderr[-4000:])
-            print("ensemble_bench: leg %s failed (exit %d); stopping" % (leg, p.returncode), file=sys.stderr)
-            return p.returncode or 1
-        legs[leg] = json.loads(lines[-1][4:])
+    legs, rc = BL.run_legs(__file__, ("0", "1", "2", "4", "kernel"), ["--sentences", args.sentences, "--repeats", args.repeats,
+                                                                      "--kernel-iters", args.kernel_iters, "--dtype", args.dtype],
+                           None, args.leg_timeout)
+    if rc:
+        return rc
     single = legs["0"]
     ens = {}
     for M in ("1", "2", "4"):

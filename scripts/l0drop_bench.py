@@ -19,7 +19,6 @@ import argparse
 import json
 import math
 import os
-import subprocess
 import sys
 import time
 
@@ -27,38 +26,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # before the HIP runtime initialises: several batches in flight
 
-V = 32000
+import _benchlib as BL  # noqa: E402
+
 LOG_ALPHA_0 = math.log(1.0 / 11.0)
 # leg -> bias of source_pruning (None: the plain transformer); log_alpha ~ N(b0, 3): quantiles of the normal distribution
 LEGS = {"transformer": None, "keep100": 20.0, "keep50": LOG_ALPHA_0, "keep25": LOG_ALPHA_0 - 0.674 * 3.0}
-
-
-def _params(args, model):
-    from zero_amd.config import transformer_base_params, SyntheticVocab
-    hp = transformer_base_params(model_name=model, scope_name="l0bench_" + model, beam_size=4, decode_alpha=0.6,
-                                 decode_length=50, eval_batch_size=32)
-    hp.src_vocab = SyntheticVocab(V)
-    hp.tgt_vocab = SyntheticVocab(V)
-    hp.decode_dtype = args.dtype
-    hp.search_mode = "cache"
-    hp.random_seed = 1234
-    return hp
-
-
-def _batches(args, hp):
-    import numpy as np
-    rng = np.random.default_rng(1234)
-    lens = np.clip(np.rint(rng.normal(28, 14, args.sentences)), 4, 100).astype(int)
-    order = np.argsort(lens, kind="stable")                     # length-sorted batches (data.py:69-73)
-    out = []
-    for b0 in range(0, args.sentences, hp.eval_batch_size):
-        idx = order[b0:b0 + hp.eval_batch_size]
-        src = np.zeros((len(idx), int(lens[idx].max()) + 1), dtype=np.int64)
-        for r, i in enumerate(idx):
-            src[r, :lens[i]] = rng.integers(3, V, lens[i])
-            src[r, lens[i]] = 2
-        out.append(src)
-    return out
 
 
 def leg(args, name):
@@ -73,15 +45,16 @@ def leg(args, name):
     load_all()
     b0 = LEGS[name]
     model = "transformer" if b0 is None else "transformer_l0drop"
-    hp = _params(args, model)
-    values = initial_values(_params(args, "transformer"), "transformer", 1234)          # the same weights in every leg
+    hp = BL.decode_hp(model, "l0bench_" + model, args.dtype)
+    # the same weights in every leg
+    values = initial_values(BL.decode_hp("transformer", "l0bench_transformer", args.dtype), "transformer", 1234)
     if b0 is not None:
         H = hp.hidden_size
         values["source_pruning/W_0_0"] = (np.random.default_rng(99).normal(0.0, 3.0 / math.sqrt(H), (H, 1))).astype(np.float32)
         values["source_pruning/b_0"] = np.asarray([b0], np.float32)
     core0 = get_core(hp, model, values)
     graph = registry.get_model(model)
-    batches = _batches(args, hp)
+    batches = BL.sorted_batches(BL.V, args.sentences, hp.eval_batch_size)
     tl = threading.local()
     stats = {"kept": 0, "valid": 0, "Lm": 0, "Ls": 0, "n": 0}
     lock = threading.Lock()
@@ -137,21 +110,10 @@ def main():
     if args.leg:
         print("LEG " + json.dumps(leg(args, args.leg)))
         return 0
-    legs = {}
-    for name in LEGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--sentences", str(args.sentences), "--repeats",
-               str(args.repeats), "--lanes", str(args.lanes), "--dtype", args.dtype]
-        try:
-            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=args.leg_timeout, text=True)
-        except subprocess.TimeoutExpired:
-            print("l0drop_bench: leg %s exceeded %d s; stopping" % (name, args.leg_timeout), file=sys.stderr)
-            return 124
-        lines = [l for l in p.stdout.splitlines() if l.startswith("LEG ")]
-        if p.returncode != 0 or not lines:
-            sys.stderr.write(p.stderr[-4000:])
-            print("l0drop_bench: leg %s failed (exit %d); stopping" % (name, p.returncode), file=sys.stderr)
-            return p.returncode or 1
-        legs[name] = json.loads(lines[-1][4:])
+    legs, rc = BL.run_legs(__file__, LEGS, ["--sentences", args.sentences, "--repeats", args.repeats, "--lanes", args.lanes,
+                                            "--dtype", args.dtype], None, args.leg_timeout)
+    if rc:
+        return rc
     base = legs["transformer"]
     for name, r in legs.items():
         r["sentences_per_s_vs_transformer"] = r["sentences_per_s"] / base["sentences_per_s"]

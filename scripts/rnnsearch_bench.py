@@ -28,7 +28,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-V = 32000
+import _benchlib as BL  # noqa: E402
+
 # pair -> [(leg, model, decode_dtype, hidden_size, embed_size)]
 PAIRS = {
     "bf16_512": [("bf16/transformer", "transformer", "bfloat16", 512, 512), ("bf16/rnnsearch", "rnnsearch", "bfloat16", 512, 512)],
@@ -37,25 +38,13 @@ PAIRS = {
 }
 
 
-def _params(leg, model, dtype, H, E):
-    from zero_amd.config import transformer_base_params, SyntheticVocab
-    hp = transformer_base_params(model_name=model, scope_name="rnnbench_" + leg.replace("/", "_"), beam_size=4,
-                                 decode_alpha=0.6, decode_length=50, eval_batch_size=32, hidden_size=H, embed_size=E,
-                                 cell="atr", caencoder=True, layer_norm=False)
-    hp.src_vocab = SyntheticVocab(V)
-    hp.tgt_vocab = SyntheticVocab(V)
-    hp.decode_dtype = dtype
-    hp.search_mode = "cache"
-    hp.random_seed = 1234
-    return hp
-
-
 class Leg(object):
     def __init__(self, leg, model, dtype, H, E, src):
         from zero_amd.models import model as registry
         from zero_amd.models._factory import get_core
         self.name, self.model, self.dtype, self.H, self.E, self.src = leg, model, dtype, H, E, src
-        self.hp = _params(leg, model, dtype, H, E)
+        self.hp = BL.decode_hp(model, "rnnbench_" + leg.replace("/", "_"), dtype, hidden_size=H, embed_size=E, cell="atr",
+                               caencoder=True, layer_norm=False)
         self.core = get_core(self.hp, model)
         self.enc, self.dec = registry.get_model(model).infer_fn(self.hp)
         self.enc_ms, self.all_ms, self.steps = [], [], 0
@@ -95,7 +84,6 @@ def main():
     ap.add_argument("--pairs", default=",".join(PAIRS), help="comma-separated subset of: " + ", ".join(PAIRS))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rnnsearch_bench.json"), help="'' writes no file")
     args = ap.parse_args()
-    import numpy as np
     import torch
     from zero_amd.models import load_all
     from zero_amd.models._factory import reset_cores
@@ -103,12 +91,7 @@ def main():
         print("rnnsearch_bench: needs a GPU (a CPU run measures nothing)", file=sys.stderr)
         return 1
     load_all()
-    rng = np.random.default_rng(1234)
-    lens = np.clip(np.rint(rng.normal(28, 6, 32)), 8, 48).astype(int)
-    src = np.zeros((len(lens), int(lens.max()) + 1), dtype=np.int64)
-    for r, n in enumerate(lens):
-        src[r, :n] = rng.integers(3, V, n)
-        src[r, n] = 2
+    src = BL.one_batch(BL.V)
     legs = {}
     for pair in args.pairs.split(","):
         reset_cores()

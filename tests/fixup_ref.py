@@ -18,18 +18,18 @@ a scalar shift in front of every sub-layer, a scalar scale behind it and no bias
 ``init_params`` / ``make_fixture``   the tiny model of the GPU model tests: every parameter matters, and the reference alone
                      is shown to be far from a tie on it.
 """
-import contextlib
 import copy
+import functools
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from oracle import ref_torch as rt
+from tests import variant_ref as V
 
 RES_DEFECTS = ("shift_before_residual", "scale_on_x", "scale2_dropped", "xs_from_rounded", "host_baked")
 FFN_DEFECTS = ("second_shift_dropped", "shift_inside_only", "host_baked")
-STORAGE = {"bf16": torch.bfloat16, "fp32": torch.float32}
 
 
 def _round_st(v, st):
@@ -149,7 +149,7 @@ def case_inputs(name, form, seed=0, ffn=False):
     """-> dict x (fp32 values) / y (values exactly representable in the storage type of `form`) [rows, H] torch float32, the
     scalars a, o, b (None where the case passes NULL), or h / o for a feed-forward case."""
     cs = (FFN_CASES if ffn else CASES)[name]
-    st = STORAGE[form]
+    st = V.STORAGE[form]
     g = torch.Generator().manual_seed(7100 + seed + sum(map(ord, name)) + (1000 if ffn else 0))
     rows, H = cs["rows"], cs["H"]
     null = cs.get("null", ())
@@ -167,20 +167,11 @@ def case_inputs(name, form, seed=0, ffn=False):
 
 
 def case_reference(name, x, form, defect=None, ffn=False):
-    st = STORAGE[form]
+    st = V.STORAGE[form]
     n = lambda t: None if t is None else t.double().numpy()
     if ffn:
         return relu_shift(n(x["h"]), x["o"], defect=defect, stale=STALE[1])
     return residual(n(x["x"]), n(x["y"]), x["a"], x["o"], x["b"], st=st, defect=defect, stale=STALE)
-
-
-def within(got, ref, bnd, what):
-    """Every element finite and within its bound; -> the largest |err| / bound (0 / 0 counts as 0)."""
-    from tests import parity as PR
-    got = torch.as_tensor(np.asarray(got, np.float64))
-    PR.assert_elementwise(got, torch.as_tensor(ref), torch.as_tensor(bnd), what)
-    err = np.abs(got.numpy() - ref)
-    return float(np.where(err > 0, err / np.maximum(bnd, 1e-300), 0.0).max())
 
 
 # ---------------------------------------------------------------------------------------------- ref_torch model
@@ -253,10 +244,7 @@ def encoder(source, hp, P):
             return _ffn(xs, P, scope)
         return rt.dot_attention(xs, None, bias, H, Pz, scope, hp.num_heads)["output"]
     out = _stack(x0, P, _sublayers("encoder", hp.num_encoder_layer, False), run, "encoder/shift/offset", "encoder/scale/scale")
-    B = out.shape[0]
-    init = {"layer_%d" % l: {"k": torch.zeros(B, 0, H, dtype=dt), "v": torch.zeros(B, 0, H, dtype=dt)}
-            for l in range(hp.num_decoder_layer)}
-    return {"encodes": out, "decoder_initializer": init, "mask": mask}
+    return {"encodes": out, "decoder_initializer": V.empty_caches(out.shape[0], H, hp.num_decoder_layer, dt), "mask": mask}
 
 
 def _decoder_layers(x0, state, hp, P, self_bias, caches):
@@ -282,20 +270,13 @@ def _decoder_layers(x0, state, hp, P, self_bias, caches):
 def decoding_fns(hp, P):
     """(encoding_fn, decoding_fn) of models/transformer_fixup.py:261-294 (search_mode = cache) for rt.beam_search."""
     hp = rt.closing_dropout(copy.copy(hp))
-    H = hp.hidden_size
 
     def encoding_fn(source):
-        state = encoder(source, hp, P)
-        state["decoder"] = {"state": state["decoder_initializer"]}
-        return state
+        return V.cached_state(encoder(source, hp, P))
 
     def decoding_fn(target, state, time):
-        dt = P["bias"].dtype
-        inputs = rt._st_fwd(P[rt._emb_name(hp, "tgt")])[target] * (H ** 0.5) + P["bias"]
-        if bool((target == hp.tgt_vocab.pad()).all()):
-            inputs = torch.zeros_like(inputs)
-        x0 = rt._st(inputs + rt.timing_signal(1, H, dt, time=time), "embed")
-        logits = _decoder_layers(x0, state, hp, P, rt.attention_bias(1, "causal").to(dt), state["decoder"]["state"])
+        x0 = V.embed_step(target, time, hp, P)
+        logits = _decoder_layers(x0, state, hp, P, rt.attention_bias(1, "causal").to(P["bias"].dtype), state["decoder"]["state"])
         return logits, state
 
     return encoding_fn, decoding_fn
@@ -304,24 +285,9 @@ def decoding_fns(hp, P):
 def full_decoder(target, state, hp, P):
     """The training-path decoder (models/transformer_fixup.py:91-203 with is_training): shifted inputs, causal bias.
     target [B, Lt] -> logits [B, Lt, V]."""
-    dt = P["bias"].dtype
-    H = hp.hidden_size
-    inputs = rt._st_fwd(P[rt._emb_name(hp, "tgt")])[target] * (H ** 0.5) + P["bias"]
-    inputs = torch.nn.functional.pad(inputs, (0, 0, 1, 0))[:, :-1, :]
-    x0 = rt._st(inputs + rt.timing_signal(inputs.shape[1], H, dt), "embed")
-    logits = _decoder_layers(x0, state, hp, P, rt.attention_bias(target.shape[1], "causal").to(dt), None)
+    x0 = V.embed_shifted(target, hp, P)
+    logits = _decoder_layers(x0, state, hp, P, rt.attention_bias(target.shape[1], "causal").to(P["bias"].dtype), None)
     return logits.reshape(target.shape[0], target.shape[1], -1)
-
-
-@contextlib.contextmanager
-def storage_model(on):
-    """ref_torch's own bf16 storage model (Cfg.store_bf16) for the duration of the block."""
-    prev = rt.Cfg.store_bf16
-    rt.Cfg.store_bf16 = bool(on)
-    try:
-        yield
-    finally:
-        rt.Cfg.store_bf16 = prev
 
 
 def score(hp, Pn, src, tgt, dtype=torch.float64, store_bf16=False):
@@ -329,7 +295,7 @@ def score(hp, Pn, src, tgt, dtype=torch.float64, store_bf16=False):
     positions that are not padding.  -> float64 numpy [B]."""
     hp = rt.closing_dropout(copy.copy(hp))
     P = rt.to_torch(Pn, dtype=dtype)
-    with storage_model(store_bf16), torch.no_grad():
+    with V.storage_model(store_bf16), torch.no_grad():
         target = torch.as_tensor(tgt)
         mask = (target != 0).to(dtype)
         target, mask = rt.remove_invalid_seq(target, mask)
@@ -393,74 +359,21 @@ def init_params(hp, seed):
     return Pn
 
 
-def search(hp, Pn, src, K, dtype=torch.float32, store_bf16=False):
-    hp = copy.copy(hp)
-    hp.beam_size, hp.search_mode = K, "cache"
-    hp.search_trace = []
-    with storage_model(store_bf16), torch.no_grad():
-        enc, dec = decoding_fns(hp, rt.to_torch(Pn, dtype=dtype))
-        out = rt.beam_search({"source": torch.as_tensor(src)}, enc, dec, hp)
-    return out, hp.search_trace
-
-
 def make_fixture(hp, src, seed, factor=4.0):
-    """The tiny model of the GPU model tests, with the proof that the REFERENCE ALONE is far from a tie on it.  Measured on
-    the CPU, for beam 1 and 4:
-      * the float64 and the fp32 run of the restated reference give identical hypotheses (every beam, every token) and the
-        same candidate order at every step;
-      * gap      the smallest difference, over all steps and sentences of the float64 run, between a candidate the search
-                 keeps (one of its 2K) and its runner-up (the next one in rank, kept or not);
-      * err      the largest |score_fp32 - score_float64| over the kept candidates;
-      and gap > factor * err (factor 4, as tests/rela_ref.make_fixture asks of its margin).
+    """The tiny model of the GPU model tests, with the proof that the REFERENCE ALONE is far from a tie on it
+    (variant_ref.candidate_margin, beam 1 and 4): the float64 and the fp32 run of the restated reference give identical
+    hypotheses and candidate orders, and the smallest gap between a kept candidate and its runner-up exceeds factor x the
+    largest fp32 - float64 score difference.
     -> dict Pn, gap, err (the worst over both beams)."""
     Pn = init_params(hp, seed)
-    gap, err = np.inf, 0.0
-    for K in (1, 4):
-        o64, t64 = search(hp, Pn, src, K, torch.float64)
-        o32, t32 = search(hp, Pn, src, K, torch.float32)
-        assert np.array_equal(o64["seq"], o32["seq"]), ("float64 and fp32 reference disagree", K, seed)
-        assert len(t64) == len(t32)
-        for (s64, i64), (s32, i32) in zip(t64, t32):
-            s64, s32 = np.maximum(s64.astype(np.float64), -1e35), np.maximum(s32.astype(np.float64), -1e35)
-            live = s64[:, :2 * K] > -1e30                      # (the first step of a beam has K - 1 dead rows)
-            g = np.where(live, s64[:, :2 * K] - s64[:, 1:2 * K + 1], np.inf)      # each kept candidate and its runner-up
-            gap = min(gap, float(g.min()))
-            assert np.array_equal(i64[:, :2 * K][live], i32[:, :2 * K][live]), ("candidate order differs", K, seed)
-            err = max(err, float(np.abs(s64[:, :2 * K] - s32[:, :2 * K])[live].max()))
-    assert gap > factor * err, (gap, err, seed)
-    return {"Pn": Pn, "gap": gap, "err": err}
+    return dict(V.candidate_margin(functools.partial(V.search, decoding_fns), hp, Pn, src, factor=factor, seed=seed), Pn=Pn)
 
 
 # ---------------------------------------------------------------------------------------------- the GPU model tests' fixture
 FIXTURE_SEED = 45                 # chosen among 41 .. 52 for the widest gap / err (tests/test_gpu_fixup_model.py quotes it)
 FIXTURE_LENGTHS = (14, 5, 9, 11)
 TARGET_LENGTHS = (10, 4, 7, 6)
+SOURCE_SEED, TARGET_SEED = 5, 9     # variant_ref.ragged(FIXTURE_LENGTHS, Vs, SOURCE_SEED) / (TARGET_LENGTHS, Vt, TARGET_SEED)
 # largest relative error of score() under ref_torch's bf16 storage model against its float64 run on the fixture (measured on
 # the CPU; tests/test_fixup_host.py re-measures it): the floor the device's bf16 score_fn is held to 4 x of
 SCORE_FLOOR = 4.966e-4
-
-
-def fixture_source(hp, lengths=FIXTURE_LENGTHS, seed=5, width=None):
-    rng = np.random.default_rng(seed)
-    src = np.zeros((len(lengths), width or max(lengths)), dtype=np.int64)
-    for b, n in enumerate(lengths):
-        src[b, :n - 1] = rng.integers(3, hp.src_vocab.size(), n - 1)
-        src[b, n - 1] = 2
-    return src
-
-
-def fixture_targets(hp, lengths=TARGET_LENGTHS, seed=9):
-    """Padded targets of unequal length (eos = 2, pad = 0)."""
-    rng = np.random.default_rng(seed)
-    tgt = np.zeros((len(lengths), max(lengths)), dtype=np.int64)
-    for b, n in enumerate(lengths):
-        tgt[b, :n - 1] = rng.integers(3, hp.tgt_vocab.size(), n - 1)
-        tgt[b, n - 1] = 2
-    return tgt
-
-
-def sharpen(Pn):
-    """The output distribution sharpened x 6 so that bf16 noise cannot flip near-ties of a random model."""
-    Pn = dict(Pn)
-    Pn["tgt_embedding"] = (Pn["tgt_embedding"] * 6.0).astype(np.float32)
-    return Pn

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from oracle import ref_torch as rt
+from tests import variant_ref as V
 
 LOG_ALPHA_0 = math.log(1.0 / 11.0)          # sigmoid(a) * 1.2 - 0.1 = 0  <=>  a = log(1 / 11)
 MASK_INF = 1e9                              # as tests/decode_parity.py
@@ -266,8 +267,7 @@ def decoding_fns(hp, P, trace=None):
     H, nh = hp.hidden_size, hp.num_heads
 
     def encoding_fn(source):
-        state = rt.encoder(source, hp, P, "transformer", False)
-        state["decoder"] = {"state": state["decoder_initializer"]}
+        state = V.cached_state(rt.encoder(source, hp, P, "transformer", False))
         if trace is not None:
             _, _, _, la = _prune_torch(state["encodes"], state["mask"], P)
             trace["log_alpha"], trace["mask"] = la.detach().double().numpy(), state["mask"].numpy()
@@ -275,10 +275,7 @@ def decoding_fns(hp, P, trace=None):
 
     def decoding_fn(target, state, time):
         dt = P["bias"].dtype
-        inputs = rt._st_fwd(P[rt._emb_name(hp, "tgt")])[target] * (H ** 0.5) + P["bias"]
-        if bool((target == hp.tgt_vocab.pad()).all()):
-            inputs = torch.zeros_like(inputs)
-        x = rt._st(inputs + rt.timing_signal(1, H, dt, time=time), "embed")
+        x = V.embed_step(target, time, hp, P)
         memory, mem_mask, count, _ = _prune_torch(state["encodes"], state["mask"], P)
         for l in range(hp.num_decoder_layer):
             pre = "decoder/layer_%d" % l
@@ -308,15 +305,11 @@ def with_pruning(Pn, W, b0):
 
 def log_alpha_of(hp, Pn, src, store_bf16=False, dtype=torch.float32):
     """log_alpha [B, Ls] (float64 numpy) and the source mask of ref_torch's encoder on `src`."""
-    old = rt.Cfg.store_bf16
-    rt.Cfg.store_bf16 = store_bf16
-    try:
+    with V.storage_model(store_bf16):
         P = rt.to_torch(Pn, dtype=dtype)
         st = rt.encoder(torch.as_tensor(src), rt.closing_dropout(copy.copy(hp)), P, "transformer", False)
         _, _, _, la = _prune_torch(st["encodes"], st["mask"], P)
         return la.detach().double().numpy(), st["mask"].double().numpy()
-    finally:
-        rt.Cfg.store_bf16 = old
 
 
 def make_fixture(hp, src, seed, lo=0.25, hi=0.75):

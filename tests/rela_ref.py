@@ -20,11 +20,13 @@ func.dot_attention replaced by it).  For one query row i, head h of nh, d = H / 
 ``init_params`` / ``make_fixture``   the tiny model of the GPU model tests and its measured distance from the discontinuity.
 """
 import copy
+import functools
 
 import numpy as np
 import torch
 
 from oracle import ref_torch as rt
+from tests import variant_ref as V
 
 EPS = 1e-8
 DEFECTS = ("mask_added", "rms_per_head", "normalised", "gate_no_x", "no_qscale", "extra_key", "neighbour_keys",
@@ -154,7 +156,6 @@ CASES = {
     "bf16_H2048": dict(B=2, G=2, nh=32, d=64, Lq=1, Lk=9, lengths=(7,), layout="kv", forms=("bf16",)),
     "fp32_d8": dict(B=4, G=2, nh=2, d=8, Lq=1, Lk=11, lengths=(11, 4), layout="kv", forms=("fp32",)),
 }
-STORAGE = {"bf16": torch.bfloat16, "fp32": torch.float32}
 SPECIAL_SCORES = (0.05, 1.0, 20.0, 3e-3)       # the single positive score of the rows 2 .. 5 of "special" (rows 0, 1: none)
 
 
@@ -166,7 +167,7 @@ def case_inputs(name, form, seed=0):
     mean square far above eps even with ONE key; masked keys are twice the mean query of their sentence: large positive
     scores, which only a mask that MULTIPLIES removes."""
     cs = CASES[name]
-    st = STORAGE[form]
+    st = V.STORAGE[form]
     B, G, nh, d, Lq, Lk = (cs[x] for x in ("B", "G", "nh", "d", "Lq", "Lk"))
     H, nB = nh * d, B // G
     g = torch.Generator().manual_seed(4200 + seed + sum(map(ord, name)))
@@ -217,17 +218,6 @@ def case_reference(name, x, time=None, defect=None):
 def case_runs(name):
     """The (time,) variants of a case: cached steps run once per device-resident position, the others once."""
     return [(t,) for t in CASES[name].get("times", (None,))]
-
-
-def assert_within(got, ref, out_dtype, what):
-    """Every element finite and within bound(ref); -> the largest |err| / bound (0/0 counts as 0)."""
-    from tests import parity as PR
-    b = bound(ref, out_dtype)
-    H = ref["out"].shape[-1]
-    got = torch.as_tensor(np.asarray(got, np.float64)).reshape(-1, H)
-    PR.assert_elementwise(got, torch.as_tensor(ref["out"]).reshape(-1, H), torch.as_tensor(b).reshape(-1, H), what)
-    err = np.abs(got.numpy() - ref["out"].reshape(-1, H))
-    return float(np.where(err > 0, err / np.maximum(b.reshape(-1, H), 1e-300), 0.0).max())
 
 
 # ---------------------------------------------------------------------------------------------- ref_torch model
@@ -282,10 +272,7 @@ def encoder(source, hp, P):
         x = rt.layer_norm(rt.residual_fn(x, y), P, pre + "/self_attention")
         y = rt.ffn_layer(x, P, pre + "/feed_forward", None, False)
         x = rt.layer_norm(rt.residual_fn(x, y), P, pre + "/feed_forward")
-    B = x.shape[0]
-    init = {"layer_%d" % l: {"k": torch.zeros(B, 0, H, dtype=dt), "v": torch.zeros(B, 0, H, dtype=dt)}
-            for l in range(hp.num_decoder_layer)}
-    return {"encodes": x, "decoder_initializer": init, "mask": mask}
+    return {"encodes": x, "decoder_initializer": V.empty_caches(x.shape[0], H, hp.num_decoder_layer, dt), "mask": mask}
 
 
 def _decoder_layers(x, state, hp, P, self_bias, caches):
@@ -310,21 +297,14 @@ def _decoder_layers(x, state, hp, P, self_bias, caches):
 def decoding_fns(hp, P):
     """(encoding_fn, decoding_fn) of models/transformer_rela.py:252-285 (search_mode = cache) for rt.beam_search."""
     hp = rt.closing_dropout(copy.copy(hp))
-    H = hp.hidden_size
 
     def encoding_fn(source):
-        state = encoder(source, hp, P)
-        state["decoder"] = {"state": state["decoder_initializer"]}
-        return state
+        return V.cached_state(encoder(source, hp, P))
 
     def decoding_fn(target, state, time):
-        dt = P["bias"].dtype
-        inputs = rt._st_fwd(P[rt._emb_name(hp, "tgt")])[target] * (H ** 0.5) + P["bias"]
-        if bool((target == hp.tgt_vocab.pad()).all()):
-            inputs = torch.zeros_like(inputs)
-        x = rt._st(inputs + rt.timing_signal(1, H, dt, time=time), "embed")
+        x = V.embed_step(target, time, hp, P)
         # transformer_rela.py:131-140: the causal bias of ONE query position, [1, 1, 1, 1] of zeros -> every cached key counts
-        logits = _decoder_layers(x, state, hp, P, rt.attention_bias(1, "causal").to(dt), state["decoder"]["state"])
+        logits = _decoder_layers(x, state, hp, P, rt.attention_bias(1, "causal").to(P["bias"].dtype), state["decoder"]["state"])
         return logits, state
 
     return encoding_fn, decoding_fn
@@ -333,12 +313,8 @@ def decoding_fns(hp, P):
 def full_decoder(target, state, hp, P):
     """The training-path decoder (models/transformer_rela.py:88-181): shifted inputs, the [L, L] causal bias MULTIPLIED into
     the scores as a 0/1 mask.  target [B, Lt] without padding -> logits [B, Lt, V]."""
-    dt = P["bias"].dtype
-    H = hp.hidden_size
-    inputs = rt._st_fwd(P[rt._emb_name(hp, "tgt")])[target] * (H ** 0.5) + P["bias"]
-    inputs = torch.nn.functional.pad(inputs, (0, 0, 1, 0))[:, :-1, :]
-    x = rt._st(inputs + rt.timing_signal(inputs.shape[1], H, dt), "embed")
-    logits = _decoder_layers(x, state, hp, P, rt.attention_bias(target.shape[1], "causal").to(dt), None)
+    x = V.embed_shifted(target, hp, P)
+    logits = _decoder_layers(x, state, hp, P, rt.attention_bias(target.shape[1], "causal").to(P["bias"].dtype), None)
     return logits.reshape(target.shape[0], target.shape[1], -1)
 
 
@@ -366,38 +342,13 @@ def init_params(hp, seed):
     return Pn
 
 
-def _search(hp, Pn, src, K, dtype):
-    hp = copy.copy(hp)
-    hp.beam_size, hp.search_mode = K, "cache"
-    hp.search_trace = []
-    enc, dec = decoding_fns(hp, rt.to_torch(Pn, dtype=dtype))
-    out = rt.beam_search({"source": torch.as_tensor(src)}, enc, dec, hp)
-    return out, hp.search_trace
-
-
 def make_fixture(hp, src, seed, factor=4.0):
     """The tiny model of the GPU model tests, with the proof that the REFERENCE ALONE is far from its discontinuity on it.
     ReLA has one softmax lacks: a row whose only positive score is barely positive is normalised up to O(1) by the
-    RMSNorm, so a rounding that flips that score's sign changes the row by O(1).  Measured on the CPU, for beam 1 and 4:
-      * the float64 and the fp32 run of the restated reference give identical hypotheses (every beam, every token);
-      * gap      the smallest difference, over all steps and sentences of the float64 run, between a candidate the
-                 search keeps (one of its 2K) and its runner-up (the next one in rank, kept or not);
-      * err      the largest |score_fp32 - score_float64| over the candidates both runs rank (the kept 2K);
-      and gap > factor * err (factor 4, as tests/l0drop_ref.make_fixture asks of its margin).
+    RMSNorm, so a rounding that flips that score's sign changes the row by O(1).  Measured on the CPU, for beam 1 and 4
+    (variant_ref.candidate_margin): the float64 and the fp32 run of the restated reference give identical hypotheses and
+    candidate orders, and the smallest gap between a kept candidate and its runner-up exceeds factor x the largest fp32 -
+    float64 score difference.
     -> dict Pn, gap, err (the worst over both beams)."""
     Pn = init_params(hp, seed)
-    gap, err = np.inf, 0.0
-    for K in (1, 4):
-        o64, t64 = _search(hp, Pn, src, K, torch.float64)
-        o32, t32 = _search(hp, Pn, src, K, torch.float32)
-        assert np.array_equal(o64["seq"], o32["seq"]), ("float64 and fp32 reference disagree", K, seed)
-        assert len(t64) == len(t32)
-        for (s64, i64), (s32, i32) in zip(t64, t32):
-            s64, s32 = np.maximum(s64.astype(np.float64), -1e35), np.maximum(s32.astype(np.float64), -1e35)
-            live = s64[:, :2 * K] > -1e30                      # (the first step of a beam has K - 1 dead rows)
-            g = np.where(live, s64[:, :2 * K] - s64[:, 1:2 * K + 1], np.inf)      # each kept candidate and its runner-up
-            gap = min(gap, float(g.min()))
-            assert np.array_equal(i64[:, :2 * K][live], i32[:, :2 * K][live]), ("candidate order differs", K, seed)
-            err = max(err, float(np.abs(s64[:, :2 * K] - s32[:, :2 * K])[live].max()))
-    assert gap > factor * err, (gap, err, seed)
-    return {"Pn": Pn, "gap": gap, "err": err}
+    return dict(V.candidate_margin(functools.partial(V.search, decoding_fns), hp, Pn, src, factor=factor, seed=seed), Pn=Pn)

@@ -27,11 +27,13 @@ figures.)  rel <= 1/4 in both forms, so the GPU tests hold the scores to that st
 restatement keeps the fp32 best hypotheses of the x 6 sharpened model on both.
 """
 import copy
+import functools
 
 import numpy as np
 import torch
 
 from oracle import ref_torch as rt
+from tests import variant_ref as V
 
 ATR_DEFECTS = ("no_twin", "gates_swapped", "no_carry", "bf16_state", "no_bias", "no_gather", "u_transposed")
 ADD_DEFECTS = ("mask_ignored", "neighbour_memory", "ctx_from_pm", "no_tanh", "extra_key", "no_v")
@@ -205,21 +207,6 @@ def add_standin(qa, pm, mem, v, mask, kv_group, Ls, form, copy=False, inf=INF):
     return out.double().numpy()
 
 
-def assert_within(got, ref_out, bound, what):
-    """Every element finite and within its bound; -> the largest |err| / bound (0 / 0 counts as 0)."""
-    from tests import parity as PR
-    got = torch.as_tensor(np.asarray(got, np.float64))
-    PR.assert_elementwise(got, torch.as_tensor(ref_out), torch.as_tensor(bound), what)
-    err = np.abs(got.numpy() - ref_out)
-    return float(np.where(err > 0, err / np.maximum(bound, 1e-300), 0.0).max())
-
-
-def exceeds(got, ref_out, bound):
-    """True when some element is outside its bound (or not finite): what a planted defect must do."""
-    err = np.abs(np.asarray(got, np.float64) - ref_out)
-    return bool((~np.isfinite(err)).any() or (err > bound).any())
-
-
 # ---------------------------------------------------------------------------------------------- ref_torch model
 def _w(P, name):
     return rt._st_fwd(P[name])
@@ -311,9 +298,7 @@ def decoding_fns(hp, P):
     hp = rt.closing_dropout(copy.copy(hp))
 
     def encoding_fn(source):
-        state = encoder(source, hp, P)
-        state["decoder"] = {"state": state["decoder_initializer"]}
-        return state
+        return V.cached_state(encoder(source, hp, P))
 
     def decoding_fn(target, state, time):
         tok = target[:, -1]
@@ -353,62 +338,25 @@ def init_params(hp, seed):
     return perturb(Pn, rng)
 
 
-def sharpen(hp, Pn, factor=6.0):
-    """The output distribution sharpened so that bf16 noise cannot flip near-ties of a random model."""
-    Pn = dict(Pn)
-    name = rt._emb_name(hp, "softmax")
-    Pn[name] = (Pn[name] * factor).astype(np.float32)
-    return Pn
-
-
-def search(hp, Pn, src, K, dtype, store_bf16=False):
-    hp = copy.copy(hp)
-    hp.beam_size, hp.search_mode = K, "cache"
-    hp.search_trace = []
-    old = rt.Cfg.store_bf16
-    rt.Cfg.store_bf16 = store_bf16
-    try:
-        enc, dec = decoding_fns(hp, rt.to_torch(Pn, dtype=dtype))
-        out = rt.beam_search({"source": torch.as_tensor(src)}, enc, dec, hp)
-    finally:
-        rt.Cfg.store_bf16 = old
-    return out, hp.search_trace
-
-
 def make_fixture(hp, src, seed, factor=4.0):
     """The tiny model of the GPU model tests with what the REFERENCE ALONE shows on it, measured on the CPU and asserted,
     for beam 1 and 4:
-      * the float64 and the fp32 run give identical hypotheses (every beam, every token) and candidate order at every step;
-      * gap   the smallest difference, over all steps and sentences of the float64 run, between a candidate the search keeps
-              (one of its 2K) and its runner-up;   err   the largest |score_fp32 - score_float64| over the kept candidates;
-              gap > factor * err;
+      * variant_ref.candidate_margin: the float64 and the fp32 run give identical hypotheses and candidate orders, and the
+        smallest gap between a kept candidate and its runner-up exceeds factor x err, the largest fp32 - float64 score
+        difference;  rel: that difference as a share of ATOL + RTOL |score_float64| -- how much of the project's fp32 score
+        tolerance the fp32 reference itself uses up (score_tol);
       * with the output embedding sharpened x 6, the bf16-storage restatement (rt.Cfg.store_bf16) keeps the best hypothesis
         of every sentence of the fp32 run.
-      * rel   the largest |score_fp32 - score_float64| / (ATOL + RTOL |score_float64|) over the same candidates: how much of
-              the project's fp32 score tolerance the fp32 reference itself uses up (score_tol).
     -> dict Pn, gap, err, rel (the worst over both beams)."""
     Pn = init_params(hp, seed)
-    gap, err, rel = np.inf, 0.0, 0.0
+    search = functools.partial(V.search, decoding_fns)
+    m = V.candidate_margin(search, hp, Pn, src, factor=factor, tol=(ATOL, RTOL), seed=seed)
+    Ps = V.sharpen(hp, Pn)
     for K in (1, 4):
-        o64, t64 = search(hp, Pn, src, K, torch.float64)
-        o32, t32 = search(hp, Pn, src, K, torch.float32)
-        assert np.array_equal(o64["seq"], o32["seq"]), ("float64 and fp32 reference disagree", K, seed)
-        assert len(t64) == len(t32)
-        for (s64, i64), (s32, i32) in zip(t64, t32):
-            s64, s32 = np.maximum(s64.astype(np.float64), -1e35), np.maximum(s32.astype(np.float64), -1e35)
-            live = s64[:, :2 * K] > -1e30                      # (the first step of a beam has K - 1 dead rows)
-            g = np.where(live, s64[:, :2 * K] - s64[:, 1:2 * K + 1], np.inf)
-            gap = min(gap, float(g.min()))
-            assert np.array_equal(i64[:, :2 * K][live], i32[:, :2 * K][live]), ("candidate order differs", K, seed)
-            diff = np.abs(s64[:, :2 * K] - s32[:, :2 * K])
-            err = max(err, float(diff[live].max()))
-            rel = max(rel, float((diff / (ATOL + RTOL * np.abs(s64[:, :2 * K])))[live].max()))
-        Ps = sharpen(hp, Pn)
         a, _ = search(hp, Ps, src, K, torch.float32)
         b, _ = search(hp, Ps, src, K, torch.float32, store_bf16=True)
         assert rt.decode_hypothesis(a["seq"], hp) == rt.decode_hypothesis(b["seq"], hp), ("bf16 storage model", K, seed)
-    assert gap > factor * err, (gap, err, seed)
-    return {"Pn": Pn, "gap": gap, "err": err, "rel": rel}
+    return dict(m, Pn=Pn)
 
 
 LENGTHS = (14, 5, 9, 11)
@@ -420,12 +368,3 @@ def fixture_hp(caencoder=True, **kw):
                  scope_name="t_rnnsearch_%s" % ("ca" if caencoder else "bi"), **kw)
     hp.embed_size = 64
     return hp
-
-
-def source(hp, lengths=LENGTHS, seed=5, width=None):
-    rng = np.random.default_rng(seed)
-    src = np.zeros((len(lengths), width or max(lengths)), dtype=np.int64)
-    for b, n in enumerate(lengths):
-        src[b, :n - 1] = rng.integers(3, hp.src_vocab.size(), n - 1)
-        src[b, n - 1] = 2
-    return src

@@ -19,6 +19,7 @@ import torch
 
 from oracle import ref_torch as rt
 from tests import parity as PR
+from tests import variant_ref as V
 
 U = PR.PER_TERM                  # 2^-23: twice the unit roundoff of fp32, per accumulated term
 TILE_ROWS, TILE_KEYS = 32, 64    # zk_f32_attn_seq: query rows per workgroup (SEQ_BR), keys per staged tile (SEQ_TK)
@@ -366,15 +367,6 @@ IDENTITY_PAD = 6.0
 IDENTITY_DIR = 4.0            # length of the direction added to the last LayerNorm offset that carries both
 
 
-def _ragged(lengths, V, seed):
-    rng = np.random.default_rng(seed)
-    out = np.zeros((len(lengths), max(lengths)), dtype=np.int64)
-    for b, n in enumerate(lengths):
-        out[b, :n - 1] = rng.integers(3, V, n - 1)
-        out[b, n - 1] = 2
-    return out
-
-
 def model_fixture(case, seed=11):
     """-> (hp, Pn, src, tgt): the tiny model of tests.common.make_hp with perturbed biases / LayerNorm parameters, padded
     sources (14, 5, 9, 11 tokens) and targets (10, 4, 7, 6 tokens)."""
@@ -382,8 +374,8 @@ def model_fixture(case, seed=11):
     model, kw = MODEL_CASES[case]
     hp = make_hp(model, scope_name="t_sf32_" + case.replace("-", "_"), **kw)
     Pn = perturb(rt.init_params(hp, model, seed=seed + 1), np.random.default_rng(seed))
-    src = _ragged(SOURCE_LENGTHS, hp.src_vocab.size(), 5)
-    tgt = _ragged(TARGET_LENGTHS, hp.tgt_vocab.size(), 6)
+    src = V.ragged(SOURCE_LENGTHS, hp.src_vocab.size(), 5)
+    tgt = V.ragged(TARGET_LENGTHS, hp.tgt_vocab.size(), 6)
     return hp, Pn, src, tgt
 
 
@@ -412,7 +404,7 @@ def identity_fixture():
     E[hp.tgt_vocab.eos()] += IDENTITY_EOS / IDENTITY_DIR * e
     E[hp.tgt_vocab.pad()] -= IDENTITY_PAD / IDENTITY_DIR * e
     Pn[name] = E.astype(np.float32)
-    src = _ragged(SOURCE_LENGTHS, hp.src_vocab.size(), 5)
+    src = V.ragged(SOURCE_LENGTHS, hp.src_vocab.size(), 5)
     return hp, Pn, src
 
 

@@ -15,6 +15,7 @@ import torch
 
 from oracle import ref_torch as rt
 from tests import fixup_ref as R
+from tests import variant_ref as V
 from tests.common import make_hp
 
 MODEL = "transformer_fixup"
@@ -93,12 +94,12 @@ FFN_RUNS = [(name, form) for name in R.FFN_CASES for form in FORMS]
 
 
 def _check_residual(got_x, got_xs, ref, x, form, what):
-    bx, bxs = R.residual_bound(ref, R.STORAGE[form])
+    bx, bxs = R.residual_bound(ref, V.STORAGE[form])
     r = 0.0
     if got_x is not None:
-        r = max(r, R.within(got_x, ref["x_out"], bx, what + " x_out"))
+        r = max(r, V.assert_within(got_x, ref["x_out"], bx, what + " x_out"))
     if got_xs is not None:
-        r = max(r, R.within(got_xs, ref["xs"], bxs, what + " xs_out"))
+        r = max(r, V.assert_within(got_xs, ref["xs"], bxs, what + " xs_out"))
     return r
 
 
@@ -107,13 +108,13 @@ def test_standins_are_within_the_bounds_on_every_case():
     for name, form in RUNS:
         x = R.case_inputs(name, form)
         ref = R.case_reference(name, x, form)
-        gx, gxs = R.standin_residual(x["x"], x["y"], x["a"], x["o"], x["b"], R.STORAGE[form])
+        gx, gxs = R.standin_residual(x["x"], x["y"], x["a"], x["o"], x["b"], V.STORAGE[form])
         worst[form] = max(worst[form], _check_residual(gx.double().numpy(), gxs.double().numpy(), ref, x, form, "%s %s" % (name, form)))
     for name, form in FFN_RUNS:
         x = R.case_inputs(name, form, ffn=True)
         ref = R.case_reference(name, x, form, ffn=True)
-        got = R.standin_relu_shift(x["h"], x["o"], R.STORAGE[form])
-        worst[form] = max(worst[form], R.within(got.double().numpy(), ref["out"], R.relu_shift_bound(ref, R.STORAGE[form]), name))
+        got = R.standin_relu_shift(x["h"], x["o"], V.STORAGE[form])
+        worst[form] = max(worst[form], V.assert_within(got.double().numpy(), ref["out"], R.relu_shift_bound(ref, V.STORAGE[form]), name))
     print("stand-ins: largest |err| / bound bf16 %.3f, fp32 %.3f" % (worst["bf16"], worst["fp32"]))
 
 
@@ -160,7 +161,7 @@ def test_each_planted_relu_shift_defect_is_outside_the_bound_somewhere(defect):
         ref = R.case_reference(name, x, form, ffn=True)
         bad = R.case_reference(name, x, form, defect=defect, ffn=True)
         try:
-            R.within(bad["out"], ref["out"], R.relu_shift_bound(ref, R.STORAGE[form]), defect)
+            V.assert_within(bad["out"], ref["out"], R.relu_shift_bound(ref, V.STORAGE[form]), defect)
         except AssertionError:
             caught.append((name, form))
     print("%s: outside the bound on %s" % (defect, caught))
@@ -222,16 +223,16 @@ def test_fixture_of_the_gpu_model_tests():
     fp32 reference's best hypotheses on the sharpened model (so the reference alone meets the bf16 test's condition); and the
     floor of the score test: the largest relative score error of the bf16 storage model against float64."""
     hp = make_hp(MODEL, search_mode="cache")
-    src = R.fixture_source(hp)
+    src = V.ragged(R.FIXTURE_LENGTHS, hp.src_vocab.size(), R.SOURCE_SEED)
     f = R.make_fixture(hp, src, R.FIXTURE_SEED)
     print("seed %d: gap %.3e, err %.3e (x %.0f)" % (R.FIXTURE_SEED, f["gap"], f["err"], f["gap"] / f["err"]))
     assert f["gap"] > 4 * f["err"]
-    Ps = R.sharpen(f["Pn"])
+    Ps = V.sharpen(hp, f["Pn"])
     for K in (1, 4):
-        a, _ = R.search(hp, Ps, src, K, torch.float32)
-        b, _ = R.search(hp, Ps, src, K, torch.float32, store_bf16=True)
+        a, _ = V.search(R.decoding_fns, hp, Ps, src, K, torch.float32)
+        b, _ = V.search(R.decoding_fns, hp, Ps, src, K, torch.float32, store_bf16=True)
         assert rt.decode_hypothesis(a["seq"], hp) == rt.decode_hypothesis(b["seq"], hp), K
-    tgt = R.fixture_targets(hp)
+    tgt = V.ragged(R.TARGET_LENGTHS, hp.tgt_vocab.size(), R.TARGET_SEED)
     s64 = R.score(hp, f["Pn"], src, tgt)
     sbf = R.score(hp, f["Pn"], src, tgt, torch.float32, store_bf16=True)
     floor = float(np.abs(sbf / s64 - 1).max())

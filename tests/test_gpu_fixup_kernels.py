@@ -18,6 +18,7 @@ pytestmark = pytest.mark.gpu
 from tests.util_gpu import eng  # noqa: E402
 from tests import parity as P  # noqa: E402
 from tests import fixup_ref as R  # noqa: E402
+from tests import variant_ref as V  # noqa: E402
 
 F32 = torch.float32
 ENTRY = {"bf16": "zk_fixup_residual", "fp32": "zk_f32_fixup_residual"}
@@ -38,7 +39,7 @@ class Operands(object):
 
     def __init__(self, name, form, x):
         cs = R.CASES[name]
-        st = R.STORAGE[form]
+        st = V.STORAGE[form]
         rows, H, ld = cs["rows"], cs["H"], cs["ld"]
         null = cs.get("null", ())
         off = 8 if ld > H else 0                                  # a column slice that does not start the row
@@ -67,12 +68,12 @@ class Operands(object):
 
 
 def _assert_case(ops, ref, form, what):
-    bx, bxs = R.residual_bound(ref, R.STORAGE[form])
+    bx, bxs = R.residual_bound(ref, V.STORAGE[form])
     r = 0.0
     if ops.x_out is not None:
-        r = max(r, R.within(ops.x_out.value().double().numpy(), ref["x_out"], bx, what + " x_out"))
+        r = max(r, V.assert_within(ops.x_out.value().double().numpy(), ref["x_out"], bx, what + " x_out"))
     if ops.xs is not None:
-        r = max(r, R.within(ops.xs.value().double().numpy(), ref["xs"], bxs, what + " xs_out"))
+        r = max(r, V.assert_within(ops.xs.value().double().numpy(), ref["xs"], bxs, what + " xs_out"))
     return r
 
 
@@ -105,7 +106,7 @@ FFN_RUNS = [(name, form, inplace) for name in R.FFN_CASES for form in ("bf16", "
 def test_relu_shift_case(name, form, inplace):
     e = eng()
     cs = R.FFN_CASES[name]
-    st = R.STORAGE[form]
+    st = V.STORAGE[form]
     x = R.case_inputs(name, form, ffn=True)
     ref = R.case_reference(name, x, form, ffn=True)
     off = 8 if cs["ld"] > cs["H"] else 0
@@ -118,7 +119,7 @@ def test_relu_shift_case(name, form, inplace):
     if not inplace:
         h.check_intact(FFN_ENTRY[form] + " h")
     out.check_guard(FFN_ENTRY[form] + " output")
-    ratio = R.within(out.value().double().numpy(), ref["out"], R.relu_shift_bound(ref, st), "%s %s" % (name, form))
+    ratio = V.assert_within(out.value().double().numpy(), ref["out"], R.relu_shift_bound(ref, st), "%s %s" % (name, form))
     print("%s %s: largest |err| / bound %.3f" % (name, form, ratio))
 
 
@@ -128,7 +129,7 @@ def test_a_replayed_graph_reads_the_new_scalars(form):
     2.0) and the graph replayed: the outputs are those of the NEW values (the reference with the old ones is the planted
     defect host_baked, which tests/test_fixup_host.py shows to leave the bound)."""
     e = eng()
-    st = R.STORAGE[form]
+    st = V.STORAGE[form]
     x = R.case_inputs("strided", form)
     fx = R.case_inputs("strided", form, ffn=True)
     cs = R.CASES["strided"]
@@ -147,7 +148,7 @@ def test_a_replayed_graph_reads_the_new_scalars(form):
             e.graph_launch(g)
             torch.cuda.synchronize()
             _assert_case(ops, R.case_reference("strided", x, form), form, "first replay")
-            R.within(hout.value().double().numpy(), R.case_reference("strided", fx, form, ffn=True)["out"],
+            V.assert_within(hout.value().double().numpy(), R.case_reference("strided", fx, form, ffn=True)["out"],
                      R.relu_shift_bound(R.case_reference("strided", fx, form, ffn=True), st), "first replay, relu_shift")
             for t, v in zip((ops.a, ops.o, ops.b), R.STALE):      # "a weight reload": new values at the same addresses
                 t.fill_(v)
@@ -159,7 +160,7 @@ def test_a_replayed_graph_reads_the_new_scalars(form):
     ref = R.residual(n(x["x"]), n(x["y"]), *R.STALE, st=st)
     _assert_case(ops, ref, form, "replay with new scalars")
     fref = R.relu_shift(n(fx["h"]), R.STALE[1])
-    R.within(hout.value().double().numpy(), fref["out"], R.relu_shift_bound(fref, st), "replay with new scalars, relu_shift")
+    V.assert_within(hout.value().double().numpy(), fref["out"], R.relu_shift_bound(fref, st), "replay with new scalars, relu_shift")
     ops.check("replayed " + ENTRY[form])
     h.check_intact("replayed relu_shift h")
     hout.check_guard("replayed relu_shift output")
@@ -168,7 +169,7 @@ def test_a_replayed_graph_reads_the_new_scalars(form):
 @pytest.mark.parametrize("form", ["bf16", "fp32"])
 def test_a_misaligned_width_is_refused_without_a_launch(form):
     e = eng()
-    st = R.STORAGE[form]
+    st = V.STORAGE[form]
     rows, H = 3, 132                      # a multiple of 4, not of 8
     g = torch.Generator().manual_seed(2)
     x, y = G(rows, H, 136, F32, torch.randn(rows, H, generator=g)), G(rows, H, 136, st, torch.randn(rows, H, generator=g))

@@ -16,16 +16,15 @@ bf16 mode: compared as tests/test_gpu_rela_model.py::test_bf16_mode compares (ou
 of every sentence against the fp32 reference; the reference under ref_torch's bf16 storage model meets the same condition
 on the CPU).
 """
-import copy
-
 import numpy as np
 import pytest
-import torch
 
 pytestmark = pytest.mark.gpu
 
 from oracle import ref_torch as rt  # noqa: E402
 from tests import fixup_ref as R  # noqa: E402
+from tests import variant_gpu as G  # noqa: E402
+from tests import variant_ref as V  # noqa: E402
 from tests.common import make_hp  # noqa: E402
 from zero_amd.models import model as registry, load_all  # noqa: E402
 from zero_amd.models._factory import get_core, reset_cores  # noqa: E402
@@ -37,63 +36,28 @@ MODEL = "transformer_fixup"
 @pytest.fixture(scope="module")
 def fx():
     hp = make_hp(MODEL, search_mode="cache")
-    src = R.fixture_source(hp)
+    src = V.ragged(R.FIXTURE_LENGTHS, hp.src_vocab.size(), R.SOURCE_SEED)
     f = R.make_fixture(hp, src, R.FIXTURE_SEED)
     print("fixture: smallest candidate gap %.3e, largest fp32 - float64 score difference %.3e (x %.0f)"
           % (f["gap"], f["err"], f["gap"] / f["err"]))
-    f.update(hp=hp, src=src, refs={})
+    f.update(hp=hp, src=src, ref=G.Reference(R.decoding_fns, hp, f["Pn"], src))
     return f
-
-
-def _hp(fx, K, dtype, **kw):
-    hp = copy.copy(fx["hp"])
-    hp.beam_size, hp.decode_dtype, hp.search_mode = K, dtype, "cache"
-    for k, v in kw.items():
-        setattr(hp, k, v)
-    return hp
-
-
-def _reference(fx, K, Pn=None, src=None, key=None):
-    """rt.beam_search with the restated model (fp32); computed once per key and left unchanged."""
-    if key is not None and key in fx["refs"]:
-        return fx["refs"][key]
-    ref, _ = R.search(fx["hp"], fx["Pn"] if Pn is None else Pn, fx["src"] if src is None else src, K, torch.float32)
-    if key is not None:
-        fx["refs"][key] = ref
-    return ref
-
-
-def _decode(hp, Pn, src):
-    from zero_amd.main import tower_infer_graph
-    reset_cores()
-    core = get_core(hp, MODEL, Pn)
-    seqs, scores = tower_infer_graph({"source": src}, registry.get_model(MODEL), hp)
-    return np.asarray(seqs), np.asarray(scores), core
-
-
-def _assert_exact(seqs, scores, ref):
-    n = min(seqs.shape[2], ref["seq"].shape[2])
-    assert np.array_equal(seqs[:, :, :n], ref["seq"][:, :, :n]), (seqs, ref["seq"])
-    assert not seqs[:, :, n:].any() and not ref["seq"][:, :, n:].any()
-    fin = ref["score"] > -1e30
-    print("largest score difference %.3e" % np.abs(scores - ref["score"])[fin].max())
-    assert np.allclose(scores[fin], ref["score"][fin], rtol=1e-5, atol=1e-6), np.abs(scores - ref["score"])[fin].max()
 
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_fp32_mode_is_token_exact(fx, K):
-    ref = _reference(fx, K, key=("plain", K))
-    seqs, scores, _ = _decode(_hp(fx, K, "float32"), fx["Pn"], fx["src"])
-    _assert_exact(seqs, scores, ref)
+    ref = fx["ref"](K, key=("plain", K))
+    seqs, scores, _ = G.decode(G.beam_hp(fx["hp"], K, "float32"), MODEL, fx["Pn"], fx["src"])
+    G.assert_exact(seqs, scores, ref)
 
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_bf16_mode(fx, K):
     from zero_amd.search import decode_hypothesis
-    Pn = R.sharpen(fx["Pn"])
-    ref = _reference(fx, K, Pn=Pn, key=("sharp", K))
-    hp = _hp(fx, K, "bfloat16")
-    seqs, scores, core = _decode(hp, Pn, fx["src"])
+    Pn = V.sharpen(fx["hp"], fx["Pn"])
+    ref = fx["ref"](K, Pn=Pn, key=("sharp", K))
+    hp = G.beam_hp(fx["hp"], K, "bfloat16")
+    seqs, scores, core = G.decode(hp, MODEL, Pn, fx["src"])
     assert core.__dict__.get("_decode_step_launches", 0) > 0           # the step ran from captured graphs
     hyp, hyp_ref = decode_hypothesis(seqs, hp), rt.decode_hypothesis(ref["seq"], hp)
     print("K=%d: top score diff %.3e, launches per step %d" % (K, np.abs(scores[:, 0] - ref["score"][:, 0]).max(),
@@ -104,33 +68,15 @@ def test_bf16_mode(fx, K):
 def test_fp32_source_padding_changes_nothing(fx, monkeypatch):
     """ZERO_HIP_DECODE_PAD_LEN = 1 (14 source positions) and = 8 (16): the masked keys contribute exact zeros, in the
     encoder and in every cross-attention, so tokens AND scores are identical."""
-    out = []
-    for pad in ("1", "8"):
-        monkeypatch.setenv("ZERO_HIP_DECODE_PAD_LEN", pad)
-        seqs, scores, _ = _decode(_hp(fx, 4, "float32"), fx["Pn"], fx["src"])
-        out.append((seqs, scores))
-    n = min(out[0][0].shape[2], out[1][0].shape[2])
-    assert np.array_equal(out[0][0][:, :, :n], out[1][0][:, :, :n])
-    assert not out[0][0][:, :, n:].any() and not out[1][0][:, :, n:].any()
-    assert np.array_equal(out[0][1], out[1][1])
+    G.assert_padding_changes_nothing(MODEL, G.beam_hp(fx["hp"], 4, "float32"), fx["Pn"], fx["src"], monkeypatch)
 
 
 def test_two_lanes_equal_one_lane(fx):
     from zero_amd.evalu import decode_many
-    from zero_amd.search import beam_search
-    import threading
-    hp = _hp(fx, 4, "bfloat16")
-    Pn = R.sharpen(fx["Pn"])
-    reset_cores(); get_core(hp, MODEL, Pn)
-    batches = [fx["src"], R.fixture_source(hp, (11, 14, 7, 9), seed=6)]
-    graph = registry.get_model(MODEL)
-    tl = threading.local()
-
-    def work(s_):
-        if not hasattr(tl, "fns"):
-            tl.fns = graph.infer_fn(hp)
-        out = beam_search({"source": s_}, tl.fns[0], tl.fns[1], hp)
-        return np.asarray(out["seq"]).copy(), np.asarray(out["score"]).copy(), out["steps"]
+    hp = G.beam_hp(fx["hp"], 4, "bfloat16")
+    reset_cores(); get_core(hp, MODEL, V.sharpen(fx["hp"], fx["Pn"]))
+    batches = [fx["src"], V.ragged((11, 14, 7, 9), hp.src_vocab.size(), 6)]
+    work = G.lane_worker(MODEL, hp)
     one = [decode_many([b], work, streams=1)[0] for b in batches]          # one at a time
     two = decode_many(batches, work, streams=2)
     assert not np.array_equal(one[0][0], one[1][0])
@@ -143,8 +89,8 @@ def test_reloaded_weights_change_the_next_batch(fx, dtype):
     """The scalars are read on the device: after store.load() of a model that differs ONLY in its offsets and scales, the
     live core -- its step graphs adopted from the first batch -- decodes what a fresh core with those weights decodes."""
     from zero_amd import search
-    hp = _hp(fx, 4, dtype)
-    Pa = R.sharpen(fx["Pn"])
+    hp = G.beam_hp(fx["hp"], 4, dtype)
+    Pa = V.sharpen(fx["hp"], fx["Pn"])
     Pb = dict(Pa)
     rng = np.random.default_rng(77)
     for n in Pb:
@@ -174,8 +120,8 @@ def test_score_fn_matches_the_reference(fx):
     re-measures it): 4.966e-04, so 1.99e-03 is allowed (the device sums in another order than the storage model; 4 x is the
     margin this project gives such floors), below the 5e-3 tests/test_gpu_model.py::test_score_fn_matches_oracle grants
     `transformer`."""
-    hp = _hp(fx, 4, "bfloat16")
-    tgt = R.fixture_targets(hp)
+    hp = G.beam_hp(fx["hp"], 4, "bfloat16")
+    tgt = V.ragged(R.TARGET_LENGTHS, hp.tgt_vocab.size(), R.TARGET_SEED)
     want = R.score(hp, fx["Pn"], fx["src"], tgt)
     reset_cores()
     out = registry.get_model(MODEL).score_fn({"source": fx["src"], "target": tgt}, hp, initializer=fx["Pn"])

@@ -16,18 +16,17 @@ fp32 mode: every hypothesis of every beam token-equal, scores within rtol 1e-5 /
 bf16 mode: compared as tests/test_gpu_model.py::test_beam_search_token_ids compares (output distribution sharpened x 6, best
 hypothesis of every sentence against the fp32 reference).
 """
-import copy
-
 import numpy as np
 import pytest
-import torch
 
 pytestmark = pytest.mark.gpu
 
 from oracle import ref_torch as rt  # noqa: E402
 from tests import rela_ref as R  # noqa: E402
+from tests import variant_gpu as G  # noqa: E402
+from tests import variant_ref as V  # noqa: E402
 from tests.common import make_hp  # noqa: E402
-from zero_amd.models import model as registry, load_all  # noqa: E402
+from zero_amd.models import load_all  # noqa: E402
 from zero_amd.models._factory import get_core, reset_cores  # noqa: E402
 
 load_all()
@@ -36,84 +35,31 @@ LENGTHS = (14, 5, 9, 11)
 SEED = 49
 
 
-def _source(hp, lengths=LENGTHS, seed=5, width=None):
-    rng = np.random.default_rng(seed)
-    src = np.zeros((len(lengths), width or max(lengths)), dtype=np.int64)
-    for b, n in enumerate(lengths):
-        src[b, :n - 1] = rng.integers(3, hp.src_vocab.size(), n - 1)
-        src[b, n - 1] = 2
-    return src
-
-
 @pytest.fixture(scope="module")
 def fx():
     hp = make_hp(MODEL, search_mode="cache")
-    src = _source(hp)
+    src = V.ragged(LENGTHS, hp.src_vocab.size(), 5)
     f = R.make_fixture(hp, src, SEED)
     print("fixture: smallest candidate gap %.3e, largest fp32 - float64 score difference %.3e (x %.0f)"
           % (f["gap"], f["err"], f["gap"] / f["err"]))
-    f.update(hp=hp, src=src, refs={})
+    f.update(hp=hp, src=src, ref=G.Reference(R.decoding_fns, hp, f["Pn"], src))
     return f
-
-
-def _hp(fx, K, dtype, **kw):
-    hp = copy.copy(fx["hp"])
-    hp.beam_size, hp.decode_dtype, hp.search_mode = K, dtype, "cache"
-    for k, v in kw.items():
-        setattr(hp, k, v)
-    return hp
-
-
-def _sharp(Pn):
-    """The output distribution sharpened so that bf16 noise cannot flip near-ties of a random model."""
-    Pn = dict(Pn)
-    Pn["tgt_embedding"] = (Pn["tgt_embedding"] * 6.0).astype(np.float32)
-    return Pn
-
-
-def _reference(fx, K, Pn=None, src=None, key=None):
-    """rt.beam_search with the restated decoder; computed once per key and left unchanged."""
-    if key is not None and key in fx["refs"]:
-        return fx["refs"][key]
-    hp = _hp(fx, K, "float32")
-    enc, dec = R.decoding_fns(hp, rt.to_torch(fx["Pn"] if Pn is None else Pn))
-    ref = rt.beam_search({"source": torch.tensor(fx["src"] if src is None else src)}, enc, dec, hp)
-    if key is not None:
-        fx["refs"][key] = ref
-    return ref
-
-
-def _decode(hp, Pn, src, model=MODEL):
-    from zero_amd.main import tower_infer_graph
-    reset_cores()
-    core = get_core(hp, model, Pn)
-    seqs, scores = tower_infer_graph({"source": src}, registry.get_model(model), hp)
-    return np.asarray(seqs), np.asarray(scores), core
-
-
-def _assert_exact(seqs, scores, ref):
-    n = min(seqs.shape[2], ref["seq"].shape[2])
-    assert np.array_equal(seqs[:, :, :n], ref["seq"][:, :, :n]), (seqs, ref["seq"])
-    assert not seqs[:, :, n:].any() and not ref["seq"][:, :, n:].any()
-    fin = ref["score"] > -1e30
-    print("largest score difference %.3e" % np.abs(scores - ref["score"])[fin].max())
-    assert np.allclose(scores[fin], ref["score"][fin], rtol=1e-5, atol=1e-6), np.abs(scores - ref["score"])[fin].max()
 
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_fp32_mode_is_token_exact(fx, K):
-    ref = _reference(fx, K, key=("plain", K))
-    seqs, scores, _ = _decode(_hp(fx, K, "float32"), fx["Pn"], fx["src"])
-    _assert_exact(seqs, scores, ref)
+    ref = fx["ref"](K, key=("plain", K))
+    seqs, scores, _ = G.decode(G.beam_hp(fx["hp"], K, "float32"), MODEL, fx["Pn"], fx["src"])
+    G.assert_exact(seqs, scores, ref)
 
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_bf16_mode(fx, K):
     from zero_amd.search import decode_hypothesis
-    Pn = _sharp(fx["Pn"])
-    ref = _reference(fx, K, Pn=Pn, key=("sharp", K))
-    hp = _hp(fx, K, "bfloat16")
-    seqs, scores, core = _decode(hp, Pn, fx["src"])
+    Pn = V.sharpen(fx["hp"], fx["Pn"])
+    ref = fx["ref"](K, Pn=Pn, key=("sharp", K))
+    hp = G.beam_hp(fx["hp"], K, "bfloat16")
+    seqs, scores, core = G.decode(hp, MODEL, Pn, fx["src"])
     assert core.__dict__.get("_decode_step_launches", 0) > 0           # the step ran from captured graphs
     hyp, hyp_ref = decode_hypothesis(seqs, hp), rt.decode_hypothesis(ref["seq"], hp)
     print("K=%d: top score diff %.3e" % (K, np.abs(scores[:, 0] - ref["score"][:, 0]).max()))
@@ -123,62 +69,25 @@ def test_bf16_mode(fx, K):
 def test_fp32_source_padding_changes_nothing(fx, monkeypatch):
     """ZERO_HIP_DECODE_PAD_LEN = 1 (14 source positions) and = 8 (16): the masked keys contribute exact zeros, in the
     encoder and in every cross-attention, so tokens AND scores are identical."""
-    out = []
-    for pad in ("1", "8"):
-        monkeypatch.setenv("ZERO_HIP_DECODE_PAD_LEN", pad)
-        seqs, scores, _ = _decode(_hp(fx, 4, "float32"), fx["Pn"], fx["src"])
-        out.append((seqs, scores))
-    n = min(out[0][0].shape[2], out[1][0].shape[2])
-    assert np.array_equal(out[0][0][:, :, :n], out[1][0][:, :, :n])
-    assert not out[0][0][:, :, n:].any() and not out[1][0][:, :, n:].any()
-    assert np.array_equal(out[0][1], out[1][1])
+    G.assert_padding_changes_nothing(MODEL, G.beam_hp(fx["hp"], 4, "float32"), fx["Pn"], fx["src"], monkeypatch)
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
 def test_step_graphs_are_reused_across_batches(fx, dtype):
     """Two batches of one shape with different content, one after the other on one engine: the second replays the first
     one's graphs and decodes what it decodes on a fresh engine."""
-    from zero_amd import search
-    hp = _hp(fx, 4, dtype)
-    Pn = _sharp(fx["Pn"])
-    first = fx["src"]
-    second = _source(hp, (11, 14, 7, 9), seed=6, width=first.shape[1])
-
-    def run(src):
-        enc, dec = registry.get_model(MODEL).infer_fn(hp)
-        out = search.beam_search({"source": src}, enc, dec, hp)
-        return np.asarray(out["seq"]).copy(), np.asarray(out["score"]).copy()
-    fresh = []
-    for src in (first, second):
-        reset_cores(); get_core(hp, MODEL, Pn)
-        fresh.append(run(src))
-    assert not np.array_equal(fresh[0][0], fresh[1][0])
-    reset_cores(); core = get_core(hp, MODEL, Pn)
-    a = run(first)
-    n0 = core.__dict__.get("_graph_adoptions", 0)
-    b = run(second)
-    assert core.__dict__.get("_graph_adoptions", 0) == n0 + 1
-    assert np.array_equal(a[0], fresh[0][0]) and np.array_equal(a[1], fresh[0][1])
-    assert np.array_equal(b[0], fresh[1][0]) and np.array_equal(b[1], fresh[1][1])
+    hp = G.beam_hp(fx["hp"], 4, dtype)
+    second = V.ragged((11, 14, 7, 9), hp.src_vocab.size(), 6, width=fx["src"].shape[1])
+    G.assert_graphs_reused(MODEL, hp, V.sharpen(fx["hp"], fx["Pn"]), fx["src"], second)
 
 
 def test_four_lanes_equal_one_lane(fx):
     from zero_amd.evalu import decode_many
-    from zero_amd.search import beam_search
-    import threading
-    hp = _hp(fx, 4, "bfloat16")
-    Pn = _sharp(fx["Pn"])
-    reset_cores(); get_core(hp, MODEL, Pn)
-    batches = [_source(hp, tuple(int(x) for x in np.random.default_rng(i).integers(5, 15, 3 + i % 2)), seed=10 + i)
+    hp = G.beam_hp(fx["hp"], 4, "bfloat16")
+    reset_cores(); get_core(hp, MODEL, V.sharpen(fx["hp"], fx["Pn"]))
+    batches = [V.ragged(tuple(int(x) for x in np.random.default_rng(i).integers(5, 15, 3 + i % 2)), hp.src_vocab.size(), 10 + i)
                for i in range(6)]
-    graph = registry.get_model(MODEL)
-    tl = threading.local()
-
-    def work(s_):
-        if not hasattr(tl, "fns"):
-            tl.fns = graph.infer_fn(hp)
-        out = beam_search({"source": s_}, tl.fns[0], tl.fns[1], hp)
-        return np.asarray(out["seq"]).copy(), np.asarray(out["score"]).copy(), out["steps"]
+    work = G.lane_worker(MODEL, hp)
     one = decode_many(batches, work, streams=1)
     four = decode_many(batches, work, streams=4)
     for i, (a, b) in enumerate(zip(one, four)):
@@ -187,7 +96,7 @@ def test_four_lanes_equal_one_lane(fx):
 
 def _small(H, name):
     hp = make_hp(MODEL, H=H, F=2 * H, heads=2, layers=1, Vs=40, Vt=36, search_mode="cache", scope_name=name)
-    return hp, R.init_params(hp, 3), _source(hp, (6, 3, 5), seed=2)
+    return hp, R.init_params(hp, 3), V.ragged((6, 3, 5), hp.src_vocab.size(), 2)
 
 
 def test_bf16_mode_names_its_limit_and_fp32_decodes_the_same_model():
@@ -198,10 +107,10 @@ def test_bf16_mode_names_its_limit_and_fp32_decodes_the_same_model():
     hp.beam_size = 2
     hp.decode_dtype = "bfloat16"
     with pytest.raises(ValueError, match="multiple of 8.*decode_dtype=float32"):
-        _decode(hp, Pn, src)
+        G.decode(hp, MODEL, Pn, src)
     for H, name in ((24, "t_rela_h24"), (16, "t_rela_h16")):
         hp, Pn, src = _small(H, name)
         hp.beam_size = 2
         hp.decode_dtype = "float32"
-        seqs, scores, _ = _decode(hp, Pn, src)
+        seqs, scores, _ = G.decode(hp, MODEL, Pn, src)
         assert seqs.shape[:2] == (3, 2) and np.isfinite(scores[:, 0]).all() and (seqs[:, 0] != 0).any()

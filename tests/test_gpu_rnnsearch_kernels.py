@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 from tests.util_gpu import eng  # noqa: E402
 from tests import parity as P  # noqa: E402
 from tests import rnnsearch_ref as R  # noqa: E402
+from tests import variant_ref as V  # noqa: E402
 from zero_amd.func import Mat  # noqa: E402
 from zero_amd.hip import ZeroHipError  # noqa: E402
 
@@ -90,8 +91,8 @@ def test_atr_step(form, Rn, H, variant):
     else:
         kw, ref = dict(with_idx=False, with_mask=False), R.atr_step(**dict(x, idx=None, mask=None))
     out, cp = _atr_run(x, form, **kw)
-    r1 = R.assert_within(out, ref["out"], R.atr_bound(ref, form), "%s R=%d H=%d %s state" % (form, Rn, H, variant))
-    r2 = R.assert_within(cp, ref["out"], R.atr_bound(ref, form, copy=True), "%s R=%d H=%d %s copy" % (form, Rn, H, variant))
+    r1 = V.assert_within(out, ref["out"], R.atr_bound(ref, form), "%s R=%d H=%d %s state" % (form, Rn, H, variant))
+    r2 = V.assert_within(cp, ref["out"], R.atr_bound(ref, form, copy=True), "%s R=%d H=%d %s copy" % (form, Rn, H, variant))
     print("%s R=%d H=%d %s: largest |err| / bound %.3f (state), %.3f (copy)" % (form, Rn, H, variant, r1, r2))
     if variant == "gather+mask":
         carried = x["mask"] == 0
@@ -107,7 +108,7 @@ def test_atr_step_keeps_the_state_in_fp32(form):
     out, _ = _atr_run(x, form)
     bound = R.atr_bound(ref, form)
     assert bound.max() < 2.0 ** -16                 # (a bf16 state is off by about 2^-9 f |h|)
-    R.assert_within(out, ref["out"], bound, "%s U = 0" % form)
+    V.assert_within(out, ref["out"], bound, "%s U = 0" % form)
 
 
 @pytest.mark.parametrize("form", ["bf16", "fp32"])
@@ -186,8 +187,8 @@ def test_add_attn(name, form):
     Ls = ADD_CASES[name]["Ls"]
     ref = R.add_attention(**x)
     ctx, cp = _add_run(x, form, Ls)
-    r1 = R.assert_within(ctx, ref["out"], R.add_bound(ref, form), "%s %s context" % (name, form))
-    r2 = R.assert_within(cp, ref["out"], R.add_bound(ref, form, copy=True), "%s %s copy" % (name, form))
+    r1 = V.assert_within(ctx, ref["out"], R.add_bound(ref, form), "%s %s context" % (name, form))
+    r2 = V.assert_within(cp, ref["out"], R.add_bound(ref, form, copy=True), "%s %s copy" % (name, form))
     print("%s %s: largest |err| / bound %.3f (fp32 context), %.3f (copy)" % (name, form, r1, r2))
     if name == "one_key":
         assert np.array_equal(ctx, x["mem"][:, 0]), "one key: the weight is 1, the context the memory row"
@@ -204,7 +205,7 @@ def test_add_attn_tanh_saturates(form):
     assert np.isfinite(ctx).all()
     with np.errstate(over="ignore"):
         ref = R.add_attention(**x)
-    R.assert_within(ctx, ref["out"], R.add_bound(ref, form), "%s saturated" % form)
+    V.assert_within(ctx, ref["out"], R.add_bound(ref, form), "%s saturated" % form)
 
 
 def test_bf16_forms_refuse_sizes_that_are_not_multiples_of_8():

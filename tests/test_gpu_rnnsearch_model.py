@@ -10,17 +10,16 @@ reference token- and order-identical, the smallest candidate gap 34 x / 51 x the
 fp32 mode: every hypothesis of every beam token-equal, scores within rtol 1e-5 / atol 1e-6 (rnnsearch_ref.score_tol).
 bf16 mode: output distribution sharpened x 6, best hypothesis of every sentence against the fp32 reference.
 """
-import copy
-
 import numpy as np
 import pytest
-import torch
 
 pytestmark = pytest.mark.gpu
 
 from oracle import ref_torch as rt  # noqa: E402
 from tests import rnnsearch_ref as R  # noqa: E402
-from zero_amd.models import model as registry, load_all  # noqa: E402
+from tests import variant_gpu as G  # noqa: E402
+from tests import variant_ref as V  # noqa: E402
+from zero_amd.models import load_all  # noqa: E402
 from zero_amd.models._factory import get_core, reset_cores  # noqa: E402
 
 load_all()
@@ -31,51 +30,19 @@ MODEL = "rnnsearch"
 def fx(request):
     ca = request.param
     hp = R.fixture_hp(ca)
-    src = R.source(hp)
+    src = V.ragged(R.LENGTHS, hp.src_vocab.size(), 5)
     f = R.make_fixture(hp, src, R.SEEDS[ca])
     print("fixture caencoder=%s: smallest candidate gap %.3e, largest fp32 - float64 score difference %.3e (x %.0f), %.3f of "
           "the fp32 score tolerance" % (ca, f["gap"], f["err"], f["gap"] / f["err"], f["rel"]))
-    f.update(hp=hp, src=src, refs={}, tol=R.score_tol(f["rel"], f["err"]))
+    f.update(hp=hp, src=src, ref=G.Reference(R.decoding_fns, hp, f["Pn"], src), tol=R.score_tol(f["rel"], f["err"]))
     return f
-
-
-def _hp(fx, K, dtype, **kw):
-    hp = copy.copy(fx["hp"])
-    hp.beam_size, hp.decode_dtype, hp.search_mode = K, dtype, "cache"
-    for k, v in kw.items():
-        setattr(hp, k, v)
-    return hp
-
-
-def _reference(fx, K, Pn=None, key=None):
-    """rt.beam_search with the restated model in fp32; computed once per key and left unchanged."""
-    if key is not None and key in fx["refs"]:
-        return fx["refs"][key]
-    ref, _ = R.search(fx["hp"], fx["Pn"] if Pn is None else Pn, fx["src"], K, torch.float32)
-    if key is not None:
-        fx["refs"][key] = ref
-    return ref
-
-
-def _decode(hp, Pn, src):
-    from zero_amd.main import tower_infer_graph
-    reset_cores()
-    core = get_core(hp, MODEL, Pn)
-    seqs, scores = tower_infer_graph({"source": src}, registry.get_model(MODEL), hp)
-    return np.asarray(seqs), np.asarray(scores), core
-
-
-def _assert_tokens(seqs, ref_seq):
-    n = min(seqs.shape[2], ref_seq.shape[2])
-    assert np.array_equal(seqs[:, :, :n], ref_seq[:, :, :n]), (seqs, ref_seq)
-    assert not seqs[:, :, n:].any() and not ref_seq[:, :, n:].any()
 
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_fp32_mode_is_token_exact(fx, K):
-    ref = _reference(fx, K, key=("plain", K))
-    seqs, scores, _ = _decode(_hp(fx, K, "float32"), fx["Pn"], fx["src"])
-    _assert_tokens(seqs, ref["seq"])
+    ref = fx["ref"](K, key=("plain", K))
+    seqs, scores, _ = G.decode(G.beam_hp(fx["hp"], K, "float32"), MODEL, fx["Pn"], fx["src"])
+    G.assert_tokens(seqs, ref["seq"])
     fin = ref["score"] > -1e30
     rtol, atol = fx["tol"]
     print("K=%d: largest score difference %.3e" % (K, np.abs(scores - ref["score"])[fin].max()))
@@ -85,10 +52,10 @@ def test_fp32_mode_is_token_exact(fx, K):
 @pytest.mark.parametrize("K", [1, 4])
 def test_bf16_mode(fx, K):
     from zero_amd.search import decode_hypothesis
-    Pn = R.sharpen(fx["hp"], fx["Pn"])
-    ref = _reference(fx, K, Pn=Pn, key=("sharp", K))
-    hp = _hp(fx, K, "bfloat16")
-    seqs, scores, core = _decode(hp, Pn, fx["src"])
+    Pn = V.sharpen(fx["hp"], fx["Pn"])
+    ref = fx["ref"](K, Pn=Pn, key=("sharp", K))
+    hp = G.beam_hp(fx["hp"], K, "bfloat16")
+    seqs, scores, core = G.decode(hp, MODEL, Pn, fx["src"])
     assert core.__dict__.get("_decode_step_launches", 0) > 0           # the step ran from captured graphs
     print("K=%d: %d launches per captured step, top score diff %.3e"
           % (K, core._decode_step_launches, np.abs(scores[:, 0] - ref["score"][:, 0]).max()))
@@ -103,9 +70,9 @@ def test_fp32_source_padding(fx, monkeypatch):
     out = []
     for pad in ("1", "8"):
         monkeypatch.setenv("ZERO_HIP_DECODE_PAD_LEN", pad)
-        seqs, scores, _ = _decode(_hp(fx, 4, "float32"), fx["Pn"], fx["src"])
+        seqs, scores, _ = G.decode(G.beam_hp(fx["hp"], 4, "float32"), MODEL, fx["Pn"], fx["src"])
         out.append((seqs, scores))
-    _assert_tokens(out[0][0], out[1][0])
+    G.assert_tokens(out[0][0], out[1][0])
     fin = out[0][1] > -1e30
     rtol, atol = fx["tol"]
     print("largest score difference between the paddings %.3e" % np.abs(out[0][1] - out[1][1])[fin].max())
@@ -116,47 +83,18 @@ def test_fp32_source_padding(fx, monkeypatch):
 def test_step_graphs_are_reused_across_batches(fx, dtype):
     """Two batches of one shape with different content, one after the other on one engine: the second replays the first
     one's graphs and decodes what it decodes on a fresh engine."""
-    from zero_amd import search
-    hp = _hp(fx, 4, dtype)
-    Pn = R.sharpen(fx["hp"], fx["Pn"])
-    first = fx["src"]
-    second = R.source(hp, (11, 14, 7, 9), seed=6, width=first.shape[1])
-
-    def run(src):
-        enc, dec = registry.get_model(MODEL).infer_fn(hp)
-        out = search.beam_search({"source": src}, enc, dec, hp)
-        return np.asarray(out["seq"]).copy(), np.asarray(out["score"]).copy()
-    fresh = []
-    for src in (first, second):
-        reset_cores(); get_core(hp, MODEL, Pn)
-        fresh.append(run(src))
-    assert not np.array_equal(fresh[0][0], fresh[1][0])
-    reset_cores(); core = get_core(hp, MODEL, Pn)
-    a = run(first)
-    n0 = core.__dict__.get("_graph_adoptions", 0)
-    b = run(second)
-    assert core.__dict__.get("_graph_adoptions", 0) == n0 + 1
-    assert np.array_equal(a[0], fresh[0][0]) and np.array_equal(a[1], fresh[0][1])
-    assert np.array_equal(b[0], fresh[1][0]) and np.array_equal(b[1], fresh[1][1])
+    hp = G.beam_hp(fx["hp"], 4, dtype)
+    second = V.ragged((11, 14, 7, 9), hp.src_vocab.size(), 6, width=fx["src"].shape[1])
+    G.assert_graphs_reused(MODEL, hp, V.sharpen(fx["hp"], fx["Pn"]), fx["src"], second)
 
 
 def test_four_lanes_equal_one_lane(fx):
     from zero_amd.evalu import decode_many
-    from zero_amd.search import beam_search
-    import threading
-    hp = _hp(fx, 4, "bfloat16")
-    Pn = R.sharpen(fx["hp"], fx["Pn"])
-    reset_cores(); get_core(hp, MODEL, Pn)
-    batches = [R.source(hp, tuple(int(x) for x in np.random.default_rng(i).integers(5, 15, 3 + i % 2)), seed=10 + i)
+    hp = G.beam_hp(fx["hp"], 4, "bfloat16")
+    reset_cores(); get_core(hp, MODEL, V.sharpen(fx["hp"], fx["Pn"]))
+    batches = [V.ragged(tuple(int(x) for x in np.random.default_rng(i).integers(5, 15, 3 + i % 2)), hp.src_vocab.size(), 10 + i)
                for i in range(6)]
-    graph = registry.get_model(MODEL)
-    tl = threading.local()
-
-    def work(s_):
-        if not hasattr(tl, "fns"):
-            tl.fns = graph.infer_fn(hp)
-        out = beam_search({"source": s_}, tl.fns[0], tl.fns[1], hp)
-        return np.asarray(out["seq"]).copy(), np.asarray(out["score"]).copy(), out["steps"]
+    work = G.lane_worker(MODEL, hp)
     one = decode_many(batches, work, streams=1)
     four = decode_many(batches, work, streams=4)
     for i, (a, b) in enumerate(zip(one, four)):
@@ -167,11 +105,11 @@ def test_four_lanes_equal_one_lane(fx):
 def test_the_other_search_modes_equal_the_device_resident_one(fx, monkeypatch, mode):
     """The step without graphs (decoding_fn + state.reorder per step) and the graph step with the bookkeeping on the host
     decode what the device-resident search decodes: reorder() / bind_caches() of the ping-pong state serve all three."""
-    hp = _hp(fx, 4, "float32")
-    base = _decode(hp, fx["Pn"], fx["src"])
+    hp = G.beam_hp(fx["hp"], 4, "float32")
+    base = G.decode(hp, MODEL, fx["Pn"], fx["src"])
     monkeypatch.setenv("ZERO_HIP_DECODE_GRAPH" if mode == "eager" else "ZERO_HIP_DECODE_DEVICE_BOOK", "0")
-    seqs, scores, _ = _decode(hp, fx["Pn"], fx["src"])
-    _assert_tokens(seqs, base[0])
+    seqs, scores, _ = G.decode(hp, MODEL, fx["Pn"], fx["src"])
+    G.assert_tokens(seqs, base[0])
     fin = base[1] > -1e30
     assert np.allclose(scores[fin], base[1][fin], rtol=fx["tol"][0], atol=fx["tol"][1])
 
@@ -180,7 +118,7 @@ def _small(H, E, name, ca=True):
     from tests.common import make_hp
     hp = make_hp(MODEL, H=H, Vs=40, Vt=36, search_mode="cache", scope_name=name, cell="atr", caencoder=ca, layer_norm=False)
     hp.embed_size = E
-    return hp, R.init_params(hp, 3), R.source(hp, (6, 3, 5), seed=2)
+    return hp, R.init_params(hp, 3), V.ragged((6, 3, 5), hp.src_vocab.size(), 2)
 
 
 def test_bf16_mode_names_its_limit_and_fp32_decodes_the_same_model():
@@ -190,9 +128,9 @@ def test_bf16_mode_names_its_limit_and_fp32_decodes_the_same_model():
     hp.beam_size = 2
     hp.decode_dtype = "bfloat16"
     with pytest.raises(ValueError, match="multiples of 8.*decode_dtype=float32"):
-        _decode(hp, Pn, src)
+        G.decode(hp, MODEL, Pn, src)
     hp.decode_dtype = "float32"
-    seqs, scores, _ = _decode(hp, Pn, src)
+    seqs, scores, _ = G.decode(hp, MODEL, Pn, src)
     assert seqs.shape[:2] == (3, 2) and np.isfinite(scores[:, 0]).all() and (seqs[:, 0] != 0).any()
 
 

@@ -9,6 +9,7 @@ import torch
 
 from oracle import ref_torch as rt
 from tests import rnnsearch_ref as R
+from tests import variant_ref as V
 from tests.common import make_hp
 
 
@@ -133,18 +134,18 @@ def test_atr_reference_standin_and_defects(form):
     ref = R.atr_step(**x)
     for copy_ in (False, True):
         bound = R.atr_bound(ref, form, copy=copy_)
-        worst = R.assert_within(R.atr_standin(form=form, copy=copy_, **x), ref["out"], bound, "stand-in %s" % form)
+        worst = V.assert_within(R.atr_standin(form=form, copy=copy_, **x), ref["out"], bound, "stand-in %s" % form)
         assert worst <= 1.0
     carried = x["mask"] == 0
     assert (R.atr_bound(ref, form)[carried] == 0).all() and np.array_equal(ref["out"][carried], ref["h"][carried])
     for d in R.ATR_DEFECTS:
         bad = R.atr_step(defect=d, **x)["out"]
-        assert R.exceeds(bad, ref["out"], R.atr_bound(ref, form)), d          # (the fp32 state: what the next step reads)
+        assert V.exceeds(bad, ref["out"], R.atr_bound(ref, form)), d          # (the fp32 state: what the next step reads)
     # the zero state: q = b
     z = dict(x, h_prev=None, idx=None)
     ref0 = R.atr_step(**z)
     assert np.allclose(ref0["q"], x["b"][None, :]) and not ref0["h"].any()
-    R.assert_within(R.atr_standin(form=form, **z), ref0["out"], R.atr_bound(ref0, form), "stand-in, zero state")
+    V.assert_within(R.atr_standin(form=form, **z), ref0["out"], R.atr_bound(ref0, form), "stand-in, zero state")
 
 
 def test_atr_bound_catches_a_bf16_state_with_u_zero():
@@ -157,8 +158,8 @@ def test_atr_bound_catches_a_bf16_state_with_u_zero():
     ref = R.atr_step(**x)
     for form in ("bf16", "fp32"):
         bound = R.atr_bound(ref, form)
-        R.assert_within(R.atr_standin(form=form, **x), ref["out"], bound, "stand-in, U = 0")
-        assert R.exceeds(R.atr_step(defect="bf16_state", **x)["out"], ref["out"], bound)
+        V.assert_within(R.atr_standin(form=form, **x), ref["out"], bound, "stand-in, U = 0")
+        assert V.exceeds(R.atr_step(defect="bf16_state", **x)["out"], ref["out"], bound)
 
 
 def _add_inputs(seed, R_=6, G=3, M=24, L=9, lengths=(9, 4), hot=True):
@@ -184,16 +185,16 @@ def test_add_attention_reference_standin_and_defects(form):
     for copy_ in (False, True):
         bound = R.add_bound(ref, form, copy=copy_)
         got = R.add_standin(x["qa"], x["pm"], x["mem"], x["v"], x["mask"], x["kv_group"], 9, form, copy=copy_)
-        assert R.assert_within(got, ref["out"], bound, "stand-in %s" % form) <= 1.0
+        assert V.assert_within(got, ref["out"], bound, "stand-in %s" % form) <= 1.0
     bound = R.add_bound(ref, form, copy=True)
     for d in R.ADD_DEFECTS:
         y = dict(x)
         if d == "extra_key":                          # keys 0 .. 7 exist, the ninth is there to be read by mistake
             y["mask"] = np.ones_like(x["mask"])
             good = R.add_attention(Ls=8, **y)
-            assert R.exceeds(R.add_attention(Ls=8, defect=d, **y)["out"], good["out"], R.add_bound(good, form, copy=True)), d
+            assert V.exceeds(R.add_attention(Ls=8, defect=d, **y)["out"], good["out"], R.add_bound(good, form, copy=True)), d
             continue
-        assert R.exceeds(R.add_attention(defect=d, **x)["out"], ref["out"], bound), d
+        assert V.exceeds(R.add_attention(defect=d, **x)["out"], ref["out"], bound), d
     # tanh saturates: huge arguments of both signs stay finite
     big = dict(x, qa=x["qa"] * 1e30)
     assert np.isfinite(R.add_attention(**big)["out"]).all()
@@ -206,7 +207,7 @@ def test_full_decoder_equals_the_cached_steps(ca):
     logits; the source's padding columns change nothing (the carry)."""
     hp = _tiny(caencoder=ca)
     P = rt.to_torch(R.init_params(hp, 2), dtype=torch.float64)
-    src = torch.as_tensor(R.source(hp, (6, 3, 5), seed=2))
+    src = torch.as_tensor(V.ragged((6, 3, 5), hp.src_vocab.size(), 2))
     tgt = torch.as_tensor(np.random.default_rng(3).integers(3, hp.tgt_vocab.size(), (3, 5)))
     enc, dec = R.decoding_fns(hp, P)
     state = enc(src)
@@ -226,7 +227,7 @@ def test_full_decoder_equals_the_cached_steps(ca):
 def test_model_fixture_margins(ca):
     """The measurements the GPU model tests rest on (recorded in tests/rnnsearch_ref.py), re-made on every CPU run."""
     hp = R.fixture_hp(ca)
-    f = R.make_fixture(hp, R.source(hp), R.SEEDS[ca])
+    f = R.make_fixture(hp, V.ragged(R.LENGTHS, hp.src_vocab.size(), 5), R.SEEDS[ca])
     print("caencoder=%s: gap %.3e err %.3e rel %.3f" % (ca, f["gap"], f["err"], f["rel"]))
     assert f["gap"] > 4 * f["err"]
     assert f["rel"] <= 0.25 and R.score_tol(f["rel"], f["err"]) == (R.RTOL, R.ATOL)
