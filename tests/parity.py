@@ -9,6 +9,9 @@ Three tools:
 ``assert_elementwise`` every element finite and within its own bound; nothing is excused.
 ``gemm_bound``         the float64 reference of a GEMM with its fused epilogue and the DERIVED bound per element.
 
+The row kernels of the training step (LayerNorm, cross entropy, column sums) have their references, derived bounds and CPU
+stand-ins at the end of this file (``ln_fwd_bound``, ``ln_bwd_bound``, ``ce_bound``, ``colsum_ref``, ``assert_exact``).
+
 The GEMM bound.  With bf16 operands every product a*b is exact in fp32, so a kernel that accumulates K products in
 fp32 in any order (MFMA blocks, split-K slab sums) is off by at most (K-1) roundings of partial sums, each at most
 2^-24 of the running magnitude, which never exceeds mag = |alpha| (|A| |B|) + |bias| + |res|; the epilogue (alpha,
@@ -360,4 +363,345 @@ def plant_attn_defects(ref, d, nh):
         neigh = ref.clone(); neigh[r, sl] = ref[r + 1, sl]
         stale = ref.clone(); stale[r, h * d + 8:h * d + 16] = float("nan")
         out.update({"zeroed" + tag: zeroed, "neighbour" + tag: neigh, "stale" + tag: stale})
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- row kernels
+# References and DERIVED bounds of the row kernels of zero_amd/csrc/zk_elem.hip (LayerNorm, cross entropy, column sums)
+# and, below them, what a correct kernel computes on the CPU (fp32 arithmetic, bf16 at the storage sites, torch's own
+# summation order) with the planted defects of tests/test_rowkernel_checker.py.
+#
+# Units.  One fp32 operation is off by at most 2^-24 of its result (half an ulp); every count below is charged
+# PER_TERM = 2^-23, twice that, as gemm_bound does.  A sum of n terms in ANY order (lanes, shuffles, LDS partials,
+# partial rows of a workspace) has n - 1 additions, each off by at most 2^-24 of a partial sum that never exceeds the sum
+# of the magnitudes: (n - 1) 2^-24 sum|terms|.  bf16 storage is off by at most 2^-8 of the stored value.
+C_LN = 8         # per-row operations of the LayerNorm kernels besides the H - 1 additions (counted in ln_*_bound)
+C_RED = 4        # per-term operations of a column reduction besides the rows - 1 additions (counted in ln_bwd_bound)
+RSQRT_ULP = 2.0  # rsqrtf: 2 ulp, the largest figure the CUDA / HIP math tables give for it
+# __expf / __logf: their error cannot be derived from this code base.  MEASURED on an MI355X over CE_CASES x ls of
+# tests/test_gpu_rowkernels_elementwise.py against the float64 reference (profiles/rowkernel_parity_constants.json):
+# the smallest c_exp the kernels need is C_EXP_MEASURED (the gradient at V = 70001 with label smoothing; ce alone needs
+# 0.63); the constant is twice that, rounded up to a power of two.  The margin covers other seeds.
+C_EXP_MEASURED = 1.33
+C_EXP = 4.0
+
+
+def _d(x):
+    return x.detach().to("cpu").double()
+
+
+def ratio(got, ref64, bound64):
+    """max |err| / bound (an element off its bound-0 reference, or a non-finite one, gives inf)."""
+    got, ref64, bound64 = _d(got).reshape(-1), _d(ref64).reshape(-1), _d(bound64).reshape(-1)
+    err = (got - ref64).abs()
+    r = torch.where(err == 0, torch.zeros_like(err), err / bound64.clamp_min(1e-300))
+    r = torch.where(torch.isfinite(got), r, torch.full_like(r, float("inf")))
+    return float(r.max()) if r.numel() else 0.0
+
+
+def assert_exact(got, ref64, what):
+    """A reduction of small integers: every summation order gives the same fp32 bits, the float64 sum."""
+    got, ref64 = _d(got), _d(ref64).reshape(got.shape)
+    if got.dim() == 1:
+        got, ref64 = got[None], ref64[None]
+    bad = ~(got == ref64)                                   # (NaN != anything)
+    n = int(bad.sum())
+    if n:
+        r, c = (int(v) for v in torch.nonzero(bad)[0])
+        raise AssertionError("%s: %d of %d elements outside their bound (0: an exact sum); first at (row %d, col %d): "
+                             "got %r ref %r" % (what, n, got.numel(), r, c, float(got[r, c]), float(ref64[r, c])))
+
+
+def ln_fwd_bound(x, y, scale, gamma, beta, eps, s_stored=None):
+    """zk_add_ln_fwd (zk_ln_dev.h add_ln_fwd_row): s = x + y * scale (bf16 when saved), out = gamma (s - mean) rstd +
+    beta.  x, y: the bf16 operands [rows, H] (y may be None), scale: what zk_dropout_mask gives for the seed and site
+    (None = no dropout), s_stored: the sum the KERNEL saved (None = the inference form).  A STAGED reference: returns
+    {"s", "mean", "rstd", "out"} -> (ref, bound), float64; "s" only with s_stored.
+
+    s.  fp32: y * scale (one rounding, of |y scale|), + x (one, of at most |x| + |y scale|), then bf16:
+        bound_s = 2^-8 |ref| + 2 PER_TERM (|x| + |y scale|);  without y the kernel stores x itself: bound 0.
+    The statistics are the kernel's own function of v, the values it normalises: the STORED s when it saves one
+    (zk_ln_dev.h:46-51), so the reference takes them from s_stored and e = 0 below; the fp32 sum otherwise, and the
+    reference takes the unrounded x + y scale, from which the kernel's v is off by e = 2 PER_TERM (|x| + |y scale|).
+    mean = fl(sum v) * fl(1 / H): H - 1 additions, the rounding of 1 / H, the product: H + 1 half-units of mean|v|.
+        bound_mean = (H + C_LN) PER_TERM mean|v| + mean(e)
+    var = sum (v - mean)^2 / H.  sum (v - m)^2 = H var + H (m - mu)^2, so the error of the mean enters squared:
+    dm2 = bound_mean^2; e enters as 2 sqrt(var mean(e^2)) + mean(e^2) (Cauchy-Schwarz).  Relative to the sum of the
+    (non-negative) terms: v - mean rounded (counts twice in the square), the square, H - 1 additions, 1 / H and the
+    product, + eps: H + 5 half-units.  rstd = rsqrtf(var + eps): half the relative error of var + eps, and RSQRT_ULP ulps:
+        rel_rstd = ((H + C_LN) PER_TERM + (dm2 + ...) / (var + eps)) / 2 + RSQRT_ULP PER_TERM;  bound_rstd = rstd rel_rstd
+    out = gamma (v - mean) rstd + beta, then bf16.  v - mean is off by bound_mean + e and its own rounding, rstd by
+    rel_rstd, two products and the addition of beta (of at most |gamma (v - mean) rstd| + |beta|) follow: on |v - mu|
+    that is (H + 6) / 2 + RSQRT_ULP + 4 <= H + 5 units for H >= 8, on mean|v| H + 1 half-units, on |beta| one:
+        bound_out = 2^-8 |ref| + (H + C_LN) PER_TERM (|gamma| rstd (|v - mu| + mean|v|) + |beta|)
+                    + |gamma| rstd (mean(e) + e + |v - mu| (dm2 + ...) / (2 (var + eps)))
+    (the last line is second order with a saved sum).  C_LN = 8 covers each of these counts and is not tuned."""
+    x = _d(x)
+    H = x.shape[1]
+    zero = torch.zeros_like(x)
+    if y is None:
+        s_ref, mag, s_bound = x, zero, zero
+    else:
+        ys = _d(y) * (1.0 if scale is None else _d(scale).reshape(x.shape))
+        s_ref, mag = x + ys, x.abs() + ys.abs()
+        s_bound = U_OUT[torch.bfloat16] * s_ref.abs() + 2 * PER_TERM * mag
+    res = {}
+    if s_stored is not None:
+        res["s"] = (s_ref, s_bound)
+        v, e = _d(s_stored), zero
+    else:
+        v, e = s_ref, 2 * PER_TERM * mag
+    g, b = _d(gamma)[None], _d(beta)[None]
+    mu, ma = v.mean(1), v.abs().mean(1)
+    lin = (H + C_LN) * PER_TERM
+    mean_bound = lin * ma + e.mean(1)
+    dv = v - mu[:, None]
+    var = (dv * dv).mean(1)
+    rstd = (var + eps) ** -0.5
+    e2 = (e * e).mean(1)
+    var_abs = mean_bound ** 2 + 2 * (var * e2).sqrt() + e2
+    rel = 0.5 * (lin + var_abs / (var + eps)) + RSQRT_ULP * PER_TERM
+    res["mean"] = (mu, mean_bound)
+    res["rstd"] = (rstd, rstd * rel)
+    out = g * dv * rstd[:, None] + b
+    gr = g.abs() * rstd[:, None]
+    res["out"] = (out, U_OUT[torch.bfloat16] * out.abs() + lin * (gr * (dv.abs() + ma[:, None]) + b.abs())
+                  + gr * (e.mean(1)[:, None] + e + dv.abs() * (0.5 * var_abs / (var + eps))[:, None]))
+    return res
+
+
+def ln_bwd_bound(dout, s, mean, rstd, gamma, scale=None, ds_stored=None, dy_stored=None):
+    """zk_add_ln_bwd (k_add_ln_bwd<>, k_add_ln_bwd_wide) + zk_add_ln_bwd_reduce.  mean and rstd are INPUTS: the
+    reference uses their fp32 values.  xh = (s - mean) rstd, g = dout gamma,
+        ds = rstd (g - mean(g) - xh mean(g xh))                                      (bf16)
+        dy = ds_stored * scale (bf16; the kernel forms it from the ds it STORED; only with dropout)
+        dgamma = sum_r dout xh, dbeta = sum_r dout, dbias_prev = sum_r dy_stored (ds_stored without dropout; zk_elem.hip:251-267)
+    ds.  xh: two roundings, g: one, g xh: one, the row sums: H - 1 additions, 1 / H and its product: two, xh mean(g xh):
+    one more, two subtractions and the product with rstd: at most H + 10 half-units on the largest of the three terms:
+        bound_ds = 2^-8 |ref| + (H + C_LN) PER_TERM rstd (|g| + mean|g| + |xh| mean|g xh|)
+    dy: one product, one bf16 rounding: (2^-8 + PER_TERM) |ref|; where scale is 0 the bound is 0.
+    Column sums: a term costs at most three roundings (xh: two, the product: one) and there are rows - 1 additions:
+        bound = (rows + C_RED) PER_TERM sum_r |term|;  a column of zero terms has bound 0."""
+    do, sv, g = _d(dout), _d(s), _d(gamma)[None]
+    rows, H = do.shape
+    mu, rs = _d(mean).reshape(rows, 1), _d(rstd).reshape(rows, 1)
+    xh, gg = (sv - mu) * rs, do * g
+    kd = dict(dim=1, keepdim=True)
+    ds = rs * (gg - gg.mean(**kd) - xh * (gg * xh).mean(**kd))
+    mag = rs.abs() * (gg.abs() + gg.abs().mean(**kd) + xh.abs() * (gg * xh).abs().mean(**kd))
+    res = {"ds": (ds, U_OUT[torch.bfloat16] * ds.abs() + (H + C_LN) * PER_TERM * mag)}
+    red = lambda t: (t.sum(0), (rows + C_RED) * PER_TERM * t.abs().sum(0))
+    res["dgamma"], res["dbeta"] = red(do * xh), red(do)
+    if ds_stored is not None:
+        src = _d(ds_stored)
+        if scale is not None:
+            dy = src * _d(scale).reshape(rows, H)
+            res["dy"] = (dy, (U_OUT[torch.bfloat16] + PER_TERM) * dy.abs())
+            src = _d(dy_stored)
+        res["dbias_prev"] = red(src)
+    return res
+
+
+def ce_constants(V, ls):
+    """p, q and the normaliser as zk_ce_fused forms them on the host, in fp32 (util.py:88-103)."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    if not 0.0 < ls < 1.0:
+        return 1.0, 0.0, 0.0
+    n = f(float(V - 1))
+    p = f(1.0) - f(ls)
+    q = f(ls) / n
+    norm = -(p * torch.log(p) + n * q * torch.log(q + f(1e-20)))
+    return float(p), float(q), float(norm)
+
+
+def ce_terms(z, ids, w, V, ld, ls):
+    """zk_ce_fused in float64: ce = lse - p z_gold - q (sum z - z_gold) - normaliser per row, dlogits = w (softmax -
+    soft) in [0, V), exactly 0 in the pad columns [V, ld) and in every row with w == 0.  z: the fp32 logits [T, >= V],
+    w: None = forward only.  Returns the references and the pieces of the bounds (see ce_bound)."""
+    z = _d(z)[:, :V]
+    T = z.shape[0]
+    ar, gold = torch.arange(T), ids.detach().to("cpu").long()
+    p, q, norm = ce_constants(V, ls)
+    lse = torch.logsumexp(z, 1)
+    zg, sabs = z[ar, gold], z.abs().sum(1)
+    t = {"ce": lse - p * zg - q * (z.sum(1) - zg) - norm,
+         "ce_exp": lse.abs() + p * zg.abs() + q * sabs, "ce_sum": (V + C_RED) * PER_TERM * q * sabs}
+    if w is not None:
+        sm = torch.exp(z - lse[:, None])
+        soft = torch.full_like(z, q)
+        soft[ar, gold] = p
+        wv = _d(w).reshape(T, 1)
+        t["dl"] = torch.zeros(T, ld, dtype=torch.float64)
+        t["dl_exp"] = torch.zeros(T, ld, dtype=torch.float64)
+        t["dl"][:, :V] = wv * (sm - soft)
+        t["dl_exp"][:, :V] = wv.abs() * (sm * (1 + (z - lse[:, None]).abs()) + soft)
+    return t
+
+
+def ce_bound(t, c_exp=None):
+    """The bounds on ce_terms' references: {"ce", "dl"} -> (ref, bound).
+        ce: c_exp PER_TERM (|lse| + p |z_gold| + q sum|z|) + (V + C_RED) PER_TERM q sum|z|
+            the second term is derived (sum z: V - 1 additions of at most sum|z|, times q, the subtraction of z_gold);
+        dl: 2^-8 |ref| + c_exp PER_TERM w (softmax (1 + |z - lse|) + soft)        (bf16; 0 where w or the column is 0)
+            an error d of the exponent z - lse moves softmax by softmax d, and d grows with |z - lse|.
+    c_exp stands for __expf, __logf and the fp32 sum of the exponentials: MEASURED (C_EXP above), not derived."""
+    c = C_EXP if c_exp is None else c_exp
+    res = {"ce": (t["ce"], c * PER_TERM * t["ce_exp"] + t["ce_sum"])}
+    if "dl" in t:
+        res["dl"] = (t["dl"], U_OUT[torch.bfloat16] * t["dl"].abs() + c * PER_TERM * t["dl_exp"])
+    return res
+
+
+def ce_c_exp_needed(t, ce, dl=None):
+    """The smallest c_exp with which ce (and dl) are inside ce_bound: for the measurement."""
+    need = lambda got, ref, fixed, shape: float(((( _d(got).reshape(ref.shape) - ref).abs() - fixed) /
+                                                 (PER_TERM * shape).clamp_min(1e-300)).clamp_min(0).max())
+    out = {"ce": need(ce, t["ce"], t["ce_sum"], t["ce_exp"])}
+    if dl is not None:
+        out["dl"] = need(dl, t["dl"], U_OUT[torch.bfloat16] * t["dl"].abs(), t["dl_exp"])
+    return out
+
+
+def colsum_ref(a, skip_L=0, scale=None, prev=None):
+    """out[c] = sum_r a[r, c] scale[r, c] over the rows with r % skip_L != 0 (skip_L = 0: every row) (+ prev: accumulate).
+    A term costs one rounding (the dropout scale), the sum rows - 1 additions, the accumulation one:
+        bound = (rows + C_RED) PER_TERM (sum_r |a scale| + |prev|)"""
+    t = _d(a)
+    rows = t.shape[0]
+    if scale is not None:
+        t = t * _d(scale).reshape(t.shape)
+    if skip_L > 0:
+        t = t.clone()
+        t[::skip_L] = 0
+    ref, mag = t.sum(0), t.abs().sum(0)
+    if prev is not None:
+        ref, mag = ref + _d(prev), mag + _d(prev).abs()
+    return ref, (rows + C_RED) * PER_TERM * mag
+
+
+def check_all(got, bounds, what, exact=()):
+    """Every output of ``got`` (name -> tensor or None) against ``bounds`` (name -> (ref, bound)), in the order of
+    ``bounds`` (the staged order); the names in ``exact`` bit for bit.  Returns name -> worst |err| / bound."""
+    worst = {}
+    for key, (ref, bound) in bounds.items():
+        if got.get(key) is None:
+            continue
+        if key in exact:
+            assert_exact(got[key], ref, "%s [%s]" % (what, key))
+        else:
+            assert_elementwise(got[key], ref, bound, "%s [%s]" % (what, key))
+        worst[key] = ratio(got[key], ref, bound)
+    return worst
+
+
+# ---- what a correct kernel computes (fp32, bf16 at the storage sites), and the planted defects
+def _f(x):
+    return x.detach().to("cpu").float()
+
+
+def ln_fwd_standin(x, y, scale, gamma, beta, eps, save, defect=None, at=(0, 0)):
+    """defect (at = (row, first column of an 8-column chunk)): "unbiased" (variance H / (H - 1), every row),
+    "short_stats" (statistics over the first H - 8 columns, every row), "eps_outside" (1 / (sqrt(var) + eps), row at[0]),
+    "neighbour" (row at[0] normalised with the statistics of the row below), "stale" (the chunk left at NaN),
+    "drop_ignored" (the chunk's dropout scale taken as 1)."""
+    r0, c0 = at
+    a = _f(x)
+    H = a.shape[1]
+    if y is not None:
+        sc = torch.ones_like(a) if scale is None else _f(scale).reshape(a.shape).clone()
+        if defect == "drop_ignored":
+            sc[r0, c0:c0 + 8] = 1.0
+        a = a + _f(y) * sc
+    s = a.to(torch.bfloat16) if save else None
+    v = s.float() if save else a
+    n = H - 8 if defect == "short_stats" else H
+    inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(n), dtype=torch.float32)
+    mean = v[:, :n].sum(1) * inv
+    dv = v - mean[:, None]
+    var = (dv[:, :n] * dv[:, :n]).sum(1) * inv
+    if defect == "unbiased":
+        var = var * (H / (H - 1.0))
+    rstd = torch.rsqrt(var + eps)
+    if defect == "eps_outside":
+        rstd[r0] = 1.0 / (var[r0].sqrt() + eps)
+    m_use, r_use = mean.clone(), rstd.clone()
+    if defect == "neighbour":
+        m_use[r0], r_use[r0] = mean[r0 + 1], rstd[r0 + 1]
+    out = (_f(gamma)[None] * (v - m_use[:, None]) * r_use[:, None] + _f(beta)[None]).to(torch.bfloat16)
+    if defect == "stale":
+        out[r0, c0:c0 + 8] = float("nan")
+    return {"s": s, "mean": mean if save else None, "rstd": rstd if save else None, "out": out}
+
+
+def ln_bwd_standin(dout, s, mean, rstd, gamma, scale=None, defect=None, at=0):
+    """defect: "drop_term" (xh mean(g xh) left out in row ``at``), "rows16_31" / "last_row" (those rows missing from the
+    three column sums), "dbp_noscale" (dbias_prev summed from ds: the dropout scale left out)."""
+    do, sv, g = _f(dout), _f(s), _f(gamma)[None]
+    rows, H = do.shape
+    mu, rs = _f(mean).reshape(rows, 1), _f(rstd).reshape(rows, 1)
+    inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(H), dtype=torch.float32)
+    xh, gg = (sv - mu) * rs, do * g
+    mg, mgx = gg.sum(1, keepdim=True) * inv, (gg * xh).sum(1, keepdim=True) * inv
+    t = xh * mgx
+    if defect == "drop_term":
+        t[at] = 0
+    ds = (rs * (gg - mg - t)).to(torch.bfloat16)
+    dy = (ds.float() * _f(scale).reshape(rows, H)).to(torch.bfloat16) if scale is not None else None
+    keep = torch.ones(rows, 1)
+    if defect == "rows16_31":
+        keep[16:32] = 0
+    if defect == "last_row":
+        keep[-1] = 0
+    src = ds.float() if (dy is None or defect == "dbp_noscale") else dy.float()
+    return {"ds": ds, "dy": dy, "dgamma": (do * xh * keep).sum(0), "dbeta": (do * keep).sum(0),
+            "dbias_prev": (src * keep).sum(0)}
+
+
+def ce_standin(z, ids, w, V, ld, ls, defect=None, at=0):
+    """defect: "no_q" (the smoothing mass left out off the gold column), "gold_shift" (gold + 1), "no_norm" (the
+    normaliser left out of ce), "lse_tail" (the last V % 4 columns left out of the log-sum-exp), "pad" (dlogits[at, V]
+    non-zero), "w0" (the rows with w == 0 get the gradient of w = 1)."""
+    zf = _f(z)[:, :V]
+    T = zf.shape[0]
+    ar, gold = torch.arange(T), ids.detach().to("cpu").long()
+    p, q, norm = ce_constants(V, ls)
+    zl = zf[:, :V & ~3] if defect == "lse_tail" else zf
+    if zl.shape[1] == 0:
+        lse = torch.full((T,), float("-inf"))
+    else:
+        m = zl.max(1).values
+        lse = m + torch.log(torch.exp(zl - m[:, None]).sum(1))
+    if defect == "gold_shift":
+        gold = (gold + 1) % V
+    zg = zf[ar, gold]
+    ce = lse - p * zg - q * (zf.sum(1) - zg) - (0.0 if defect == "no_norm" else norm)
+    if w is None:
+        return {"ce": ce, "dl": None}
+    soft = torch.full_like(zf, 0.0 if defect == "no_q" else q)
+    soft[ar, gold] = p
+    wv = _f(w).reshape(T).clone()
+    if defect == "w0":
+        wv[wv == 0] = 1.0
+    dl = torch.zeros(T, ld)
+    dl[:, :V] = wv[:, None] * (torch.exp(zf - lse[:, None]) - soft)
+    if defect == "pad":
+        dl[at, V] = 2.0 ** -10
+    return {"ce": ce, "dl": dl.to(torch.bfloat16)}
+
+
+def colsum_standin(a, skip_L=0, scale=None, prev=None, defect=None):
+    """defect: "skip_included" (the rows r % skip_L == 0 summed too), "last_chunk" (the last chunk of 32 rows missing),
+    "acc_ignored" (prev not added)."""
+    t = _f(a)
+    rows = t.shape[0]
+    if scale is not None:
+        t = t * _f(scale).reshape(t.shape)
+    keep = torch.ones(rows, 1)
+    if skip_L > 0 and defect != "skip_included":
+        keep[::skip_L] = 0
+    if defect == "last_chunk":
+        keep[(rows - 1) // 32 * 32:] = 0
+    out = (t * keep).sum(0)
+    if prev is not None and defect != "acc_ignored":
+        out = out + _f(prev)
     return out

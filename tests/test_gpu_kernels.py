@@ -576,6 +576,12 @@ def test_add_ln_fwd_bwd(H, drop):
     mu = sf.mean(-1, keepdim=True); var = ((sf - mu) ** 2).mean(-1, keepdim=True)
     ref = gf * (sf - mu) * torch.rsqrt(var + 1e-8) + bfp
     assert rel_err(out, ref) < 6e-3 and rel_err(s, sf) < 5e-3
+    # the fp32 statistics the backward (and tests/test_gpu_sync_ln.py) build on: against float64 of the STORED sum, with the
+    # derived bounds of tests/parity.py (the unbiased variance moves rstd by 1 / (2 H), a bf16 `out` does not show that)
+    from tests import parity
+    bounds = parity.ln_fwd_bound(x, y, msk if drop > 0 else None, gamma, beta, float(torch.tensor(1e-8)), s_stored=s)
+    parity.assert_elementwise(mean, *bounds["mean"], "add_ln_fwd mean")
+    parity.assert_elementwise(rstd, *bounds["rstd"], "add_ln_fwd rstd")
     dout = rand_bf(T, H, seed=3)
     ref.backward(dout.float())
     dsum = torch.zeros_like(out); dy = torch.zeros_like(out)
