@@ -7,7 +7,8 @@ A trace is ``{phase: [[entry point, [argument, ...]], ...], "graph_nodes": int}`
 prototype table parsed from include/zero_hip.h (``lib.protos``): a pointer as None (NULL) or "nonnull", everything else
 by value.  Phases: ``encode`` (encoding_fn), ``step0`` / ``reorder`` / ``step1`` (two eager decoding_fn calls at
 time = 0, 1 with an identity reorder of the caches between them); ``graph_nodes`` is ``core._decode_step_launches``
-after one whole beam search of the same batch.
+after one whole beam search of the same batch.  A scoring case has one phase, ``score`` (one score_fn call on a batch of
+5 sentence pairs of at most 9 and 11 tokens), and no ``graph_nodes``: a case names its own phases.
 
 Shapes: the smallest that take every arm -- H = 128, F = 256, 2 heads (head size 64: the fused attention launches
 apply), 2 + 2 layers, B = 5 sources of at most 9 tokens, beam 4.
@@ -40,16 +41,38 @@ def _cases():
         out["%s-float32-f32_fuse0" % m] = dict(models=(m,), dtype="float32", env={"ZERO_HIP_F32_FUSE": "0"})
     out["transformer-bfloat16-head32"] = dict(models=("transformer",), hp={"hidden_size": 96, "embed_size": 96, "num_heads": 3})
     out["ensemble-bfloat16"] = dict(models=("transformer", "transformer_aan"))
+    for dt in ("bfloat16", "float32"):           # both encoder forms, weights as tests/test_gpu_rnnsearch_model.py builds them
+        for tag, ca in (("", True), ("-caencoder0", False)):
+            out["rnnsearch-%s%s" % (dt, tag)] = dict(models=("rnnsearch",), dtype=dt,
+                                                    hp={"cell": "atr", "caencoder": ca, "layer_norm": False})
+    # score_fn: the fp32 scorer of every model that has one and both of its switches, the bf16 scorer of transformer_fixup
+    for m in ("transformer", "transformer_aan", "transformer_rpr", "transformer_fuse"):
+        out["score-%s-float32" % m] = dict(models=(m,), dtype="float32", score=True)
+    out["score-transformer_aan-float32-use_ffn"] = dict(models=("transformer_aan",), dtype="float32", score=True,
+                                                        hp={"use_ffn": True})
+    out["score-transformer-float32-f32_fuse0"] = dict(models=("transformer",), dtype="float32", score=True,
+                                                      env={"ZERO_HIP_F32_FUSE": "0"})
+    out["score-transformer_fixup-bfloat16"] = dict(models=("transformer_fixup",), score=True)
     return out
 
 
 CASES = _cases()
 
 
-def _source(hp, seed):
+def phases(name):
+    """The phases of case ``name``, in the order they are recorded."""
+    return ("score",) if CASES[name].get("score") else PHASES
+
+
+def summary(trace):
+    """'<launches per phase> launches[, graph of <n> nodes]' of a trace, for the print lines."""
+    text = " + ".join("%d" % len(v) for v in trace.values() if isinstance(v, list)) + " launches"
+    return text + (", graph of %d nodes" % trace["graph_nodes"] if "graph_nodes" in trace else "")
+
+
+def _batch(hp, seed):
     from tests.common import make_batch
-    src, _ = make_batch(np.random.default_rng(seed), 5, 9, 11, hp.src_vocab.size(), hp.tgt_vocab.size())
-    return src
+    return make_batch(np.random.default_rng(seed), 5, 9, 11, hp.src_vocab.size(), hp.tgt_vocab.size())
 
 
 def _params(hp, model, src, seed):
@@ -67,6 +90,9 @@ def _params(hp, model, src, seed):
     elif model == "transformer_fixup":
         from tests import fixup_ref
         Pn = dict(fixup_ref.init_params(hp, seed))
+    elif model == "rnnsearch":
+        from tests import rnnsearch_ref
+        Pn = rnnsearch_ref.init_params(hp, seed)
     else:
         Pn = perturb(rt.init_params(hp, model, seed=seed + 1), np.random.default_rng(seed))
     Pn["tgt_embedding"] = (Pn["tgt_embedding"] * 6.0).astype(np.float32)
@@ -132,13 +158,22 @@ def run_case(name, patch):
     models = case["models"]
     hps, Pns = [], []
     for i, m in enumerate(models):
-        hp = make_hp(m, beam_size=K, search_mode="cache", decode_dtype=case.get("dtype", "bfloat16"))
+        hp = make_hp(m, beam_size=K, search_mode="cache",
+                     **{"score_dtype" if case.get("score") else "decode_dtype": case.get("dtype", "bfloat16")})
         hp.override_from_dict(case.get("hp", {}))
         if i == 0:
-            src = _source(hp, 21)
+            src, tgt = _batch(hp, 21)
         hps.append(hp)
         Pns.append(_params(hp, m, src, 21 + i))
     reset_cores()
+    if case.get("score"):
+        get_core(hps[0], models[0], Pns[0])
+        rec = Recorder(patch)
+        with rec.phase("score"):
+            registry.get_model(models[0]).score_fn({"source": src, "target": tgt}, hps[0])
+        torch.cuda.synchronize()
+        reset_cores()
+        return dict(rec.phases)
     if len(models) == 1:
         core = get_core(hps[0], models[0], Pns[0])
         enc, dec = registry.get_model(models[0]).infer_fn(hps[0])
@@ -204,10 +239,12 @@ def dump(traces, path=GOLDEN):
     for name in sorted(traces):
         tr = traces[name]
         body = []
-        for ph in PHASES:
-            calls = ",\n".join("   " + json.dumps(c, separators=(",", ":")) for c in tr[ph])
-            body.append('  "%s": [\n%s\n  ]' % (ph, calls))
-        body.append('  "graph_nodes": %d' % tr["graph_nodes"])
+        for ph, launches in tr.items():
+            if isinstance(launches, list):
+                calls = ",\n".join("   " + json.dumps(c, separators=(",", ":")) for c in launches)
+                body.append('  "%s": [\n%s\n  ]' % (ph, calls))
+        if "graph_nodes" in tr:
+            body.append('  "graph_nodes": %d' % tr["graph_nodes"])
         lines.append('"%s": {\n%s\n }' % (name, ",\n".join(body)))
     with open(path, "w") as f:
         f.write("{\n" + ",\n".join(lines) + "\n}\n")

@@ -3,12 +3,13 @@
 
 For every case of tests/decode_trace.CASES -- the seven models in bf16 and in decode_dtype=float32, the forms selected by
 ZERO_HIP_DECODE_FUSE_ATT / ZERO_HIP_DECODE_FUSE_LN / ZERO_HIP_F32_FUSE / use_ffn, a head size of 32 (the launch-per-op
-path) and a two-member ensemble -- records every call of the library's entry points by encoding_fn, by two eager
-decoding_fn steps with a cache reorder between them, and the node count of the captured step graph of a whole beam
-search (tests/decode_trace.run_case).
+path), a two-member ensemble and rnnsearch with both encoder forms -- records every call of the library's entry points by
+encoding_fn, by two eager decoding_fn steps with a cache reorder between them, and the node count of the captured step
+graph of a whole beam search; for every scoring case -- the fp32 scorer of four models and of its switches, the bf16
+scorer of transformer_fixup -- every call by one score_fn (tests/decode_trace.run_case).
 
 Writes tests/golden/decode_launch_trace.json (or the path given as the first argument), which
-tests/test_gpu_decode_launch_trace.py must reproduce exactly: a host-side change of decoding that adds, drops, reorders
+tests/test_gpu_decode_launch_trace.py must reproduce exactly: a host-side change of decoding or scoring that adds, drops, reorders
 or re-parameterises a launch shows there.  A few seconds.
 """
 import os
@@ -28,8 +29,8 @@ def main():
     for name in DT.CASES:
         with pytest.MonkeyPatch.context() as patch:
             traces[name] = DT.run_case(name, patch)
-        print("%-40s %s, graph of %d nodes" % (name, " + ".join("%d" % len(traces[name][ph]) for ph in DT.PHASES),
-                                              traces[name]["graph_nodes"]), flush=True)
+        assert tuple(ph for ph in traces[name] if ph != "graph_nodes") == DT.phases(name)
+        print("%-40s %s" % (name, DT.summary(traces[name])), flush=True)
     DT.dump(traces, path)
     assert not any(DT.diff(traces[n], DT.load(path)[n]) for n in traces)
     print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))

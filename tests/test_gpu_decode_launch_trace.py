@@ -1,7 +1,8 @@
 """The host side of decoding issues the launches pinned in tests/golden/decode_launch_trace.json: the same entry points
 in the same order with the same scalar arguments and the same pointer pattern, for every model in both decode dtypes, for
-both forms of every decode switch, on the launch-per-op path and for an ensemble (tests/decode_trace.py; the file is
-written by tests/golden/make_decode_launch_trace.py).  The library itself runs: nothing is faked."""
+both forms of every decode switch, on the launch-per-op path, for an ensemble, for rnnsearch with both encoder forms and
+for the score_fn of the fp32 scorer and of transformer_fixup (tests/decode_trace.py; the file is written by
+tests/golden/make_decode_launch_trace.py).  The library itself runs: nothing is faked."""
 import pytest
 
 from tests import decode_trace as DT
@@ -21,8 +22,8 @@ def test_every_case_is_pinned(golden):
 @pytest.mark.parametrize("name", sorted(DT.CASES))
 def test_launch_trace(name, golden, monkeypatch):
     got = DT.run_case(name, monkeypatch)
-    print("%s: %s launches, graph of %d nodes" % (name, " + ".join("%d" % len(got[ph]) for ph in DT.PHASES),
-                                                 got["graph_nodes"]))
-    assert got["graph_nodes"] > 0
+    print("%s: %s" % (name, DT.summary(got)))
+    assert tuple(ph for ph in got if ph != "graph_nodes") == DT.phases(name)
+    assert DT.CASES[name].get("score") or got["graph_nodes"] > 0
     msgs = DT.diff(golden[name], got)
     assert not msgs, "\n".join(msgs[:20])

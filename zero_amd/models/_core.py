@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from zero_amd.func import Engine, Mat
+from zero_amd.models._fixup import Fixup, fixup_ops
 from zero_amd.variables import get_store
 
 BF16 = torch.bfloat16
@@ -671,9 +672,6 @@ class TransformerCore(object):
     def encode(self, batch, train, save):
         """transformer.py:15-84."""
         e, hp, H = self.eng, self.hp, self.H
-        if self.fixup:
-            from zero_amd.models._fixup import Fixup
-            return Fixup(self, False).encode(batch)
         B, Ls = batch["B"], batch["Ls"]
         Ts = B * Ls
         smask = batch.get("smask")
@@ -684,6 +682,8 @@ class TransformerCore(object):
         if not self.__dict__.get("_embeds_done"):      # (forward(): both embeddings went out as one launch)
             e.embed_fwd(batch["src"], self.store.s(self.src_emb), self.b("bias"), x, B, Ls, H,
                         drop_p=hp.dropout if train else 0.0, sid=9001)
+        if self.fixup:
+            return Fixup(self, fixup_ops(self, False)).encode(batch, x, smask)
         for l in range(hp.num_encoder_layer):
             pre = "encoder/layer_%d" % l
             x = self._self_attn_fwd(x, B, Ls, pre + "/self_attention", "e%d.sa" % l, smask, False, save,
@@ -703,13 +703,12 @@ class TransformerCore(object):
             tmask = e.buf("tmask", (B, Lt), F32)
             w = e.buf("tw", (B, Lt), F32)
             e.target_stats(batch["tgt"], tmask, w, B, Lt, want)
-        if self.fixup:
-            from zero_amd.models._fixup import Fixup
-            return Fixup(self, False).decode_train(batch, enc, smask), tmask, w
         x = e.mat("dec.x0", Tt, H)
         if not self.__dict__.get("_embeds_done"):
             e.embed_fwd(batch["tgt"], self.store.s(self.tgt_emb), self.b("bias"), x, B, Lt, H, shift=True,
                         drop_p=hp.dropout if train else 0.0, sid=9002)
+        if self.fixup:
+            return Fixup(self, fixup_ops(self, False)).decode_train(batch, x, enc, smask), tmask, w
         NE = hp.num_encoder_layer
         group_kv = self.group_wgrad and e.gemm_impl == 0
         if group_kv:

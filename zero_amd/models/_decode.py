@@ -37,6 +37,8 @@ from zero_amd.models._core import trim_columns
 from zero_amd.models._factory import get_core
 from zero_amd.models import _decode_f32 as _f32
 from zero_amd.models import _l0drop as _l0
+from zero_amd.models._fixup import Fixup, fixup_ops
+from zero_amd.models._ops import BF16_CACHES, F32_CACHES, Storage, ops_for  # noqa: F401  (the storages are named here too)
 from zero_amd.utils import dtype as zdtype
 
 F32 = torch.float32
@@ -173,15 +175,6 @@ class lanes_mode(object):
     def __exit__(self, *a):
         from zero_amd import hip
         hip.lib().raw("zk_dec_group")(self.prev)
-
-
-# Where a decode mode keeps its per-beam caches: the prefix of its engine buffers (a bf16 and an fp32 decode of one engine
-# never alias), the element type of the k / v caches and its size in bytes.  defer_aan: the step's input launch can take
-# over the beam reorder of the average-attention sums (zk_dec_embed: gather_src / gather_idx); the fp32 step has no such
-# launch and gathers at once.
-Storage = collections.namedtuple("Storage", "prefix dtype esz defer_aan")
-BF16_CACHES = Storage("dc.", torch.bfloat16, 2, True)
-F32_CACHES = Storage("dq.", F32, 4, False)
 
 
 class DecodeState(dict):
@@ -400,19 +393,27 @@ def check_member(model_name, i):
 
 
 # ---- start-up of a batch -------------------------------------------------------------------------------------------
-# What a decode mode brings to the start-up: its cache storage, its encoder (batch -> (encoder output Mat, source mask)),
-# its linear op (x, scope, out) and its factory of named matrices (name, rows, cols).
-Mode = collections.namedtuple("Mode", "storage encode linear mat")
+def pad_len():
+    """ZERO_HIP_DECODE_PAD_LEN: the multiple that source lengths and step counts are rounded up to."""
+    return max(1, int(os.environ.get("ZERO_HIP_DECODE_PAD_LEN", "8")))
 
 
-def _mode(core, hp):
-    if _f32.wanted(hp):
-        # the fp32 mode: fp32 masters, activations and caches through zk_f32_* (models/_decode_f32.py)
-        o = _f32._Ops(core)
-        return Mode(F32_CACHES, lambda batch: _f32.encode(core, hp, batch), o.linear, o.mat)
-    e = core.eng
-    return Mode(BF16_CACHES, lambda batch: core.encode(batch, False, False), core._linear,
-                lambda name, rows, cols: e.mat("dc." + name, rows, cols))
+def shape_batch(core, hp, source, max_steps):
+    """Upload ``source`` in its shape bucket -> (the batch of core.upload, the step count).  Shape bucketing for the
+    step-graph cache: the source is padded (id 0 = pad: masked in the encoder and in every cross-attention,
+    func.py:372-387) and the cache length rounded up to a multiple of pad_len(), so that length-sorted batches fall into few
+    shapes.  Masked keys contribute exact zeros to the softmax sums: hypotheses and scores are unchanged
+    (tests/test_gpu_model.py).  max_steps None: the longest source + decode_length + 2."""
+    pad = pad_len()
+    src = np.asarray(source.cpu() if torch.is_tensor(source) else source)
+    if pad > 1:
+        trimmed = trim_columns(src)
+        batch = core.upload(np.pad(trimmed, ((0, 0), (0, -trimmed.shape[1] % pad))), trim=False)
+    else:
+        batch = core.upload(src)
+    if max_steps is None:
+        max_steps = int((src != 0).sum(1).max()) + hp.decode_length + 2
+    return batch, -(-int(max_steps) // pad) * pad
 
 
 def _fused_weights(state, core, hp):
@@ -439,44 +440,36 @@ def _fused_weights(state, core, hp):
                          % (keys, H))
 
 
+def _encode_bf16(core, hp, batch, o):
+    return core.encode(batch, False, False)
+
+
 def build_state(core, hp, model_name, source, K, max_steps):
     """encoding_fn of both decode modes: source batch -> DecodeState."""
     e, H = core.eng, core.H
     f32 = _f32.wanted(hp)
-    pad = max(1, int(os.environ.get("ZERO_HIP_DECODE_PAD_LEN", "8")))
     # nothing here depends on the data: refuse before the encoder pass
     if f32:
         _f32.check_model(core)
     else:
         check_bf16_shape(model_name, core, hp, K)
-    mode = _mode(core, hp)
-    st = mode.storage
-    if pad > 1:
-        # Shape bucketing for the step-graph cache: the source is padded (id 0 = pad: masked in the encoder's
-        # self-attention and in every cross-attention, func.py:372-387) and the cache length rounded up to a multiple
-        # of `pad`, so that length-sorted batches fall into few shapes.  Masked keys contribute exact zeros to the
-        # softmax sums: hypotheses and scores are unchanged (tests/test_gpu_model.py).
-        src_np = trim_columns(np.asarray(source.cpu() if torch.is_tensor(source) else source))
-        src_np = np.pad(src_np, ((0, 0), (0, -src_np.shape[1] % pad)))
-        batch = core.upload(src_np, trim=False)
-        if max_steps is not None:
-            max_steps = -(-int(max_steps) // pad) * pad
-    else:
-        batch = core.upload(source)
+    # the ops of the mode and its encoder: fp32 masters, activations and caches through zk_f32_* (models/_decode_f32.py), or
+    # the training path's bf16 forward
+    o = ops_for(core, f32)
+    encode = _f32.encode if f32 else _encode_bf16
+    st = o.storage
+    batch, max_steps = shape_batch(core, hp, source, max_steps)
     B, Ls = batch["B"], batch["Ls"]
-    enc, smask = mode.encode(batch)
+    enc, smask = encode(core, hp, batch, o)
     kbias = None
     if core.l0drop:
         # the pruned memory, its mask and its length stand in for the encoder output from here on (models/_l0drop.py)
-        enc_keep, mask_keep, Ls, kbias = _l0.prune(core, enc, smask, B, Ls, pad, f32)
+        enc_keep, mask_keep, Ls, kbias = _l0.prune(core, enc, smask, B, Ls, pad_len(), o)
     else:
-        enc_keep = mode.mat("enc", B * Ls, H)
+        enc_keep = o.mat("enc", B * Ls, H)
         enc_keep.t.copy_(enc.t)
         mask_keep = e.buf(st.prefix + "smask", (B, Ls), F32)
         mask_keep.copy_(smask)
-    if max_steps is None:
-        src_len = (np.asarray(source.cpu() if torch.is_tensor(source) else source) != 0).sum(1)
-        max_steps = -(-(int(src_len.max()) + hp.decode_length + 2) // pad) * pad
     BK = B * K
     nl = hp.num_decoder_layer
     state = DecodeState()
@@ -487,9 +480,9 @@ def build_state(core, hp, model_name, source, K, max_steps):
         state["kbias"] = kbias
     for l in range(nl):
         p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
-        kv = mode.mat("%d.kv" % l, B * Ls, 2 * H)
-        mode.linear(enc_keep, p + "k_map", kv.cols_slice(0, H))
-        mode.linear(enc_keep, p + "v_map", kv.cols_slice(H, 2 * H))
+        kv = o.mat("%d.kv" % l, B * Ls, 2 * H)
+        o.linear(enc_keep, p + "k_map", kv.cols_slice(0, H))
+        o.linear(enc_keep, p + "v_map", kv.cols_slice(H, 2 * H))
         lay = {"mk": kv.cols_slice(0, H), "mv": kv.cols_slice(H, 2 * H)}
         if core.aan or core.fuse:
             lay["aan"] = None
@@ -605,6 +598,27 @@ def run_step(state, core, body, fast_capture):
         startup_end(state)
 
 
+def static_step(state, hp, logits_of, fast_capture, temperature, forbid_value, defer_aan=False):
+    """One whole decode step with every per-step value read from device memory: the bookkeeping head, the beam reorder of
+    the caches (indices chosen by the previous step), the step itself -- logits_of(state, time_dev) -> fp32 logits Mat --
+    and the fused log-softmax + length penalty + top-2K, through run_step.  A batch whose state carries no "_gkey" yet
+    first asks the cross-batch cache for the graphs of its shape."""
+    core = state["_core"]
+    e = core.eng
+    book = state.get("book")          # device-resident search bookkeeping (search._beam_search_device)
+    noise = hp.enable_noise_beam_search
+    if "_gkey" not in state:
+        adopt_graphs(state, book, temperature, forbid_value, noise)
+
+    def body():
+        time_dev = state["stepbuf"][0:1]
+        if book is not None:
+            e.lib.call("zk_beam_dev_prepare", *book, e.stream)
+        state.reorder(state["idx"], time_dev=time_dev, defer_aan=defer_aan)
+        search_tail(state, core, logits_of(state, time_dev), noise, temperature, forbid_value)
+    run_step(state, core, body, fast_capture)
+
+
 def make_infer_fns(params, model_name):
     hp = params
     check_search_mode(model_name, hp)
@@ -614,23 +628,8 @@ def make_infer_fns(params, model_name):
         return build_state(core, hp, model_name, source, hp.beam_size if beam_size is None else beam_size, max_steps)
 
     def step_static(state, temperature, forbid_value):
-        """One whole decode step with every per-step value read from device memory: beam reorder of
-        the caches (indices chosen by the previous step), the AAN decoder step, logits, fused
-        log-softmax + length penalty + top-2K."""
-        core = state["_core"]
-        e = core.eng
-        book = state.get("book")          # device-resident search bookkeeping (search._beam_search_device)
-        if "_gkey" not in state:
-            adopt_graphs(state, book, temperature, forbid_value, hp.enable_noise_beam_search)
-
-        def body():
-            sb = state["stepbuf"]
-            if book is not None:
-                e.lib.call("zk_beam_dev_prepare", *book, e.stream)
-            state.reorder(state["idx"], time_dev=sb[0:1], defer_aan=core.aan)
-            logits, _ = _step_cache(state["tok"], state, None, time_dev=sb[0:1])
-            search_tail(state, core, logits, hp.enable_noise_beam_search, temperature, forbid_value)
-        run_step(state, core, body, True)
+        static_step(state, hp, lambda st, time_dev: _step_cache(st["tok"], st, None, time_dev=time_dev)[0], True,
+                    temperature, forbid_value, defer_aan=state["_core"].aan)
 
     def _step_cache(target, state, time, time_dev=None):
         core = state["_core"]
@@ -642,8 +641,7 @@ def make_infer_fns(params, model_name):
             return _f32.step_cache(target, state, time, time_dev, hp)
         if core.fixup:
             # launch-per-op: projection, the softmax attention kernels, o_map, zk_fixup_residual (models/_fixup.py)
-            from zero_amd.models._fixup import Fixup
-            return Fixup(core, False).step(target, state, time, time_dev, hp)
+            return Fixup(core, fixup_ops(core, False)).step(target, state, time, time_dev, hp)
         fuse_ln = core.aan and os.environ.get("ZERO_HIP_DECODE_FUSE_LN", "1") != "0"
         # an attention sub-layer (projection, attention, the head's share of the output projection) as ONE launch per
         # (sentence, head) with the previous LayerNorm as its prologue (zk_dec_cross / zk_dec_self)

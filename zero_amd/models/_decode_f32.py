@@ -17,14 +17,9 @@ caches double-buffered and reordered by one row gather); buffers are named ``dq.
 the same engine never alias.
 """
 
-import os
-
-import torch
-
 from zero_amd.func import Mat
-from zero_amd.utils import dtype as zdtype
-
-F32 = torch.float32
+from zero_amd.models._fixup import Fixup, fixup_ops
+from zero_amd.models._ops import ops_for
 
 
 def wanted(hp):
@@ -37,132 +32,19 @@ def check_model(core):
         raise ZeroHipError("decode_dtype=float32 needs a head size that is a multiple of 4 (got %d)" % core.d)
 
 
-class _Ops(object):
-    """The op layer of the fp32 step: thin wrappers over the zk_f32_* entry points (include/zero_hip.h)."""
-
-    def __init__(self, core):
-        self.core, self.e = core, core.eng
-        self.lib = core.eng.lib
-        self.H, self.nh, self.d = core.H, core.nh, core.d
-        # round 6: row-local launches folded into their neighbours (ZERO_HIP_F32_FUSE=0: one launch per op, as in round 5 --
-        # the two forms are compared in tests/test_gpu_decode_f32.py)
-        self.fold = os.environ.get("ZERO_HIP_F32_FUSE", "1") != "0"
-
-    def mat(self, name, rows, cols):
-        return Mat(self.e.buf("dq." + name, (rows, cols), F32), rows, cols)
-
-    def w(self, name):
-        t = self.core.store.w(name)              # fp32 master (physical shape)
-        return Mat(t, t.shape[0], t.shape[1])
-
-    def embed(self, ids, rows, L, table, out, max_pos, pos0=0, pos_dev=None, zero_flag=None):
-        """func.py:341-369: out = table[ids] * sqrt(H) + bias + timing signal of the row's position (row % L + pos0, or
-        + *pos_dev); rows of a step whose ids are all pad (*zero_flag) are zero embeddings."""
-        st = self.core.store
-        tim = self.e.timing(max_pos + 1, self.H)
-        self.lib.call("zk_f32_embed", ids.data_ptr(), rows, L, st.w(table).data_ptr(), st.w("bias").data_ptr(),
-                      tim.data_ptr(), int(tim.shape[0]), out.ptr, self.H, float(self.H) ** 0.5, pos0, pos_dev,
-                      zero_flag.data_ptr() if zero_flag is not None else None, self.e.stream)
-        return out
-
-    def embed_step(self, ids, rows, out, max_pos, pos0, pos_dev, pad, aan=None, cat=None):
-        """embed() of one decode position with the all-pad test inside the launch; aan / cat: the first layer's average
-        attention from the embedded row (cache tensor, cat Mat) in the same launch."""
-        st = self.core.store
-        tim = self.e.timing(max_pos + 1, self.H)
-        self.lib.call("zk_f32_embed_step", ids.data_ptr(), rows, st.w(self.core.tgt_emb).data_ptr(), st.w("bias").data_ptr(),
-                      tim.data_ptr(), int(tim.shape[0]), out.ptr, self.H, float(self.H) ** 0.5, pos0, pos_dev, pad,
-                      aan.data_ptr() if aan is not None else None, cat.ptr if cat is not None else None, self.e.stream)
-        return out
-
-    def gemm(self, A, B, C, M, N, K, tb=0, bias=None, act=0):
-        self.lib.call("zk_f32_gemm", A.ptr, B.ptr, C.ptr, M, N, K, A.ld, B.ld, C.ld, tb,
-                      bias.data_ptr() if bias is not None else None, act, self.e.stream)
-
-    def linear(self, x, scope, out, act=0):
-        """func.py:14-65: out = x W + b (act 1: ReLU)."""
-        W = self.w(scope + "/W_0_0")
-        bias = None if self.core.fixup else self.core.store.w(scope + "/b_0")      # (fixup.py: every linear map is bias=False)
-        self.gemm(x, W, out, x.rows, W.cols, W.rows, 0, bias, act)
-        return out
-
-    def add_ln(self, x, y, scope, out):
-        """func.py:321-324 + 289-303: LN(x + y) with the scope's scale / offset."""
-        st = self.core.store
-        if self.fold and self.H % 4 == 0 and self.H <= 2048:
-            # the 16-byte-load form (round 6: 4.8 us against 7.2 for a decode step's 128 rows)
-            return self.ln_fused(x, y, scope, out)
-        self.lib.call("zk_f32_add_ln", x.ptr, y.ptr if y is not None else None, st.w(scope + "/layer_norm/scale").data_ptr(),
-                      st.w(scope + "/layer_norm/offset").data_ptr(), out.ptr, x.rows, self.H, zdtype.epsilon(), self.e.stream)
-        return out
-
-    def attn(self, q, k, v, out, B, Lq, Lk, bsq, bsk, bsv, kmask=None, ldmask=0, kv_group=1, nkeys_dev=None, rpr=None,
-             q_pos0=0, q_pos_dev=None, kbias=None, max_rel=None):
-        """rpr: attention scope prefix (".../dot_attention/") whose rpr_keys / rpr_values tables take part, or None.
-        kbias: fp32 [.., ldmask] added to the scores (transformer_l0drop's log counts: zk_f32_attn_kb), or None.
-        max_rel: the clipping distance handed to the kernel (default: the model's max_relative_position)."""
-        rk = rv = None
-        if rpr is not None:
-            rk = self.core.store.w(rpr + "rpr_keys/embeddings").data_ptr()
-            rv = self.core.store.w(rpr + "rpr_values/embeddings").data_ptr()
-        head = (q.ptr, k.ptr, v.ptr, out.ptr, B, self.nh, Lq, Lk, self.d, q.ld, k.ld, v.ld, out.ld, int(bsq), int(bsk), int(bsv),
-                int(Lq * out.ld), kmask.data_ptr() if kmask is not None else None, int(ldmask))
-        tail = (int(kv_group), float(self.d) ** -0.5, zdtype.inf(), nkeys_dev.data_ptr() if nkeys_dev is not None else None,
-                rk, rv, int(self.core.hp.max_relative_position if max_rel is None else max_rel), int(q_pos0),
-                q_pos_dev.data_ptr() if q_pos_dev is not None else None, self.e.stream)
-        if kbias is not None:
-            self.lib.call("zk_f32_attn_kb", *head, kbias.data_ptr(), *tail)
-        else:
-            self.lib.call("zk_f32_attn", *head, *tail)
-        return out
-
-    def rela_attn(self, q, k, v, out, B, Lq, Lk, bsq, bsk, bsv, scope, kmask=None, ldmask=0, kv_group=1, nkeys_dev=None):
-        """modules/rela.py:56-81 (zk_f32_rela_attn).  scope: the attention scope prefix (".../dot_attention/") whose
-        post/{scale, gate} normalise the combined heads; the other arguments as attn()."""
-        st = self.core.store
-        self.lib.call("zk_f32_rela_attn", q.ptr, k.ptr, v.ptr, out.ptr, B, self.nh, Lq, Lk, self.d, q.ld, k.ld, v.ld, out.ld,
-                      int(bsq), int(bsk), int(bsv), int(Lq * out.ld), kmask.data_ptr() if kmask is not None else None,
-                      int(ldmask), int(kv_group), float(self.d) ** -0.5,
-                      nkeys_dev.data_ptr() if nkeys_dev is not None else None, st.w(scope + "post/scale").data_ptr(),
-                      st.w(scope + "post/gate").data_ptr(), float(zdtype.epsilon()), self.e.stream)
-        return out
-
-    def ln_fused(self, x, y, scope, out, gate=None, aan_next=None, time=0, time_dev=None):
-        """zk_f32_ln_fused (round 6): LN(x + y) with row-local neighbours in the same launch.  gate = (z, cat): y is the
-        average-attention gate of transformer_aan.py:186-189 and the residual is cat[:, :H] (x, y = None);
-        aan_next = (cache tensor, cat Mat): the next layer's average attention from the normalised row."""
-        st = self.core.store
-        z, cat = gate if gate is not None else (None, None)
-        cache, cat_out = aan_next if aan_next is not None else (None, None)
-        self.lib.call("zk_f32_ln_fused", x.ptr if x is not None else None, y.ptr if y is not None else None,
-                      z.ptr if z is not None else None, cat.ptr if cat is not None else None,
-                      st.w(scope + "/layer_norm/scale").data_ptr(), st.w(scope + "/layer_norm/offset").data_ptr(), out.ptr,
-                      out.rows, self.H, zdtype.epsilon(), cache.data_ptr() if cache is not None else None,
-                      cat_out.ptr if cat_out is not None else None, int(time), time_dev, self.e.stream)
-        return out
-
-    def ffn(self, x, scope, tag, aan_next=None, time=0, time_dev=None):
-        """func.py:327-338 + residual + LayerNorm (transformer.py:62-69)."""
-        h = self.mat(tag + ".h", x.rows, self.core.F)
-        self.linear(x, scope + "/ffn_layer/enlarge", h, act=1)
-        y = self.mat("y", x.rows, self.H)
-        self.linear(h, scope + "/ffn_layer/output", y)
-        if aan_next is not None:
-            return self.ln_fused(x, y, scope, self.mat(tag + ".o", x.rows, self.H), aan_next=aan_next, time=time,
-                                 time_dev=time_dev)
-        return self.add_ln(x, y, scope, self.mat(tag + ".o", x.rows, self.H))
-
-
-def encode(core, hp, batch):
-    """transformer.py:15-84 in fp32: -> (encoder output Mat [B*Ls, H], source mask fp32 [B, Ls])."""
-    if core.fixup:
-        from zero_amd.models._fixup import Fixup
-        return Fixup(core, True).encode(batch)
-    o = _Ops(core)
+def encode(core, hp, batch, o=None, attn=None):
+    """transformer.py:15-84 in fp32: -> (encoder output Mat [B*Ls, H], source mask fp32 [B, Ls]).  o: the ops object (default:
+    the decode mode's own, over ``dq.*``); attn: the softmax attention launch (default o.attn, one wave per query row; the
+    scorer passes o.attn_seq)."""
     H = core.H
     B, Ls = batch["B"], batch["Ls"]
     T = B * Ls
     smask = batch["smask"]
+    if core.fixup:
+        o = fixup_ops(core, True)
+        return Fixup(core, o).encode(batch, o.embed(batch["src"], T, Ls, core.src_emb, o.mat("enc.x0", T, H), Ls), smask)
+    o = o or ops_for(core, True)
+    attn = attn or o.attn
     x = o.embed(batch["src"], T, Ls, core.src_emb, o.mat("enc.x0", T, H), Ls)
     for l in range(hp.num_encoder_layer):
         pre = "encoder/layer_%d" % l
@@ -174,8 +56,8 @@ def encode(core, hp, batch):
             o.rela_attn(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, B, Ls, Ls,
                         Ls * 3 * H, Ls * 3 * H, Ls * 3 * H, p, kmask=smask, ldmask=Ls)
         else:
-            o.attn(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, B, Ls, Ls,
-                   Ls * 3 * H, Ls * 3 * H, Ls * 3 * H, kmask=smask, ldmask=Ls, rpr=p if core.rpr else None)
+            attn(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, B, Ls, Ls,
+                 Ls * 3 * H, Ls * 3 * H, Ls * 3 * H, kmask=smask, ldmask=Ls, rpr=p if core.rpr else None)
         y = o.mat("y", T, H)
         o.linear(att, p + "o_map", y)
         x = o.add_ln(x, y, pre + "/self_attention", o.mat("e%d.sa.o" % l, T, H))
@@ -188,14 +70,13 @@ def step_cache(target, state, time, time_dev, hp):
     fp32 [B*K, Vpad].  time_dev: the step counter lives in device memory (hipGraph replay)."""
     from zero_amd.models._decode import append_kv
     core = state["_core"]
-    o = _Ops(core)
+    o = ops_for(core, True)
     e, H = core.eng, core.H
     BK, K, B, Ls, Tmax = state["BK"], state["K"], state["B"], state["Ls"], state["Tmax"]
     if time_dev is None and time >= Tmax:
         raise RuntimeError("decode step %d exceeds the allocated cache length %d" % (time, Tmax))
     if core.fixup:
-        from zero_amd.models._fixup import Fixup
-        return Fixup(core, True).step(target, state, time, time_dev, hp)
+        return Fixup(core, fixup_ops(core, True)).step(target, state, time, time_dev, hp)
     tdev = time_dev.data_ptr() if time_dev is not None else None
     t_host = 0 if time_dev is not None else time
     fold = o.fold
@@ -275,8 +156,8 @@ def step_cache(target, state, time, time_dev, hp):
         o.linear(att, p + "o_map", y)
         x = o.add_ln(x, y, pre + "/" + core.cross, o.mat("d%d.ca.o" % l, BK, H))
         x = o.ffn(x, pre + "/feed_forward", "d%d.ff" % l, aan_next=aan_next, time=t_host, time_dev=tdev)
-    logits = Mat(e.buf("dq.logits", (BK, core.Vpad), F32), BK, core.Vpad)
-    o.gemm(x, o.w(core.soft_emb), logits, BK, core.V, H, tb=1)
+    logits = o.logits_mat(BK)
+    o.gemm(x, o.W(core.soft_emb), logits, BK, core.V, H, tb=1)
     if time_dev is None:
         state["time_filled"] = time + 1
     return logits, state

@@ -175,24 +175,15 @@ def make_infer_fns(total_graphs, total_params):
         logits = [dec(target, state, time)[0] for dec in decs]
         return combine(get_core(hp0, names[0]), logits, logits[0].rows), state
 
+    def step_logits(state, time_dev):
+        logits = [dec.step_cache(state["tok"], m, None, time_dev=time_dev)[0] for dec, m in zip(decs, state["members"])]
+        return combine(state["_core"], logits, state["BK"])
+
     def step_static(state, temperature, forbid_value):
-        """One whole ensemble step with every per-step value read from device memory (models/_decode.py step_static):
+        """One whole ensemble step with every per-step value read from device memory (models/_decode.py static_step):
         bookkeeping head, every member's cache reorder, every member's decoder step, the combine, the search tail.  One
         eager pass per ping-pong parity sizes every member's scratch, the second is captured, the rest are replays."""
-        core = state["_core"]
-        e = core.eng
-
-        def body():
-            sb = state["stepbuf"]
-            book = state.get("book")
-            if book is not None:
-                e.lib.call("zk_beam_dev_prepare", *book, e.stream)
-            state.reorder(state["idx"], time_dev=sb[0:1], defer_aan=True)
-            logits = [dec.step_cache(state["tok"], m, None, time_dev=sb[0:1])[0]
-                      for dec, m in zip(decs, state["members"])]
-            _dec.search_tail(state, core, combine(core, logits, state["BK"]), hp0.enable_noise_beam_search, temperature,
-                             forbid_value)
-        _dec.run_step(state, core, body, False)
+        _dec.static_step(state, hp0, step_logits, False, temperature, forbid_value, defer_aan=True)
 
     decoding_fn.step_static = step_static
     return encoding_fn, decoding_fn, hp0

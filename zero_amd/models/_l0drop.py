@@ -15,18 +15,16 @@ step graph cached for (B, K, Lm, Tmax, ..) replays against the same addresses.
 
 import torch
 
-from zero_amd.func import Mat
-
 F32 = torch.float32
 I32 = torch.int32
 
 
-def prune(core, enc, smask, B, Ls, pad, f32):
-    """enc: Mat [B*Ls, H] (bf16, or fp32 with ``f32``), smask fp32 [B, Ls] -> (memory Mat [B*Lm, H] of enc's type, mask
-    fp32 [B, Lm], Lm, kbias fp32 [B, Lm])."""
+def prune(core, enc, smask, B, Ls, pad, o):
+    """enc: Mat [B*Ls, H] of the storage type of the decode mode's ops object ``o``, smask fp32 [B, Ls] -> (memory Mat
+    [B*Lm, H] of enc's type, mask fp32 [B, Lm], Lm, kbias fp32 [B, Lm])."""
     e, H = core.eng, core.H
-    pre = "dq." if f32 else "dc."
-    dt = F32 if f32 else torch.bfloat16
+    pre = o.pre
+    f32 = o.storage.dtype == F32             # the kernels' is_f32 flag
     gate = e.buf(pre + "l0.gate", (B, Ls), F32)
     pos = e.buf(pre + "l0.pos", (B, Ls), I32)
     cnt = e.buf(pre + "l0.cnt", (2, B), I32)
@@ -45,7 +43,7 @@ def prune(core, enc, smask, B, Ls, pad, f32):
     if not 0 <= k <= Ls:
         raise RuntimeError("zk_l0_gate reported %d kept positions for a source of %d" % (k, Ls))
     Lm = -(-(1 + k) // pad) * pad
-    mem = Mat(e.buf(pre + "enc", (B * Lm, H), dt), B * Lm, H)
+    mem = o.mat("enc", B * Lm, H)
     gmask = e.buf(pre + "smask", (B, Lm), F32)
     kbias = e.buf(pre + "kbias", (B, Lm), F32)
     e.lib.call("zk_l0_compact", enc.ptr, enc.ld, 1 if f32 else 0, gate.data_ptr(), pos.data_ptr(), cnt[0].data_ptr(),

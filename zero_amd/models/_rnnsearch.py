@@ -24,8 +24,6 @@ beam reorder is the row index of the step's first cell launch (no gather launch)
 stored once per sentence (kv_group = K).
 """
 
-import os
-
 import numpy as np
 import torch
 
@@ -33,10 +31,10 @@ from zero_amd.func import Engine, Mat
 from zero_amd.models import _decode as _dec
 from zero_amd.models import _decode_f32 as _f32
 from zero_amd.models._core import trim_columns
+from zero_amd.models._ops import ops_for
 from zero_amd.variables import get_store
 
 F32 = torch.float32
-BF16 = torch.bfloat16
 
 
 class RnnSearchCore(object):
@@ -93,44 +91,15 @@ def check_shape(core, f32):
                          "hidden_size)" % (M, "1 x" if core.ca else "2 x"))
 
 
-class _Ops(object):
-    """The op layer of one mode: buffers, weights and products of the storage type."""
+RN = "rn."        # this model's buffers: the decode mode's prefix + "rn." (RnnState.graph_pointers selects them by it)
 
-    def __init__(self, core, f32):
-        self.core, self.e, self.f32 = core, core.eng, bool(f32)
-        self.st = F32 if f32 else BF16
-        self.esz = 4 if f32 else 2
-        self.pre = (_dec.F32_CACHES if f32 else _dec.BF16_CACHES).prefix + "rn."
 
-    def mat(self, name, rows, cols, dt=None):
-        return Mat(self.e.buf(self.pre + name, (rows, cols), self.st if dt is None else dt), rows, cols)
+def _ops(core, f32):
+    return ops_for(core, f32, (_dec.F32_CACHES if f32 else _dec.BF16_CACHES).prefix + RN)
 
-    def W(self, name):
-        t = self.core.store.w(name) if self.f32 else self.core.store.s(name)
-        return Mat(t, t.shape[0], t.shape[1])
 
-    def table(self, name):
-        return self.core.store.w(name) if self.f32 else self.core.store.s(name)
-
-    def b(self, name):
-        return self.core.store.w(name)
-
-    def gemm(self, A, B, C, M, N, K, tb=0, bias=None):
-        """C = A op(B) (+ bias).  C may be an fp32 Mat in the bf16 mode (the input of a tanh, the logits)."""
-        if self.f32:
-            self.e.lib.call("zk_f32_gemm", A.ptr, B.ptr, C.ptr, M, N, K, A.ld, B.ld, C.ld, tb,
-                            bias.data_ptr() if bias is not None else None, 0, self.e.stream)
-        else:
-            self.e.gemm(A, B, C, M, N, K, 0, tb, bias=bias)
-
-    def project(self, x, name, out, bias=None):
-        """out = x W (+ b): fetch_states and the attention maps."""
-        W = self.W(name)
-        self.gemm(x, W, out, x.rows, W.cols, W.rows, 0, bias)
-        return out
-
-    def cell(self, scope, h_prev, p, out, out_copy=None, idx=None, mask=None):
-        self.e.rnn_atr_step(h_prev, self.W(scope + "/hide_h/W_0_0"), self.b(scope + "/hide_h/b_0"), p, out, out_copy, idx, mask)
+def cell(o, scope, h_prev, p, out, out_copy=None, idx=None, mask=None):
+    o.e.rnn_atr_step(h_prev, o.W(scope + "/hide_h/W_0_0"), o.b(scope + "/hide_h/b_0"), p, out, out_copy, idx, mask)
 
 
 def _at(m, B, t, L, c0=0, cols=None):
@@ -143,6 +112,7 @@ def encode(core, o, batch, K):
     """-> (memory Mat [B * Ls, M], projected memory Mat [B * Ls, M]); writes h_0 into the state buffer of parity 0,
     tiled K times per sentence."""
     e, H, E, M = core.eng, core.H, core.E, core.M
+    esz, f32 = o.storage.esz, o.storage.dtype == F32
     B, Ls = batch["B"], batch["Ls"]
     T = B * Ls
     smask = batch["smask"]
@@ -156,7 +126,7 @@ def encode(core, o, batch, K):
         """A plain rnn.rnn scan over the positions in `order`; copy_of(t): where position t's state goes."""
         prev = None
         for n, t in enumerate(order):
-            o.cell(scope, prev, _at(p, B, t, Ls), hs[n & 1], copy_of(t), mask=mask_at(t))
+            cell(o, scope, prev, _at(p, B, t, Ls), hs[n & 1], copy_of(t), mask=mask_at(t))
             prev = hs[n & 1]
     f = "encoder/forward/"
     pf = o.project(x, f + "fetch_state_atr/hide_x/W_0_0", o.mat("enc.pf", T, H))
@@ -169,8 +139,8 @@ def encode(core, o, batch, K):
         g, s = hs[0], hs[1]
         for t in range(Ls - 1, -1, -1):        # cond_rnn(one2one=True) on the reversed sequence
             first = t == Ls - 1
-            o.cell(b + "cell_atr_lower", None if first else g, _at(plo, B, t, Ls), s, mask=mask_at(t))
-            o.cell(b + "cell_atr_higher", s, _at(phi, B, t, Ls), g, _at(enc, B, t, Ls), mask=mask_at(t))
+            cell(o, b + "cell_atr_lower", None if first else g, _at(plo, B, t, Ls), s, mask=mask_at(t))
+            cell(o, b + "cell_atr_higher", s, _at(phi, B, t, Ls), g, _at(enc, B, t, Ls), mask=mask_at(t))
         feature = _at(enc, B, 0, Ls)
     else:
         scan(f + "cell_atr", pf, range(Ls), lambda t: _at(enc, B, t, Ls, 0, H))
@@ -179,13 +149,13 @@ def encode(core, o, batch, K):
         feature = o.mat("enc.feat", B, M)
         for t, c0 in ((Ls - 1, 0), (0, H)):    # [hf_{Ls-1}, hb_0]
             src = _at(enc, B, t, Ls, c0, H)
-            e.lib.call("zk_gather_rows", src.ptr, src.ld * o.esz, None, feature.ptr + c0 * o.esz, M * o.esz, B, H * o.esz,
+            e.lib.call("zk_gather_rows", src.ptr, src.ld * esz, None, feature.ptr + c0 * esz, M * esz, B, H * esz,
                        e.stream)
     i = "decoder_initializer/atr_init/"
     h0 = o.project(feature, i + "W_0_0", o.mat("enc.h0", B, H, F32))
     state0 = Mat(e.buf(o.pre + "hs.0", (B * K, H), F32), B * K, H)
     e.buf(o.pre + "hs.1", (B * K, H), F32)
-    e.rnn_bias_tanh(h0, o.b(i + "b_0"), out_f32=state0, rep=K, f32=o.f32)
+    e.rnn_bias_tanh(h0, o.b(i + "b_0"), out_f32=state0, rep=K, f32=f32)
     pm = o.project(enc, "decoder/context_att/W_0_0", o.mat("pm", T, M))
     return enc, pm
 
@@ -197,7 +167,7 @@ class RnnState(_dec.DecodeState):
 
     def _half(self, pp):
         core = self["_core"]
-        return Mat(core.eng.buf(self.storage.prefix + "rn.hs.%d" % pp, (self["BK"], core.H), F32), self["BK"], core.H)
+        return Mat(core.eng.buf(self.storage.prefix + RN + "hs.%d" % pp, (self["BK"], core.H), F32), self["BK"], core.H)
 
     def reorder(self, index_dev, time_dev=None, defer_aan=False):
         pp = self["_pp"]
@@ -212,7 +182,7 @@ class RnnState(_dec.DecodeState):
         """Every address a captured step holds (models/_decode.py adopt_graphs / retire_graphs)."""
         core = self["_core"]
         e = core.eng
-        pre = self.storage.prefix + "rn."
+        pre = self.storage.prefix + RN
         ptrs = [self["pack_dev"].data_ptr(), self["out_dev"].data_ptr(), self["mask"].data_ptr(), self["encodes"].ptr,
                 self["pm"].ptr, e.seed.data_ptr(), core.store.shadow.data_ptr(), core.store.master.data_ptr()]
         ptrs += [b.data_ptr() for nm, b in sorted(e.bufs.items()) if nm.startswith(pre)]
@@ -222,7 +192,8 @@ class RnnState(_dec.DecodeState):
 def step(state, target, time, time_dev, hp):
     """One cached decoder step -> (logits Mat fp32 [BK, Vpad], state)."""
     core = state["_core"]
-    o = _Ops(core, state["f32"])
+    o = _ops(core, state["f32"])
+    f32 = o.storage.dtype == F32
     e, H, E, M = core.eng, core.H, core.E, core.M
     BK, K, Ls = state["BK"], state["K"], state["Ls"]
     if time_dev is None and time >= state["Tmax"]:
@@ -237,18 +208,18 @@ def step(state, target, time, time_dev, hp):
     plo = o.project(y, d + "fetch_state_atr_lower/hide_x/W_0_0", o.mat("plo", BK, H))
     s = o.mat("s", BK, H, F32)
     sc = o.mat("sc", BK, H)
-    o.cell(d + "cell_atr_lower", src, plo, s, sc, idx=idx)
+    cell(o, d + "cell_atr_lower", src, plo, s, sc, idx=idx)
     qa = o.project(sc, d + "attention/feed_query/W_0_0", o.mat("qa", BK, M), bias=o.b(d + "attention/feed_query/b_0"))
     v = o.b(d + "attention/feed_logits/W_0_0")
-    if o.f32:
+    if f32:       # the fp32 context is of the storage type already: no separate fp32 buffer
         e.add_attn(qa, state["pm"], state["encodes"], v, state["mask"], c, None, K, Ls)
     else:
         e.add_attn(qa, state["pm"], state["encodes"], v, state["mask"], o.mat("ctx", BK, M, F32), c, K, Ls)
     phi = o.project(c, d + "fetch_state_atr_higher/hide_x/W_0_0", o.mat("phi", BK, H))
-    o.cell(d + "cell_atr_higher", s, phi, dst, cat.cols_slice(0, H))
+    cell(o, d + "cell_atr_higher", s, phi, dst, cat.cols_slice(0, H))
     pre = o.project(cat, "pre_logits/W_0_0", o.mat("pre", BK, E, F32))
     feat = o.mat("feat", BK, E)
-    e.rnn_bias_tanh(pre, o.b("pre_logits/b_0"), out_copy=feat, f32=o.f32)
+    e.rnn_bias_tanh(pre, o.b("pre_logits/b_0"), out_copy=feat, f32=f32)
     logits = o.mat("logits", BK, core.Vpad, F32)
     o.gemm(feat, o.W(core.soft_emb), logits, BK, core.V, E, 1)
     if time_dev is None:
@@ -262,24 +233,15 @@ def build_state(core, hp, source, K, max_steps):
     carry the state over it and the attention gives it the weight 0."""
     f32 = _f32.wanted(hp)
     check_shape(core, f32)
-    o = _Ops(core, f32)
+    o = _ops(core, f32)
     e = core.eng
-    pad = max(1, int(os.environ.get("ZERO_HIP_DECODE_PAD_LEN", "8")))
-    src_np = np.asarray(source.cpu() if torch.is_tensor(source) else source)
-    if pad > 1:
-        trimmed = trim_columns(src_np)
-        batch = core.upload(np.pad(trimmed, ((0, 0), (0, -trimmed.shape[1] % pad))), trim=False)
-    else:
-        batch = core.upload(src_np)
-    if max_steps is None:
-        max_steps = int((src_np != 0).sum(1).max()) + hp.decode_length + 2
-    max_steps = -(-int(max_steps) // pad) * pad
+    batch, max_steps = _dec.shape_batch(core, hp, source, max_steps)
     B, Ls = batch["B"], batch["Ls"]
     enc, pm = encode(core, o, batch, K)
     mask_keep = e.buf(o.pre + "smask", (B, Ls), F32)
     mask_keep.copy_(batch["smask"])
     state = RnnState()
-    state.storage = _dec.F32_CACHES if f32 else _dec.BF16_CACHES
+    state.storage = o.storage
     state.update({"_core": core, "B": B, "K": K, "BK": B * K, "Ls": Ls, "Tmax": max_steps, "encodes": enc, "pm": pm,
                   "mask": mask_keep, "time_filled": 0, "decoder": {}, "f32": f32, "_pp": 0})
     state.bind_caches()
@@ -295,21 +257,8 @@ def make_infer_fns(params, model_name):
         return build_state(core, hp, source, hp.beam_size if beam_size is None else beam_size, max_steps)
 
     def step_static(state, temperature, forbid_value):
-        """One whole decode step with every per-step value read from device memory (the driver of models/_decode.py)."""
-        core = state["_core"]
-        e = core.eng
-        book = state.get("book")
-        if "_gkey" not in state:
-            _dec.adopt_graphs(state, book, temperature, forbid_value, hp.enable_noise_beam_search)
-
-        def body():
-            sb = state["stepbuf"]
-            if book is not None:
-                e.lib.call("zk_beam_dev_prepare", *book, e.stream)
-            state.reorder(state["idx"], time_dev=sb[0:1])
-            logits, _ = step(state, state["tok"], None, sb[0:1], hp)
-            _dec.search_tail(state, core, logits, hp.enable_noise_beam_search, temperature, forbid_value)
-        _dec.run_step(state, core, body, True)
+        _dec.static_step(state, hp, lambda st, time_dev: step(st, st["tok"], None, time_dev, hp)[0], True, temperature,
+                         forbid_value)
 
     def decoding_fn(target, state, time):
         return step(state, target, time, None, hp)

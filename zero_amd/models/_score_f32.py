@@ -24,8 +24,8 @@ for ``transformer``, ``transformer_aan`` (incl. ``use_ffn`` and both ``aan_mask`
 
 import torch
 
-from zero_amd.func import Mat
 from zero_amd.models import _decode_f32
+from zero_amd.models._ops import ops_for
 
 F32 = torch.float32
 
@@ -44,67 +44,9 @@ def check_model(core):
                            "zk_f32_attn_seq reads keys 16 bytes at a time and holds two channels per lane" % core.d)
 
 
-class _Ops(_decode_f32._Ops):
-    """The op layer of ``_decode_f32`` over ``sq.*`` buffers, plus the three full-sequence launches.  ``fold`` keeps the
-    parent's meaning: ZERO_HIP_F32_FUSE=0 selects zk_f32_add_ln instead of the 16-byte-load zk_f32_ln_fused here too."""
-
-    def mat(self, name, rows, cols):
-        return Mat(self.e.buf("sq." + name, (rows, cols), F32), rows, cols)
-
-    def attn_seq(self, q, k, v, out, B, Lq, Lk, bsq, bsk, bsv, kmask=None, ldmask=0, rpr=None, causal=False):
-        rk = rv = None
-        if rpr is not None:
-            rk = self.core.store.w(rpr + "rpr_keys/embeddings").data_ptr()
-            rv = self.core.store.w(rpr + "rpr_values/embeddings").data_ptr()
-        from zero_amd.utils import dtype as zdtype
-        self.lib.call("zk_f32_attn_seq", q.ptr, k.ptr, v.ptr, out.ptr, B, self.nh, Lq, Lk, self.d, q.ld, k.ld, v.ld, out.ld,
-                      int(bsq), int(bsk), int(bsv), int(Lq * out.ld), kmask.data_ptr() if kmask is not None else None,
-                      int(ldmask), float(self.d) ** -0.5, zdtype.inf(), rk, rv, int(self.core.hp.max_relative_position), 0,
-                      1 if causal else 0, self.e.stream)
-        return out
-
-    def cumavg(self, x, tmask, out, B, L, use_mask, add=None):
-        self.lib.call("zk_f32_cumavg", x.ptr, x.ld, tmask.data_ptr(), add.ptr if add is not None else None,
-                      add.ld if add is not None else 0, out.ptr, out.ld, B, L, self.H, 1 if use_mask else 0, self.e.stream)
-        return out
-
-    def embed_shift(self, ids, rows, L, out):
-        st = self.core.store
-        tim = self.e.timing(L + 1, self.H)
-        self.lib.call("zk_f32_embed_shift", ids.data_ptr(), rows, L, st.w(self.core.tgt_emb).data_ptr(),
-                      st.w("bias").data_ptr(), tim.data_ptr(), int(tim.shape[0]), out.ptr, self.H, float(self.H) ** 0.5,
-                      self.e.stream)
-        return out
-
-
-def encode(core, hp, batch, o=None):
-    """transformer.py:15-84 in fp32 (``_decode_f32.encode`` with the attention of a whole sentence per launch):
-    -> (encoder output Mat [B*Ls, H], source mask fp32 [B, Ls])."""
-    o = o or _Ops(core)
-    H = core.H
-    B, Ls = batch["B"], batch["Ls"]
-    T = B * Ls
-    smask = batch["smask"]
-    x = o.embed(batch["src"], T, Ls, core.src_emb, o.mat("enc.x0", T, H), Ls)
-    for l in range(hp.num_encoder_layer):
-        pre = "encoder/layer_%d" % l
-        p = pre + "/self_attention/dot_attention/"
-        qkv = o.mat("enc.qkv", T, 3 * H)
-        o.linear(x, p + "qkv_map", qkv)
-        att = o.mat("enc.att", T, H)
-        o.attn_seq(qkv.cols_slice(0, H), qkv.cols_slice(H, 2 * H), qkv.cols_slice(2 * H, 3 * H), att, B, Ls, Ls,
-                   Ls * 3 * H, Ls * 3 * H, Ls * 3 * H, kmask=smask, ldmask=Ls, rpr=p if core.rpr else None)
-        y = o.mat("y", T, H)
-        o.linear(att, p + "o_map", y)
-        x = o.add_ln(x, y, pre + "/self_attention", o.mat("e%d.sa.o" % l, T, H))
-        x = o.ffn(x, pre + "/feed_forward", "e%d.ff" % l)
-    return x, smask
-
-
-def decode_train(core, hp, batch, enc, smask, o=None):
+def decode_train(core, hp, batch, enc, smask, o):
     """transformer.py:87-181 / transformer_aan.py:120-192 / transformer_fuse.py:131-160, training path, in fp32:
     -> decoder output Mat [B*Lt, H]."""
-    o = o or _Ops(core)
     e, H = core.eng, core.H
     B, Ls, Lt = batch["B"], batch["Ls"], batch["Lt"]
     T = B * Lt
@@ -162,7 +104,7 @@ def decode_train(core, hp, batch, enc, smask, o=None):
 def score(core, hp, batch):
     """transformer.py:235-249 in fp32: the batch of ``core.upload`` -> per-sentence scores fp32 [B]."""
     check_model(core)
-    o = _Ops(core)
+    o = ops_for(core, True, prefix="sq.")
     e = core.eng
     B, Lt = batch["B"], batch["Lt"]
     T = B * Lt
@@ -172,10 +114,10 @@ def score(core, hp, batch):
         e.make_mask(batch["src"], batch["smask"], B * batch["Ls"])
         batch["tmask"] = e.buf("tmask", (B, Lt), F32)
         e.make_mask(batch["tgt"], batch["tmask"], T)
-    enc, smask = encode(core, hp, batch, o)
+    enc, smask = _decode_f32.encode(core, hp, batch, o, o.attn_seq)
     feat = decode_train(core, hp, batch, enc, smask, o)
-    logits = Mat(e.buf("sq.logits", (T, core.Vpad), F32), T, core.Vpad)
-    o.gemm(feat, o.w(core.soft_emb), logits, T, core.V, core.H, tb=1)
+    logits = o.mat("logits", T, core.Vpad)
+    o.gemm(feat, o.W(core.soft_emb), logits, T, core.V, core.H, tb=1)
     ce = e.buf("sq.ce", (T,), F32)
     e.ce_fused(logits, batch["tgt"], None, ce, None, T, core.V, 0.0)
     per_sample = e.buf("sq.per_sample", (B,), F32)
