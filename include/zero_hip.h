@@ -744,6 +744,29 @@ int zk_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, co
 int zk_f32_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const float* U, int ldu, const float* b,
                         const float* p, int ldp, const float* mask, int ldm, float* out, int ldo, float* out_copy, int ldc,
                         int R, int H, zk_stream_t stream);
+/* ONE time step of ONE GRU cell (rnns/gru.py:32-57; models/rnnsearch_deepatt.py with cell=gru) as TWO launches -- the
+ * candidate product contracts r (.) h over all of K and r needs the gate product of every column:
+ *   zk_rnn_gru_gates  [z | r] = sigmoid(xg + h Ug + bg);  rh = r (.) h.   h = h_prev[idx[r]] as in zk_rnn_atr_step (idx NULL:
+ *                     row r; h_prev NULL: the zero state -- no product, rh = 0).  Ug [H, 2 H] and xg [R, 2 H] (the input
+ *                     projection x Wg) of the storage type, the z columns first; bg fp32 [2 H].  z: fp32 [R, H]; rh [R, H]
+ *                     in the storage type: the operand of the second product, formed from the fp32 state, rounded once.
+ *                     z (and, in the fp32 form, rh) must not overlap h_prev: refused.
+ *   zk_rnn_gru_out    c = tanh(xh + rh Uh + bh);  o = z h + (1 - z) c;  out = m o + (1 - m) h.   Uh [H, H], xh [R, H] of the
+ *                     storage type, bh fp32 [H]; z, h_prev, idx as given to zk_rnn_gru_gates (z h and the carry read the fp32
+ *                     state: a carried row is the gathered state bit for bit); mask, out, out_copy as in zk_rnn_atr_step.
+ *                     h_prev NULL: rh is not read.  out must not overlap h_prev or z: refused.
+ * bf16 forms: H % 8 == 0 and H <= 2048 (the gates launch keeps a [32][H + 8] bf16 image of its columns of Ug in LDS: 66 KB
+ * for H = 1000, 129 KB for H = 2048), 16-byte aligned rows of Ug / Uh; anything else is refused by name.  fp32 forms: any H. */
+int zk_rnn_gru_gates(const float* h_prev, int ldh, int n_prev, const int* idx, const void* Ug, int ldu, const float* bg,
+                     const void* xg, int ldx, float* z, int ldz, void* rh, int ldr, int R, int H, zk_stream_t stream);
+int zk_f32_rnn_gru_gates(const float* h_prev, int ldh, int n_prev, const int* idx, const float* Ug, int ldu, const float* bg,
+                         const float* xg, int ldx, float* z, int ldz, float* rh, int ldr, int R, int H, zk_stream_t stream);
+int zk_rnn_gru_out(const void* rh, int ldr, const void* Uh, int ldu, const float* bh, const void* xh, int ldx, const float* z,
+                   int ldz, const float* h_prev, int ldh, int n_prev, const int* idx, const float* mask, int ldm, float* out,
+                   int ldo, void* out_copy, int ldc, int R, int H, zk_stream_t stream);
+int zk_f32_rnn_gru_out(const float* rh, int ldr, const float* Uh, int ldu, const float* bh, const float* xh, int ldx,
+                       const float* z, int ldz, const float* h_prev, int ldh, int n_prev, const int* idx, const float* mask,
+                       int ldm, float* out, int ldo, float* out_copy, int ldc, int R, int H, zk_stream_t stream);
 int zk_add_attn(const void* qa, int ldq, const void* pm, int ldpm, long bspm, const void* mem, int ldmem, long bsmem,
                 const float* v, const float* kmask, int ldmask, float* ctx, int ldo, void* ctx_copy, int ldc, int R,
                 int kv_group, int Ls, int M, float neg, zk_stream_t stream);

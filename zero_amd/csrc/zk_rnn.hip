@@ -1,5 +1,6 @@
 // zk_rnn.hip -- the recurrent family at inference: `rnnsearch` (models/rnnsearch.py; rnns/rnn.py, rnns/atr.py,
-// func.py:107-161 additive_attention).  bf16 forms (bf16 GEMM operands, fp32 arithmetic) and fp32 forms (zk_f32_*).
+// func.py:107-161 additive_attention) and `rnnsearch_deepatt` (models/rnnsearch_deepatt.py; the same launches plus the GRU
+// cell of rnns/gru.py, whose two launches are described where they are defined).  bf16 forms (bf16 GEMM operands, fp32 arithmetic) and fp32 forms (zk_f32_*).
 //
 // ATR cell (rnns/atr.py:32-60, twin gates) for one time step of R rows, with the mask carry of rnns/rnn.py:41-49:
 //     q = h_prev U + b      i = sigmoid(p + q)      f = sigmoid(p - q)      h = i p + f h_prev
@@ -217,8 +218,328 @@ static bool rnn_rows_overlap(const float* a, long lda, long ra, const float* b, 
   ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, h_prev, ldh, n_prev, H),                                                      \
                NAME ": out overlaps h_prev (every column tile reads whole rows of h_prev while others write out)")
 
+// ---------------------------------------------------------------- GRU step (rnns/gru.py:32-57), two launches
+//     [z | r] = sigmoid(xg + h Ug + bg)        rh = r (.) h                               (zk_rnn_gru_gates)
+//     c = tanh(xh + rh Uh + bh)                o = z h + (1 - z) c      out = m o + (1 - m) h   (zk_rnn_gru_out)
+// The candidate product contracts r (.) h over ALL of K and r needs the gate product of every column, so the two products
+// cannot share a launch without an exchange between workgroups: the launch boundary is that exchange.  Tiling as the ATR
+// step.  A gates workgroup owns 16 columns j AND the 16 columns H + j of Ug (two accumulators per wave), so z_j and r_j of
+// an element meet in one lane and rh needs no second pass; its LDS image is [32][K + 8] bf16: 66 KB for H = 1000, and
+// GRU_MAX_H = 2048 (129 KB of the 160 KB of a CU) is the largest H of the bf16 forms.  rh is the MFMA operand of the second
+// launch: formed from the fp32 state and rounded ONCE to the storage type.  z stays fp32; z h and the carry read the fp32
+// state in the second launch, so a carried row is the gathered state bit for bit.  The fp32 forms tile as
+// zk_f32_rnn_atr_step (lane = column, k ascending) and take any H.
+#define GRU_MAX_H 2048
+
+// sT [16][KS] = U[0 .. H - 1][c0 + n0 .. c0 + n0 + 15] transposed; the columns n0 + c >= H and the rows k >= H are zero
+__device__ __forceinline__ void gru_stage_slab(bf16_t* sT, int KS, const bf16_t* __restrict__ U, int ldu, int c0, int n0, int H,
+                                               int Kr) {
+  for (int k = threadIdx.x; k < Kr; k += 256) {
+    uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = lo;
+    if (k < H) {                                               // (H % 8 == 0: a group of 8 columns is inside or outside)
+      const bf16_t* up = U + (size_t)k * ldu + c0 + n0;
+      if (n0 < H) lo = *reinterpret_cast<const uint4*>(up);
+      if (n0 + 8 < H) hi = *reinterpret_cast<const uint4*>(up + 8);
+    }
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      sT[(2 * c) * KS + k] = (bf16_t)(w[c] & 0xffffu);
+      sT[(2 * c + 1) * KS + k] = (bf16_t)(w[c] >> 16);
+    }
+  }
+}
+
+// acc[t] += A[row] . sU tile t for the 16 rows of a wave; A_F32: the row is fp32 (rounded here), else bf16 already
+template <int NT, bool A_F32>
+__device__ __forceinline__ void gru_product(rf32x4_t (&acc)[NT], const bf16_t* sU, int KS, int Kr, int H, const void* arow,
+                                            bool valid, int vec_a, int lane) {
+  const bf16_t* bt = sU + (lane & 15) * KS + (lane >> 4) * 8;
+  for (int kk = 0; kk < Kr; kk += 32) {
+    const int k = kk + (lane >> 4) * 8;
+    uint4 af = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (A_F32) {
+      const float* hp = reinterpret_cast<const float*>(arow);
+      float a[8];
+      if (vec_a) {
+        float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
+        if (valid && k < H) {
+          x0 = *reinterpret_cast<const float4*>(hp + k);
+          x1 = *reinterpret_cast<const float4*>(hp + k + 4);
+        }
+        a[0] = x0.x; a[1] = x0.y; a[2] = x0.z; a[3] = x0.w; a[4] = x1.x; a[5] = x1.y; a[6] = x1.z; a[7] = x1.w;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = (valid && k + e < H) ? hp[k + e] : 0.f;
+      }
+      af = pack8(a);
+    } else {
+      const bf16_t* ap = reinterpret_cast<const bf16_t*>(arow);
+      if (vec_a) {
+        if (valid && k < H) af = *reinterpret_cast<const uint4*>(ap + k);
+      } else {
+        float a[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = (valid && k + e < H) ? bf2f(ap[k + e]) : 0.f;
+        af = pack8(a);                                         // (exact: the values are bf16 already)
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const uint4 bf = *reinterpret_cast<const uint4*>(bt + (size_t)t * 16 * KS + kk);
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(rbf16x8_t, af), __builtin_bit_cast(rbf16x8_t, bf),
+                                                       acc[t], 0, 0, 0);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_rnn_gru_gates(const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                       const int* __restrict__ idx, const bf16_t* __restrict__ Ug, int ldu,
+                                                       const float* __restrict__ bg, const bf16_t* __restrict__ xg, int ldx,
+                                                       float* __restrict__ z, int ldz, bf16_t* __restrict__ rh, int ldr, int R,
+                                                       int H, int vec_a) {
+  extern __shared__ __align__(16) unsigned char gru_lds[];
+  bf16_t* sU = reinterpret_cast<bf16_t*>(gru_lds);            // [2][ATR_BN][KS]: the z columns, then the r columns
+  const int Kr = (H + 31) / 32 * 32, KS = Kr + 8;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
+  rf32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  if (h_prev != nullptr) {
+    gru_stage_slab(sU, KS, Ug, ldu, 0, n0, H, Kr);
+    gru_stage_slab(sU + (size_t)ATR_BN * KS, KS, Ug, ldu, H, n0, H, Kr);
+    __syncthreads();
+    if (r0 < R) {                                              // wave-uniform: the MFMA runs with all 64 lanes
+      const int row = r0 + (lane & 15);
+      const bool valid = row < R;
+      int src = valid ? (idx != nullptr ? idx[row] : row) : 0;
+      src = min(max(src, 0), n_prev - 1);
+      gru_product<2, true>(acc, sU, KS, Kr, H, h_prev + (size_t)src * ldh, valid, vec_a, lane);
+    }
+  }
+  const int col = n0 + (lane & 15);
+  if (col >= H) return;
+  const float bz = bg[col], br = bg[H + col];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = r0 + (lane >> 4) * 4 + r;
+    if (row >= R) continue;
+    float hv = 0.f;
+    if (h_prev != nullptr) {
+      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
+      hv = h_prev[(size_t)src * ldh + col];
+    }
+    const bf16_t* xr = xg + (size_t)row * ldx;
+    z[(size_t)row * ldz + col] = rnn_sigmoid(bf2f(xr[col]) + (acc[0][r] + bz));
+    rh[(size_t)row * ldr + col] = f2bf(rnn_sigmoid(bf2f(xr[H + col]) + (acc[1][r] + br)) * hv);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_rnn_gru_out(const bf16_t* __restrict__ rh, int ldr, const bf16_t* __restrict__ Uh,
+                                                     int ldu, const float* __restrict__ bh, const bf16_t* __restrict__ xh,
+                                                     int ldx, const float* __restrict__ z, int ldz,
+                                                     const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                     const int* __restrict__ idx, const float* __restrict__ mask, int ldm,
+                                                     float* __restrict__ out, int ldo, bf16_t* __restrict__ out_copy, int ldc,
+                                                     int R, int H, int vec_a) {
+  extern __shared__ __align__(16) unsigned char gru_lds[];
+  bf16_t* sU = reinterpret_cast<bf16_t*>(gru_lds);            // [ATR_BN][KS]
+  const int Kr = (H + 31) / 32 * 32, KS = Kr + 8;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
+  rf32x4_t acc[1] = {{0.f, 0.f, 0.f, 0.f}};
+  if (h_prev != nullptr) {                                     // (the zero state: rh = 0, no product)
+    gru_stage_slab(sU, KS, Uh, ldu, 0, n0, H, Kr);
+    __syncthreads();
+    if (r0 < R) {
+      const int row = r0 + (lane & 15);
+      const bool valid = row < R;
+      gru_product<1, false>(acc, sU, KS, Kr, H, rh + (size_t)(valid ? row : 0) * ldr, valid, vec_a, lane);
+    }
+  }
+  const int col = n0 + (lane & 15);
+  if (col >= H) return;
+  const float bias = bh[col];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = r0 + (lane >> 4) * 4 + r;
+    if (row >= R) continue;
+    float hv = 0.f;
+    if (h_prev != nullptr) {
+      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
+      hv = h_prev[(size_t)src * ldh + col];
+    }
+    const float c = tanhf(bf2f(xh[(size_t)row * ldx + col]) + (acc[0][r] + bias));
+    const float zv = z[(size_t)row * ldz + col];
+    float h = zv * hv + (1.f - zv) * c;
+    if (mask != nullptr) {
+      const float m = mask[(size_t)row * ldm];
+      h = m * h + (1.f - m) * hv;
+    }
+    out[(size_t)row * ldo + col] = h;
+    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = f2bf(h);
+  }
+}
+
+// fp32 forms: acc[j] += sum_k A[row j of the wave][k] U[k][col]; the block's 32 rows of A pass through LDS in chunks of 64 k.
+// arow: the row this thread stages (NULL: a row past R, zeros)
+__device__ __forceinline__ void gru_f32_product(float (&acc)[8], float (*sh)[64], const float* arow, const float* __restrict__ U,
+                                                int ldu, int H, int col, int wave) {
+  const int lr = threadIdx.x >> 3, lk = (threadIdx.x & 7) * 8;
+  for (int k0 = 0; k0 < H; k0 += 64) {
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sh[lr][lk + e] = (arow != nullptr && k0 + lk + e < H) ? arow[k0 + lk + e] : 0.f;
+    __syncthreads();
+    const int kn = min(64, H - k0);
+    if (col < H) {
+      int kk = 0;
+      for (; kk + 8 <= kn; kk += 8) {                          // eight rows of U in flight per lane, then their products
+        float u[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) u[e] = U[(size_t)(k0 + kk + e) * ldu + col];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float4 a0 = *reinterpret_cast<const float4*>(&sh[wave * 8 + j][kk]);
+          const float4 a1 = *reinterpret_cast<const float4*>(&sh[wave * 8 + j][kk + 4]);
+          const float a[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[j] = fmaf(a[e], u[e], acc[j]);       // (k ascending per output)
+        }
+      }
+      for (; kk < kn; ++kk) {
+        const float u = U[(size_t)(k0 + kk) * ldu + col];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = fmaf(sh[wave * 8 + j][kk], u, acc[j]);
+      }
+    }
+  }
+}
+
+// (the fp32 gates launch needs no pairing of z_j with r_j: rh = r h takes r alone.  So its grid is 2 x H / 64 column tiles -- the
+// first half forms z, the second rh -- and twice as many CUs pull Ug as a paired tile would give)
+__global__ void __launch_bounds__(256) k_f32_rnn_gru_gates(const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                           const int* __restrict__ idx, const float* __restrict__ Ug, int ldu,
+                                                           const float* __restrict__ bg, const float* __restrict__ xg, int ldx,
+                                                           float* __restrict__ z, int ldz, float* __restrict__ rh, int ldr,
+                                                           int R, int H) {
+  __shared__ __align__(16) float sh[ATRF_BM][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nct = gridDim.x >> 1;
+  const bool second = (int)blockIdx.x >= nct;                  // block-uniform: this tile forms r (and rh), not z
+  const int col = ((int)blockIdx.x - (second ? nct : 0)) * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
+  const int gcol = (second ? H : 0) + col;                     // the column of Ug, bg and xg
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  if (h_prev != nullptr) {
+    const int grow = r0 + (threadIdx.x >> 3);
+    int src = grow < R ? (idx != nullptr ? idx[grow] : grow) : 0;
+    src = min(max(src, 0), n_prev - 1);
+    gru_f32_product(acc, sh, grow < R ? h_prev + (size_t)src * ldh : nullptr, Ug + (second ? H : 0), ldu, H, col, wave);
+  }
+  if (col >= H) return;
+  const float bias = bg[gcol];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = r0 + wave * 8 + j;
+    if (row >= R) continue;
+    const float g = rnn_sigmoid(xg[(size_t)row * ldx + gcol] + (acc[j] + bias));
+    if (!second) {
+      z[(size_t)row * ldz + col] = g;
+      continue;
+    }
+    float hv = 0.f;
+    if (h_prev != nullptr) {
+      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
+      hv = h_prev[(size_t)src * ldh + col];
+    }
+    rh[(size_t)row * ldr + col] = g * hv;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_f32_rnn_gru_out(const float* __restrict__ rh, int ldr, const float* __restrict__ Uh,
+                                                         int ldu, const float* __restrict__ bh, const float* __restrict__ xh,
+                                                         int ldx, const float* __restrict__ z, int ldz,
+                                                         const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                         const int* __restrict__ idx, const float* __restrict__ mask, int ldm,
+                                                         float* __restrict__ out, int ldo, float* __restrict__ out_copy, int ldc,
+                                                         int R, int H) {
+  __shared__ __align__(16) float sh[ATRF_BM][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int col = blockIdx.x * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  if (h_prev != nullptr) {
+    const int grow = r0 + (threadIdx.x >> 3);
+    gru_f32_product(acc, sh, grow < R ? rh + (size_t)grow * ldr : nullptr, Uh, ldu, H, col, wave);
+  }
+  if (col >= H) return;
+  const float bias = bh[col];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = r0 + wave * 8 + j;
+    if (row >= R) continue;
+    float hv = 0.f;
+    if (h_prev != nullptr) {
+      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
+      hv = h_prev[(size_t)src * ldh + col];
+    }
+    const float c = tanhf(xh[(size_t)row * ldx + col] + (acc[j] + bias));
+    const float zv = z[(size_t)row * ldz + col];
+    float h = zv * hv + (1.f - zv) * c;
+    if (mask != nullptr) {
+      const float m = mask[(size_t)row * ldm];
+      h = m * h + (1.f - m) * hv;
+    }
+    out[(size_t)row * ldo + col] = h;
+    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = h;
+  }
+}
+
+#define GRU_CHECK_STATE(NAME)                                                                                               \
+  ZK_CHECK_ARG(R >= 0 && H >= 1, NAME ": bad shape (R=%d H=%d)", R, H);                                                     \
+  ZK_CHECK_ARG(h_prev == nullptr || ldh >= H, NAME ": ldh=%d is smaller than H=%d", ldh, H);                                \
+  ZK_CHECK_ARG(h_prev == nullptr || (idx != nullptr ? n_prev >= 1 : n_prev >= R),                                           \
+               NAME ": h_prev has n_prev=%d rows (R=%d without an index, at least 1 with one)", n_prev, R)
+
+#define GRU_CHECK_GATES(NAME)                                                                                               \
+  ZK_CHECK_ARG(Ug != nullptr && bg != nullptr && xg != nullptr && z != nullptr && rh != nullptr,                            \
+               NAME ": Ug, bg, xg, z and rh are required");                                                                 \
+  GRU_CHECK_STATE(NAME);                                                                                                    \
+  ZK_CHECK_ARG(ldu >= 2 * H && ldx >= 2 * H && ldz >= H && ldr >= H,                                                        \
+               NAME ": a leading dimension is too small for H=%d (ldu=%d and ldx=%d hold 2 H columns, ldz=%d ldr=%d)", H,   \
+               ldu, ldx, ldz, ldr);                                                                                         \
+  ZK_CHECK_ARG(!rnn_rows_overlap(z, ldz, R, h_prev, ldh, n_prev, H),                                                        \
+               NAME ": z overlaps h_prev (every column tile reads whole rows of h_prev while others write z)")
+
+#define GRU_CHECK_OUT(NAME)                                                                                                 \
+  ZK_CHECK_ARG(rh != nullptr && Uh != nullptr && bh != nullptr && xh != nullptr && z != nullptr && out != nullptr,          \
+               NAME ": rh, Uh, bh, xh, z and out are required");                                                            \
+  GRU_CHECK_STATE(NAME);                                                                                                    \
+  ZK_CHECK_ARG(ldr >= H && ldu >= H && ldx >= H && ldz >= H && ldo >= H && (out_copy == nullptr || ldc >= H),               \
+               NAME ": a leading dimension is smaller than H=%d (ldr=%d ldu=%d ldx=%d ldz=%d ldo=%d ldc=%d)", H, ldr, ldu,  \
+               ldx, ldz, ldo, ldc);                                                                                         \
+  ZK_CHECK_ARG(mask == nullptr || ldm >= 1, NAME ": the mask stride must be at least 1 (ldm=%d)", ldm);                     \
+  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, h_prev, ldh, n_prev, H),                                                      \
+               NAME ": out overlaps h_prev (a row of h_prev may be gathered by several rows while others write out)");      \
+  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, z, ldz, R, H), NAME ": out overlaps z")
+
+#define GRU_CHECK_BF16(NAME, U, F32NAME)                                                                                    \
+  ZK_CHECK_ARG(H % 8 == 0 && H <= GRU_MAX_H && ldu % 8 == 0 && (((uintptr_t)U) & 15) == 0,                                  \
+               NAME ": the bf16 form needs H a multiple of 8 and at most %d (its LDS image of the recurrent matrix) and "   \
+               "16-byte aligned rows of the matrix (H=%d ldu=%d); " F32NAME " takes any H", GRU_MAX_H, H, ldu)
+
+template <typename Kern>
+static int gru_lds_attr(const char* name, Kern kern, size_t lds) {
+  if (lds < 64 * 1024) return 0;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return zk_set_error((int)e, "%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
+  return 0;
+}
+
 // ---------------------------------------------------------------- additive attention
-#define ADD_RB 4           // beam rows per workgroup (1 when a sentence has a single row)
+#define ADD_RB 4          // beam rows per workgroup (1 when a sentence has a single row)
 #define ADD_CC 8           // 256-channel chunks a thread accumulates: M <= 2048
 
 template <bool F32, int NV>
@@ -481,6 +802,66 @@ int zk_f32_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx
   if (R == 0) return 0;
   hipLaunchKernelGGL(k_f32_rnn_atr_step, dim3((unsigned)((H + ATRF_BN - 1) / ATRF_BN), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
                      dim3(256), 0, stream, h_prev, ldh, n_prev, idx, U, ldu, b, p, ldp, mask, ldm, out, ldo, out_copy, ldc, R, H);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_rnn_gru_gates(const float* h_prev, int ldh, int n_prev, const int* idx, const void* Ug, int ldu, const float* bg,
+                     const void* xg, int ldx, float* z, int ldz, void* rh, int ldr, int R, int H, hipStream_t stream) {
+  GRU_CHECK_GATES("zk_rnn_gru_gates");
+  GRU_CHECK_BF16("zk_rnn_gru_gates", Ug, "zk_f32_rnn_gru_gates");
+  if (R == 0) return 0;
+  const int Kr = (H + 31) / 32 * 32;
+  const size_t lds = (size_t)2 * ATR_BN * (Kr + 8) * sizeof(bf16_t);
+  if (gru_lds_attr("zk_rnn_gru_gates", k_rnn_gru_gates, lds) != 0) return -1;
+  const int vec_a = h_prev != nullptr && ldh % 4 == 0 && (((uintptr_t)h_prev) & 15) == 0;
+  hipLaunchKernelGGL(k_rnn_gru_gates, dim3((unsigned)((H + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)),
+                     dim3(256), lds, stream, h_prev, ldh, n_prev, idx, reinterpret_cast<const bf16_t*>(Ug), ldu, bg,
+                     reinterpret_cast<const bf16_t*>(xg), ldx, z, ldz, reinterpret_cast<bf16_t*>(rh), ldr, R, H, vec_a);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_f32_rnn_gru_gates(const float* h_prev, int ldh, int n_prev, const int* idx, const float* Ug, int ldu, const float* bg,
+                         const float* xg, int ldx, float* z, int ldz, float* rh, int ldr, int R, int H, hipStream_t stream) {
+  GRU_CHECK_GATES("zk_f32_rnn_gru_gates");
+  ZK_CHECK_ARG(!rnn_rows_overlap(rh, ldr, R, h_prev, ldh, n_prev, H), "zk_f32_rnn_gru_gates: rh overlaps h_prev");
+  if (R == 0) return 0;
+  hipLaunchKernelGGL(k_f32_rnn_gru_gates, dim3((unsigned)(2 * ((H + ATRF_BN - 1) / ATRF_BN)), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
+                     dim3(256), 0, stream, h_prev, ldh, n_prev, idx, Ug, ldu, bg, xg, ldx, z, ldz, rh, ldr, R, H);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_rnn_gru_out(const void* rh, int ldr, const void* Uh, int ldu, const float* bh, const void* xh, int ldx, const float* z,
+                   int ldz, const float* h_prev, int ldh, int n_prev, const int* idx, const float* mask, int ldm, float* out,
+                   int ldo, void* out_copy, int ldc, int R, int H, hipStream_t stream) {
+  GRU_CHECK_OUT("zk_rnn_gru_out");
+  GRU_CHECK_BF16("zk_rnn_gru_out", Uh, "zk_f32_rnn_gru_out");
+  if (R == 0) return 0;
+  const int Kr = (H + 31) / 32 * 32;
+  const size_t lds = (size_t)ATR_BN * (Kr + 8) * sizeof(bf16_t);
+  if (gru_lds_attr("zk_rnn_gru_out", k_rnn_gru_out, lds) != 0) return -1;
+  const int vec_a = ldr % 8 == 0 && (((uintptr_t)rh) & 15) == 0;
+  hipLaunchKernelGGL(k_rnn_gru_out, dim3((unsigned)((H + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)), dim3(256),
+                     lds, stream, reinterpret_cast<const bf16_t*>(rh), ldr, reinterpret_cast<const bf16_t*>(Uh), ldu, bh,
+                     reinterpret_cast<const bf16_t*>(xh), ldx, z, ldz, h_prev, ldh, n_prev, idx, mask, ldm, out, ldo,
+                     reinterpret_cast<bf16_t*>(out_copy), ldc, R, H, vec_a);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_f32_rnn_gru_out(const float* rh, int ldr, const float* Uh, int ldu, const float* bh, const float* xh, int ldx,
+                       const float* z, int ldz, const float* h_prev, int ldh, int n_prev, const int* idx, const float* mask,
+                       int ldm, float* out, int ldo, float* out_copy, int ldc, int R, int H, hipStream_t stream) {
+  GRU_CHECK_OUT("zk_f32_rnn_gru_out");
+  ZK_CHECK_ARG(!rnn_rows_overlap(out_copy, ldc, R, h_prev, ldh, n_prev, H), "zk_f32_rnn_gru_out: out_copy overlaps h_prev");
+  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, rh, ldr, R, H) && !rnn_rows_overlap(out_copy, ldc, R, rh, ldr, R, H),
+               "zk_f32_rnn_gru_out: out or out_copy overlaps rh (every column tile reads whole rows of rh)");
+  if (R == 0) return 0;
+  hipLaunchKernelGGL(k_f32_rnn_gru_out, dim3((unsigned)((H + ATRF_BN - 1) / ATRF_BN), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
+                     dim3(256), 0, stream, rh, ldr, Uh, ldu, bh, xh, ldx, z, ldz, h_prev, ldh, n_prev, idx, mask, ldm, out, ldo,
+                     out_copy, ldc, R, H);
   ZK_LAUNCH_CHECK();
   return 0;
 }

@@ -648,6 +648,20 @@ class Engine(object):
         self.lib.call(name, *mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx), U.ptr, U.ld,
                       b.data_ptr(), p.ptr, p.ld, *mp(mask), out.ptr, out.ld, *mp(out_copy), out.rows, out.cols, self.stream)
 
+    def rnn_gru_step(self, h_prev, Ug, bg, Uh, bh, xg, xh, z, rh, out, out_copy=None, idx=None, mask=None):
+        """rnns/gru.py:32-57 + the carry of rnns/rnn.py:41-49, one time step of one cell as TWO launches (zk_rnn_gru_gates,
+        zk_rnn_gru_out; the fp32 forms by xh's dtype): [z | r] = sigmoid(xg + h Ug + bg), out = carry(mask, z h + (1 - z)
+        tanh(xh + (r h) Uh + bh), h) with h = h_prev[idx].  h_prev, idx, mask, out, out_copy as in rnn_atr_step; Ug: Mat [H, 2 H],
+        Uh: Mat [H, H], xg: Mat [R, 2 H], xh: Mat [R, H] of the storage type; bg fp32 [2 H], bh fp32 [H]; z (fp32 Mat [R, H])
+        and rh (storage-type Mat [R, H]) are the caller's scratch between the two launches."""
+        f32 = xh.t.dtype == torch.float32
+        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
+        state = (*mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx))
+        self.lib.call("zk_f32_rnn_gru_gates" if f32 else "zk_rnn_gru_gates", *state, Ug.ptr, Ug.ld, bg.data_ptr(), xg.ptr, xg.ld,
+                      z.ptr, z.ld, rh.ptr, rh.ld, out.rows, out.cols, self.stream)
+        self.lib.call("zk_f32_rnn_gru_out" if f32 else "zk_rnn_gru_out", rh.ptr, rh.ld, Uh.ptr, Uh.ld, bh.data_ptr(), xh.ptr,
+                      xh.ld, z.ptr, z.ld, *state, *mp(mask), out.ptr, out.ld, *mp(out_copy), out.rows, out.cols, self.stream)
+
     def add_attn(self, qa, pm, mem, v, kmask, ctx, ctx_copy, kv_group, Ls):
         """func.py:107-161 for one decode step (zk_add_attn / zk_f32_add_attn): qa Mat [R, M]; pm, mem Mats [R / kv_group *
         Ls, M] (projected memory, memory) of the storage type; v fp32 [M]; kmask fp32 [R / kv_group, Ls] or None; ctx fp32

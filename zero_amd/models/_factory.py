@@ -68,6 +68,9 @@ def _core_class(model_name):
     if model_name == "rnnsearch":
         from zero_amd.models._rnnsearch import RnnSearchCore
         return RnnSearchCore
+    if model_name == "rnnsearch_deepatt":
+        from zero_amd.models._deepatt import DeepAttCore
+        return DeepAttCore
     return TransformerCore
 
 

@@ -134,6 +134,55 @@ def _rnnsearch_specs(params):
     return [(n, s, k, None) for n, s, k in v]
 
 
+def _deepatt_specs(params):
+    """models/rnnsearch_deepatt.py:68-128, 132-236, 240-303 + rnns/rnn.py + rnns/{atr,gru,cell}.py + func.py:107-161 in
+    creation order (cell "atr" or "gru", layer_norm off).  A cell `s` owns its input projections fetch_state_<s>/... (no
+    bias) and its recurrent maps cell_<s>/... :
+        atr   fetch: hide_x/W_0_0 [in, H]                            cell: hide_h/{W_0_0 [H, H], b_0}
+        gru   fetch: gate_x/W_0_0 [in, 2 H], hide_x/W_0_0 [in, H]    cell: gate_h/{W_0_0 [H, 2 H], b_0}, hide_h/{W_0_0 [H, H], b_0}
+    Every scan creates the input projections of its cells (and, in the decoder, context_att) IN FRONT of tf.scan and the
+    recurrent maps -- in the decoder also each deep_attention_l and fetch_state_<c>_higher_l, which act on values computed
+    inside the step -- INSIDE it, in the order the step body runs.  The memory is H wide.  Embeddings and `bias` as
+    _rnnsearch_specs."""
+    H, E = params.hidden_size, params.embed_size
+    Vs, Vt = params.src_vocab.size(), params.tgt_vocab.size()
+    shared = params.shared_source_target_embedding
+    c = str(params.cell).lower()
+    if c not in ("atr", "gru"):
+        raise NotImplementedError("rnnsearch_deepatt: the variables of cell=%s are not laid out (atr and gru are)" % c)
+
+    def fetch(pre, s, width):
+        p = pre + "fetch_state_%s/" % s
+        gate = [(p + "gate_x/W_0_0", (width, 2 * H), "w")] if c == "gru" else []
+        return gate + [(p + "hide_x/W_0_0", (width, H), "w")]
+
+    def cell(pre, s):
+        p = pre + "cell_%s/" % s
+        gate = [(p + "gate_h/W_0_0", (H, 2 * H), "w"), (p + "gate_h/b_0", (2 * H,), "zeros")] if c == "gru" else []
+        return gate + [(p + "hide_h/W_0_0", (H, H), "w"), (p + "hide_h/b_0", (H,), "zeros")]
+    v = [("embedding" if shared else "src_embedding", (Vs, E), "embed_w"), ("bias", (E,), "w")]
+    v += fetch("encoder/layer_0/", c, E) + cell("encoder/layer_0/", c)
+    for l in range(1, params.num_encoder_layer + 1):
+        pre = "encoder/layer_%d/" % l
+        v += fetch(pre, c + "_lower", E) + fetch(pre, c + "_higher", H) + cell(pre, c + "_lower") + cell(pre, c + "_higher")
+    i = "decoder_initializer/dec_init_state_init/"
+    v += [(i + "W_0_0", (H, H), "w"), (i + "b_0", (H,), "zeros")]
+    if not shared:
+        v.append(("tgt_embedding", (Vt, E), "embed_w"))
+    d = "decoder/"
+    v += fetch(d, c + "_lower", E) + [(d + "context_att/W_0_0", (H, H), "w")] + cell(d, c + "_lower")
+    D = params.num_decoder_layer
+    for l in range(D):
+        a = d + "deep_attention_%d/" % l
+        v += [(a + "feed_query/W_0_0", (H, H), "w"), (a + "feed_query/b_0", (H,), "zeros"),
+              (a + "feed_logits/W_0_0", (H, 1), "w"), (a + "feed_logits/b_0", (1,), "zeros")]
+        v += fetch(d, "%s_higher_%d" % (c, l), H) + cell(d, "%s_higher_%d" % (c, l))
+    v += [("ff/W_0_0", (H + D * H + E, E), "w"), ("ff/b_0", (E,), "zeros")]
+    if not shared and not params.shared_target_softmax_embedding:
+        v.append(("softmax_embedding", (Vt, E), "embed_w"))
+    return [(n, s, k, None) for n, s, k in v]
+
+
 def variable_specs(params, model_name):
     """[(name, logical_shape, kind, layer)] in the reference's creation order
     (transformer.py:16-33,88-102,184-192; transformer_aan.py:165-192;
@@ -142,6 +191,8 @@ def variable_specs(params, model_name):
     transformer_rela.py:48,134,154 + modules/rela.py:34-84: `transformer` plus post/{scale,gate} per attention scope)."""
     if model_name == "rnnsearch":       # (the one family whose embeddings are not H wide: before the H == E test)
         return _rnnsearch_specs(params)
+    if model_name == "rnnsearch_deepatt":
+        return _deepatt_specs(params)
     H, E, F = params.hidden_size, params.embed_size, params.filter_size
     if H != E:
         raise ValueError("hidden_size must equal embed_size for the Transformer models "
