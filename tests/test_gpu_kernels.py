@@ -475,10 +475,14 @@ def test_embed_bwd_sorted_long_runs_of_one_id(H):
     dout = rand_bf(B * L, H, seed=7)
     srt = device_sort_arrays(e, "runs%d" % H, ids_np, False)
     dtab = torch.zeros(V, H, device="cuda")
-    e.embed_bwd_sorted(srt, mat(dout), dtab, H, accumulate=False)
+    e.set_seed(97)
+    e.embed_bwd_sorted(srt, mat(dout), dtab, H, accumulate=False, drop_p=0.5, sid=13)
+    msk = torch.zeros(B * L * H, device="cuda")
+    e.lib.call("zk_dropout_mask", msk.data_ptr(), B * L * H, 0.5, e.seed.data_ptr(), 13, e.stream)
     torch.cuda.synchronize()
+    assert 0.4 < float((msk == 0).float().mean()) < 0.6 and set(msk.unique().tolist()) == {0.0, 2.0}
     ref = torch.zeros(V, H, dtype=torch.float64, device="cuda")
-    ref.index_add_(0, torch.tensor(ids_np.reshape(-1), device="cuda"), dout.double() * H ** 0.5)
+    ref.index_add_(0, torch.tensor(ids_np.reshape(-1), device="cuda"), dout.double() * msk.view(B * L, H).double() * H ** 0.5)
     assert rel_err(dtab, ref.float()) < 2e-6
     assert float(dtab[0].abs().max()) == 0.0
 
