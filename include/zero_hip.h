@@ -217,6 +217,20 @@ int zk_embed_bwd_sorted_pair(const int* rows_a, const int* seg_a, const int* uid
 int zk_colsum_pair(const void* a, int rows_a, int lda, int skip_a, uint32_t sid_a, const void* b, int rows_b, int ldb,
                    int skip_b, uint32_t sid_b, int N, float* out, float drop_p, const uint64_t* seed, void* workspace,
                    size_t ws_bytes, zk_stream_t stream);
+/* The tail of the backward pass in ONE launch (+ the final k_partials_reduce of the bias sum): the grouped reductions of
+ * zk_reduce_grouped (red_descs / nred / red_blocks as there; bias gradients of func.py:58-60, LayerNorm gradients of
+ * func.py:289-303), both scatters of zk_embed_bwd_sorted_pair and both sides of zk_colsum_pair (the embedding and shared
+ * input-bias gradients of transformer.py:16-33 / 88-119), as block ranges of one grid: they do not depend on one another,
+ * each keeps the arithmetic and the summation order of the launch it replaces (same bits).  dout_x: bf16 [T_x, H], ld = H,
+ * also the column sum's input (rows r % skip_x == 0 left out when skip_x > 0); T_x is max_uniq of the sort arrays too.
+ * zero_rows_b > 0 (needs acc_b = 0): every row r < zero_rows_b of dtable_b whose id is NOT in uid_b is written as zeros
+ * (the rows in uid_b are the ones the scatter writes), so dtable_b needs no zero fill before the backward.
+ * workspace >= zk_colsum_workspace(T_a, H) + zk_colsum_workspace(T_b, H). */
+int zk_step_tail(const void* red_descs, int nred, int red_blocks, const int* rows_a, const int* seg_a, const int* uid_a,
+                 const int* n_a, int T_a, const void* dout_a, float* dtable_a, int acc_a, int skip_a, uint32_t sid_a,
+                 const int* rows_b, const int* seg_b, const int* uid_b, const int* n_b, int T_b, const void* dout_b,
+                 float* dtable_b, int acc_b, int skip_b, uint32_t sid_b, int H, float scale, int zero_rows_b, float* dbias,
+                 float drop_p, const uint64_t* seed, void* workspace, size_t ws_bytes, zk_stream_t stream);
 /* dtable (fp32 [V,H]) and dbias (fp32 [H]) are ACCUMULATED into with atomics. */
 int zk_embed_bwd(const int* ids, const void* dout, float* dtable, float* dbias, int B, int L, int H,
                  float scale, int shift, float drop_p, const uint64_t* seed, uint32_t sid, zk_stream_t stream);
@@ -270,6 +284,12 @@ int zk_colsum_rowchunks(int rows);
  * = w[r]*(softmax - soft).                                                            */
 int zk_ce_fused(const float* logits, const int* ids, const float* w, float* ce_out, void* dlogits, int rows,
                 int V, int ld, float label_smooth, zk_stream_t stream);
+/* zk_ce_fused with the per-sentence loss and its mean (zk_loss_reduce; util.py:88-103, transformer.py:198-211) formed by the
+ * block that arrives LAST instead of a launch of its own -- the same code and order of sums.  arrive: a device word the
+ * caller zeroed ONCE; every call leaves it zero again.  ids [B, L], rows = B * L; loss may be NULL. */
+int zk_ce_fused_tail(const float* logits, const int* ids, const float* w, float* ce_out, void* dlogits, int rows, int V,
+                     int ld, float label_smooth, float* per_sample, float* loss, int B, int L, uint32_t* arrive,
+                     zk_stream_t stream);
 /* transformer.py:208-216: mask=(id!=0); w = loss_scale*mask/(len_b*B); per-sentence loss and mean */
 int zk_target_stats(const int* ids, float* mask, float* w, int B, int L, float loss_scale, zk_stream_t stream);
 int zk_loss_reduce(const float* ce, const int* ids, float* per_sample, float* loss, int B, int L,
@@ -337,6 +357,14 @@ size_t zk_adam_step_workspace(void);
 int zk_adam_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, size_t n, float* hyper,
                  float* pnorm_out, uint64_t* seed, int norm_free, const int* skip_word, void* workspace, size_t ws_bytes,
                  zk_stream_t stream);
+/* zk_adam_step with the finish of its norm_free form (cycle.py:94-101: gradient norm -> hyper[6] / [7] / [10], parameter
+ * norm -> pnorm_out) done by the block of the Adam pass that arrives LAST instead of a one-block launch of its own: the
+ * same per-block partials added in the same order (same bits), one launch for the whole update.  arrive: a device word
+ * the caller zeroed ONCE; every call leaves it zero again (a graph replay starts clean).  No block waits for another.
+ * norm_free = 0: exactly zk_adam_step. */
+int zk_adam_step_fold(float* p, const float* g, float* m, float* v, void* shadow_bf16, size_t n, float* hyper,
+                      float* pnorm_out, uint64_t* seed, int norm_free, const int* skip_word, void* workspace,
+                      size_t ws_bytes, uint32_t* arrive, zk_stream_t stream);
 int zk_norm_flag(float* hyper, zk_stream_t stream);
 int zk_cast_f32_bf16(const float* x, void* y, size_t n, zk_stream_t stream);
 int zk_cast_bf16_f32(const void* x, float* y, size_t n, zk_stream_t stream);

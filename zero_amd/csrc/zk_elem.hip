@@ -477,17 +477,17 @@ __global__ void __launch_bounds__(256) k_colsum(const bf16_t* __restrict__ a, in
 // without the shifted rows, skip_L -- and from the encoder's): blockIdx.z = the side, partial rows of side b behind side
 // a's in the workspace; one k_partials_reduce then adds all of them in that order.
 struct ColsumSide { const bf16_t* a; int rows, lda, skip_L; uint32_t sid; int gy; };
-__global__ void __launch_bounds__(256) k_colsum_pair(ColsumSide sa, ColsumSide sb, int N, float* __restrict__ partials, uint32_t thr,
-                                                     float inv_keep, const uint64_t* __restrict__ seedp) {
-  __shared__ float red[32][64 + 1];
-  const ColsumSide& s_ = blockIdx.z == 0 ? sa : sb;
-  if ((int)blockIdx.y >= s_.gy) return;
+__device__ __forceinline__ void colsum_pair_body(const ColsumSide& sa, const ColsumSide& sb, int N, float* __restrict__ partials,
+                                                 uint32_t thr, float inv_keep, const uint64_t* __restrict__ seedp, int bx, int by,
+                                                 int bz, float (*red)[64 + 1]) {
+  const ColsumSide& s_ = bz == 0 ? sa : sb;
+  if (by >= s_.gy) return;
   const bf16_t* __restrict__ a = s_.a;
   const int rows = s_.rows, lda = s_.lda, skip_L = s_.skip_L;
   const int tx = threadIdx.x & 7, ty = threadIdx.x >> 3;
-  const int c0 = blockIdx.x * 64 + tx * 8;
+  const int c0 = bx * 64 + tx * 8;
   const int rpb = (rows + s_.gy - 1) / s_.gy;
-  const int r0 = blockIdx.y * rpb;
+  const int r0 = by * rpb;
   const int r1 = min(rows, r0 + rpb);
   const uint64_t seed = thr ? *seedp : 0;
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -510,13 +510,18 @@ __global__ void __launch_bounds__(256) k_colsum_pair(ColsumSide sa, ColsumSide s
   for (int j = 0; j < 8; ++j) red[ty][tx * 8 + j] = acc[j];
   __syncthreads();
   if (threadIdx.x < 64) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
+    const int c = bx * 64 + threadIdx.x;
     if (c < N) {
       float t = 0.f;
       for (int i = 0; i < 32; ++i) t += red[i][threadIdx.x];
-      partials[(size_t)((blockIdx.z == 0 ? 0 : sa.gy) + blockIdx.y) * N + c] = t;
+      partials[(size_t)((bz == 0 ? 0 : sa.gy) + by) * N + c] = t;
     }
   }
+}
+__global__ void __launch_bounds__(256) k_colsum_pair(ColsumSide sa, ColsumSide sb, int N, float* __restrict__ partials, uint32_t thr,
+                                                     float inv_keep, const uint64_t* __restrict__ seedp) {
+  __shared__ float red[32][64 + 1];
+  colsum_pair_body(sa, sb, N, partials, thr, inv_keep, seedp, blockIdx.x, blockIdx.y, blockIdx.z, red);
 }
 
 // ---- grouped column reductions: every bias gradient / LayerNorm parameter gradient of a group of
@@ -573,10 +578,9 @@ struct ReduceDesc {
   int nblk, nq, H, block_start;
   int bstride, qstride;       // element strides between blocks / quantities; 0 = packed (nq * H, H)
 };
-__global__ void __launch_bounds__(256) k_reduce_grouped(const ReduceDesc* __restrict__ descs, int nprob) {
+__device__ __forceinline__ void reduce_grouped_body(const ReduceDesc* __restrict__ descs, int nprob, int bid,
+                                                    float (*red)[ZK_RED_COLS + 1]) {
   constexpr int NG = 256 / ZK_RED_COLS;
-  __shared__ float red[NG][ZK_RED_COLS + 1];
-  const int bid = blockIdx.x;
   int p = 0;
   {   // the last problem whose first block is <= bid: binary search (a linear scan is one dependent global load per
       // problem -- ~8 us before the first partial is read with the ~80 problems of a whole-step group)
@@ -618,6 +622,10 @@ __global__ void __launch_bounds__(256) k_reduce_grouped(const ReduceDesc* __rest
     for (int i = 0; i < NG; ++i) v += red[i][cl];
     o[c] = v;
   }
+}
+__global__ void __launch_bounds__(256) k_reduce_grouped(const ReduceDesc* __restrict__ descs, int nprob) {
+  __shared__ float red[256 / ZK_RED_COLS][ZK_RED_COLS + 1];
+  reduce_grouped_body(descs, nprob, blockIdx.x, red);
 }
 // Embedding-table gradient without atomics: the host sorts the token rows by id (it owns the
 // ids anyway); one wave per DISTINCT id sums its rows in fp32 and does a single read-modify-write
@@ -703,6 +711,137 @@ __global__ void __launch_bounds__(256) k_embed_bwd_sorted_pair(EmbedBwdSide a, E
                         inv_keep, seedp, s_.sid, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6);
 }
 
+// The tail of the backward pass as ONE launch: the launches behind the weight-gradient GEMM are independent of one
+// another and each is bound by latency (a scatter of ~25 MB in 36 us, ~80 column reductions in 31 us), so they share a grid
+// instead of a stream.  Block ranges take roles, the long-running ones first:
+//   [0, 2 sc)          both embedding-gradient scatters (k_embed_bwd_sorted_pair: side a, then side b)
+//   [.., + red)        the grouped reductions (k_reduce_grouped)
+//   [.., + zb)         zero rows: every row of side b's table whose id is NOT in this batch's sorted uid list is written as
+//                      zeros, so the table needs no zero fill ahead of the backward.  The scatter writes exactly the listed
+//                      rows (accumulate = 0 on that side): the two roles touch disjoint rows and need no order.
+//   [.., + cs)         both sides of the bias column sum (k_colsum_pair; k_partials_reduce finishes as before)
+// Every role runs the device body of the kernel it replaces on the block / wave indices that kernel would have had: the
+// sums keep their order and the results their bits.  No workgroup waits for another.
+#define ZK_TAIL_ZROWS 16     // table rows per wave of the zero-row role
+struct StepTailArgs {
+  EmbedBwdSide ea, eb;
+  ColsumSide ca, cb;
+  const ReduceDesc* rdescs;
+  float* cs_partials;
+  int nred, sc_blocks, red_blocks, z_blocks, cs_gx;
+  int H, zrows;
+  float scale, inv_keep;
+  uint32_t thr;
+};
+__global__ void __launch_bounds__(256) k_step_tail(StepTailArgs t, const uint64_t* __restrict__ seedp) {
+  __shared__ float sm[32 * (64 + 1)];
+  int bid = blockIdx.x;
+  if (bid < 2 * t.sc_blocks) {
+    const bool second = bid >= t.sc_blocks;
+    const EmbedBwdSide& s_ = second ? t.eb : t.ea;
+    const int lb = second ? bid - t.sc_blocks : bid;
+    embed_bwd_sorted_body(s_.rows_sorted, s_.seg, s_.uid, s_.n_uniq_dev, s_.dout, s_.dtable, t.H, t.scale, s_.accumulate, t.thr,
+                          t.inv_keep, seedp, s_.sid, (lb * 256 + (int)threadIdx.x) >> 6, (t.sc_blocks * 256) >> 6);
+    return;
+  }
+  bid -= 2 * t.sc_blocks;
+  if (bid < t.red_blocks) {
+    reduce_grouped_body(t.rdescs, t.nred, bid, reinterpret_cast<float (*)[ZK_RED_COLS + 1]>(sm));
+    return;
+  }
+  bid -= t.red_blocks;
+  if (bid < t.z_blocks) {
+    // one lane per row looks its id up (binary search of the ascending uid list: <= 13 dependent loads for 64 x 64 ids,
+    // once per ZK_TAIL_ZROWS rows); then the wave writes the absent rows, 16 bytes per lane
+    const int lane = threadIdx.x & 63;
+    const int nu = *t.eb.n_uniq_dev;
+    const int* __restrict__ uid = t.eb.uid;
+    const int row0 = (bid * 4 + ((int)threadIdx.x >> 6)) * ZK_TAIL_ZROWS;
+    const int my = row0 + (lane & (ZK_TAIL_ZROWS - 1));
+    int lo = 0, hi = nu;                       // first index with uid[index] >= my
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (uid[mid] < my) lo = mid + 1; else hi = mid;
+    }
+    const bool absent = my < t.zrows && !(lo < nu && uid[lo] == my);
+    const unsigned long long todo = __ballot(absent);
+    const int h4 = t.H >> 2;
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 4
+    for (int j = 0; j < ZK_TAIL_ZROWS; ++j) {
+      if (!((todo >> j) & 1ull)) continue;     // wave-uniform
+      float4* dst = reinterpret_cast<float4*>(t.eb.dtable + (size_t)(row0 + j) * t.H);
+      for (int c = lane; c < h4; c += 64) dst[c] = z;
+    }
+    return;
+  }
+  bid -= t.z_blocks;
+  const int ry = bid / t.cs_gx, bx = bid - ry * t.cs_gx;
+  const int bz = ry >= t.ca.gy ? 1 : 0;
+  colsum_pair_body(t.ca, t.cb, t.H, t.cs_partials, t.thr, t.inv_keep, seedp, bx, bz ? ry - t.ca.gy : ry, bz,
+                   reinterpret_cast<float (*)[64 + 1]>(sm));
+}
+
+// The body of k_loss_tail (below; its comment describes the order of the sums), for a block of any number of waves: a
+// sentence is summed by ONE wave whichever it is, the mean by the first four waves as block_sum<4> adds them -- with EVERY
+// wave going through both barriers of that sum (waves that leave in front of a barrier the others still wait at are not
+// something to rely on).  SC1: ce was written by OTHER workgroups of this launch (the folded form, ce_arrive_tail): every
+// load of it is an agent-scope load, served past this CU's L1.
+template <bool SC1>
+__device__ __forceinline__ void loss_tail_body(const float* ce, const int* __restrict__ ids, float* per_sample,
+                                               float* __restrict__ loss, int B, int L, float* sm) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  for (int b = w; b < B; b += nw) {
+    float a = 0.f, c = 0.f;
+    for (int t = lane; t < L; t += 64) {
+      const float mk = (ids[b * L + t] != 0) ? 1.f : 0.f;
+      const float x = SC1 ? __hip_atomic_load(ce + b * L + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ce[b * L + t];
+      a += x * mk;
+      c += mk;
+    }
+    a = wave_sum(a);
+    c = wave_sum(c);
+    if (lane == 0) per_sample[b] = a / c;
+  }
+  __syncthreads();                       // (the block's own global writes are visible to it behind the barrier)
+  if (loss == nullptr) return;           // (uniform)
+  float a = 0.f;
+  if (threadIdx.x < 256)
+    for (int i = threadIdx.x; i < B; i += 256) a += per_sample[i];
+  a = wave_sum(a);
+  __syncthreads();
+  if (lane == 0 && w < 4) sm[w] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float r = 0.f;
+    for (int i = 0; i < 4; ++i) r += sm[i];            // (block_sum<4>'s order)
+    loss[0] = (B > 0) ? r / (float)B : 0.f;
+  }
+}
+// Cross entropy with the loss tail folded in: per_sample / loss / B / L of k_loss_tail and an arrival counter (a device
+// word, zero before the launch).  Thread 0 of every block has stored its ce value write-through (an agent-scope store);
+// here it drains its stores, takes a ticket with a returning add, and the block that drew the last one runs the tail
+// (and leaves the counter at zero).  The ordering rests on the s_waitcnt below and on write-through stores / agent-scope
+// loads, not on a C++ memory order.  Nobody waits for anybody.
+struct CeTail { float* per_sample; float* loss; unsigned* arrive; int B, L; };
+__device__ __forceinline__ void ce_store(float* ce_out, int r, float v, bool publish) {
+  if (publish) __hip_atomic_store(ce_out + r, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else ce_out[r] = v;
+}
+__device__ __forceinline__ void ce_arrive_tail(const CeTail& t, const float* ce, const int* __restrict__ ids, float* sm) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned k = __hip_atomic_fetch_add(t.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = k == gridDim.x - 1;
+    if (last) __hip_atomic_store(t.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sm[0] = last ? 1.f : 0.f;
+  }
+  __syncthreads();
+  const bool last = sm[0] != 0.f;
+  __syncthreads();
+  if (last) loss_tail_body<true>(ce, ids, t.per_sample, t.loss, t.B, t.L, sm);
+}
 // =====================================================================================
 // K6  label-smoothed cross entropy, fused forward + backward on fp32 logits
 //     util.py:88-103 (soft labels p on gold, q=eps/(V-1) elsewhere, normaliser),
@@ -712,11 +851,10 @@ __global__ void __launch_bounds__(256) k_embed_bwd_sorted_pair(EmbedBwdSide a, E
 //     One block per token row; pass 1 streams the row from HBM (online max/sum), pass 2
 //     re-reads it from L2 and writes bf16 dlogits.
 // =====================================================================================
-__global__ void __launch_bounds__(256) k_ce_fused(
+__device__ __forceinline__ void ce_fused_body(
     const float* __restrict__ logits, const int* __restrict__ ids, const float* __restrict__ w,
-    float* __restrict__ ce_out, bf16_t* __restrict__ dlogits, int V, int ld, float p, float q,
-    float normalizer) {
-  __shared__ float sm[8];
+    float* ce_out, bf16_t* __restrict__ dlogits, int V, int ld, float p, float q,
+    float normalizer, bool publish, float* sm) {
   const int r = blockIdx.x;
   const float* z = logits + (size_t)r * ld;
   const float wr = (w != nullptr) ? w[r] : 0.f;
@@ -745,7 +883,7 @@ __global__ void __launch_bounds__(256) k_ce_fused(
   const float lse = gm + __logf(gs);
   const float zg = z[gold];
   if (threadIdx.x == 0 && ce_out != nullptr)
-    ce_out[r] = lse - p * zg - q * (gsz - zg) - normalizer;
+    ce_store(ce_out, r, lse - p * zg - q * (gsz - zg) - normalizer, publish);
   if (!need_bwd) return;
   bf16_t* d = dlogits + (size_t)r * ld;
   if (wr == 0.f) {
@@ -768,14 +906,22 @@ __global__ void __launch_bounds__(256) k_ce_fused(
     __builtin_nontemporal_store(pk, reinterpret_cast<zk_u32x2*>(d + c));
   }
 }
+__global__ void __launch_bounds__(256) k_ce_fused(
+    const float* __restrict__ logits, const int* __restrict__ ids, const float* __restrict__ w,
+    float* ce_out, bf16_t* __restrict__ dlogits, int V, int ld, float p, float q,
+    float normalizer, CeTail tail) {
+  __shared__ float sm[8];
+  ce_fused_body(logits, ids, w, ce_out, dlogits, V, ld, p, q, normalizer, tail.arrive != nullptr, sm);
+  if (tail.arrive != nullptr) ce_arrive_tail(tail, ce_out, ids, sm);
+}
 
 // Same computation with the whole row held in registers (V <= NV*4096): one HBM read of the
 // logits row, no second pass -- 1024 threads (16 waves) per row.
 template <int NV>
 __global__ void __launch_bounds__(1024, 8) k_ce_fused_reg(
     const float* __restrict__ logits, const int* __restrict__ ids, const float* __restrict__ w,
-    float* __restrict__ ce_out, bf16_t* __restrict__ dlogits, int V, int ld, float p, float q,
-    float normalizer) {
+    float* ce_out, bf16_t* __restrict__ dlogits, int V, int ld, float p, float q,
+    float normalizer, CeTail tail) {
   __shared__ float sm[16];
   __shared__ float bc;
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -831,15 +977,14 @@ __global__ void __launch_bounds__(1024, 8) k_ce_fused_reg(
     for (int i = 0; i < 16; ++i) t += sm[i];
     const float lse = gm + __logf(gs);
     const float zg = z[gold];
-    if (ce_out != nullptr) ce_out[r] = lse - p * zg - q * (t - zg) - normalizer;
+    if (ce_out != nullptr) ce_store(ce_out, r, lse - p * zg - q * (t - zg) - normalizer, tail.arrive != nullptr);
   }
-  if (dlogits == nullptr) return;
   bf16_t* d = dlogits + (size_t)r * ld;
   const float inv = wr / gs;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 1024 + tid) * 4;
-    if (c >= ld) continue;
+    if (dlogits == nullptr || c >= ld) continue;
     float o[4] = {v[i].x * inv, v[i].y * inv, v[i].z * inv, v[i].w * inv};   // exp(-inf)=0 past V
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -849,6 +994,7 @@ __global__ void __launch_bounds__(1024, 8) k_ce_fused_reg(
     }
     *reinterpret_cast<uint2*>(d + c) = make_uint2(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]));
   }
+  if (tail.arrive != nullptr) ce_arrive_tail(tail, ce_out, ids, sm);
 }
 
 // target statistics: mask=(id!=0), w = loss_scale*mask/(len_b*B) (gradient weight of each
@@ -898,24 +1044,7 @@ __global__ void __launch_bounds__(256) k_mean(const float* __restrict__ x, float
 __global__ void __launch_bounds__(1024) k_loss_tail(const float* __restrict__ ce, const int* __restrict__ ids,
                                                     float* __restrict__ per_sample, float* __restrict__ loss, int B, int L) {
   __shared__ float sm[8];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int b = w; b < B; b += 16) {
-    float a = 0.f, c = 0.f;
-    for (int t = lane; t < L; t += 64) {
-      const float mk = (ids[b * L + t] != 0) ? 1.f : 0.f;
-      a += ce[b * L + t] * mk;
-      c += mk;
-    }
-    a = wave_sum(a);
-    c = wave_sum(c);
-    if (lane == 0) per_sample[b] = a / c;
-  }
-  __syncthreads();                       // (the block's own global writes are visible to it behind the barrier)
-  if (loss == nullptr || threadIdx.x >= 256) return;
-  float a = 0.f;
-  for (int i = threadIdx.x; i < B; i += 256) a += per_sample[i];
-  a = block_sum<4>(a, sm);
-  if (threadIdx.x == 0) loss[0] = (B > 0) ? a / (float)B : 0.f;
+  loss_tail_body<false>(ce, ids, per_sample, loss, B, L, sm);
 }
 
 __global__ void __launch_bounds__(256) k_make_mask(const int* __restrict__ ids, float* __restrict__ mask, int n) {
@@ -1245,13 +1374,75 @@ __global__ void __launch_bounds__(256) k_norm_final(const float* __restrict__ pa
 //              of a pass of its own over the 308 MB.  The update is applied whatever the norm turns out to be --
 //              exactly what the reference does without safe_nan (train_op and the norm are fetched together).
 // seed (may be NULL): the per-step dropout seed is advanced here (one launch fewer per step).
+// The finish of k_adam<true> (k_norm_final2 below, or k_adam's last block): gnorm = sqrt(sum gsq) -> hyper[6], the
+// per-update flag hyper[7] and the sticky count hyper[10] of non-finite norms; pnorm = sqrt(sum psq) -> pnorm_out.  One
+// block of 256 threads; thread i adds partials i, i + 256, .. in that order, then block_sum<4>.  SC1: the partials were
+// written by OTHER workgroups of this launch -- every load of them is an agent-scope load (served past this CU's L1).
+template <bool SC1>
+__device__ __forceinline__ void norm_final2_body(const float* psq, const float* gsq, int n, float* __restrict__ hyper,
+                                                 float* __restrict__ pnorm_out, float* sm) {
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    if (SC1) {
+      a += __hip_atomic_load(gsq + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      b += __hip_atomic_load(psq + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (this form always has both)
+    } else {
+      a += gsq[i];
+      if (psq != nullptr) b += psq[i];
+    }
+  }
+  a = block_sum<4>(a, sm);
+  b = block_sum<4>(b, sm);
+  if (threadIdx.x == 0) {
+    const float gn = sqrtf(a);
+    hyper[6] = gn;
+    const bool bad = !(gn == gn) || fabsf(gn) == INFINITY;
+    hyper[7] = bad ? 1.f : 0.f;
+    if (bad) hyper[10] += 1.f;
+    if (pnorm_out != nullptr) pnorm_out[0] = sqrtf(b);
+#ifdef ZK_STEP_STAMPS
+    {
+      const unsigned int i_ = atomicAdd(&zk_step_stamp_n[1], 1u);
+      if (i_ < 4096) zk_step_stamp_buf[4096 + i_] = __builtin_amdgcn_s_memrealtime();
+    }
+#endif
+  }
+}
+// k_adam with an arrival counter: thread 0 publishes the block's two partials (write-through stores, drained before the
+// ticket), takes a ticket with a returning add; true in EVERY thread of the block that drew the last one.  Nobody waits
+// for anybody.  `arrive` is zero before the launch; the last block leaves it zero again (adam_finish).  psq and gsq are
+// both required.  The ordering rests on the s_waitcnt between the write-through (agent-scope) stores and the ticket and
+// on the agent-scope loads of the last block behind the barrier that follows its ticket -- not on a C++ memory order:
+// a release fence here would write the L2 back behind a 300-MB pass.
+__device__ __forceinline__ bool adam_arrive(float* psq, float* gsq, float pv, float gv, unsigned* arrive, float* sm) {
+  __syncthreads();                          // (block_sum's readers of sm are done)
+  if (threadIdx.x == 0) {
+    __hip_atomic_store(psq + blockIdx.x, pv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(gsq + blockIdx.x, gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sm[0] = (t == gridDim.x - 1) ? 1.f : 0.f;
+  }
+  __syncthreads();
+  const bool last = sm[0] != 0.f;
+  __syncthreads();                          // (sm is block_sum's again)
+  return last;
+}
+__device__ __forceinline__ void adam_finish(float* psq, float* gsq, float* __restrict__ hyper, float* __restrict__ pnorm_out,
+                                            unsigned* arrive, float* sm) {
+  norm_final2_body<true>(psq, gsq, (int)gridDim.x, hyper, pnorm_out, sm);      // all four waves, to the end
+  if (threadIdx.x == 0) __hip_atomic_store(arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 template <bool GSQ, int U = 1, bool CONTIG = false>
 __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float* __restrict__ g,
                                               float* __restrict__ m, float* __restrict__ v,
                                               bf16_t* __restrict__ shadow, size_t n,
                                               float* __restrict__ hyper, float* __restrict__ psq,
                                               float* __restrict__ gsq, uint64_t* __restrict__ seed,
-                                              const int* __restrict__ skip_word = nullptr, int nt = 0) {
+                                              const int* __restrict__ skip_word = nullptr, int nt = 0,
+                                              unsigned* arrive = nullptr, float* __restrict__ pnorm_out = nullptr) {
+  // arrive (GSQ only; a device word, zero before the launch): the block that arrives last also does k_norm_final2's work
+  // (hyper[6] / [7] / [10], pnorm_out) -- same partials, same order of additions, one launch fewer per step
   // nt (tuning key 18, A/B): bit 0 = the fp32 parameter / moment STORES are non-temporal (nobody reads them before the next
   // step's update: they need not displace the bf16 shadow -- the next forward's weight operand -- from the L2 / Infinity
   // Cache); bit 1 = their loads as well
@@ -1266,6 +1457,10 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
   // applied -- parameters, moments and shadow stay as they are -- and the step is booked as skipped: the gradient
   // norm is reported as NaN (GSQ: k_norm_final2 turns it into hyper[7] / the sticky hyper[10]; !GSQ: set here).
   if (skip_word != nullptr && *skip_word != 0) {
+    if (GSQ && arrive != nullptr) {
+      if (adam_arrive(psq, gsq, 0.f, __builtin_nanf(""), arrive, sm_)) adam_finish(psq, gsq, hyper, pnorm_out, arrive, sm_);
+      return;
+    }
     if (threadIdx.x == 0) {
       if (psq != nullptr) psq[blockIdx.x] = 0.f;
       if (GSQ && gsq != nullptr) gsq[blockIdx.x] = __builtin_nanf("");
@@ -1357,6 +1552,12 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
     p[i] -= lr * m[i] / (sqrtf(v[i]) + eps);
     if (shadow != nullptr) shadow[i] = f2bf(p[i]);
   }
+  if (GSQ && arrive != nullptr) {
+    pacc = block_sum<4>(pacc, sm_);
+    gacc = block_sum<4>(gacc, sm_);
+    if (adam_arrive(psq, gsq, pacc, gacc, arrive, sm_)) adam_finish(psq, gsq, hyper, pnorm_out, arrive, sm_);
+    return;
+  }
   if (psq != nullptr) {
     pacc = block_sum<4>(pacc, sm_);
     if (threadIdx.x == 0) psq[blockIdx.x] = pacc;
@@ -1366,29 +1567,11 @@ __global__ void __launch_bounds__(256) k_adam(float* __restrict__ p, const float
     if (threadIdx.x == 0) gsq[blockIdx.x] = gacc;
   }
 }
-// finishes k_adam<true>: gnorm = sqrt(sum gsq) -> hyper[6], the per-update flag hyper[7] and the sticky count
-// hyper[10] of non-finite norms; pnorm = sqrt(sum psq) -> pnorm_out.  One block.
+// finishes k_adam<true> as a launch of its own (norm_final2_body above).  One block.
 __global__ void __launch_bounds__(256) k_norm_final2(const float* __restrict__ psq, const float* __restrict__ gsq,
                                                      int n, float* __restrict__ hyper, float* __restrict__ pnorm_out) {
   __shared__ float sm[8];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) { a += gsq[i]; if (psq != nullptr) b += psq[i]; }
-  a = block_sum<4>(a, sm);
-  b = block_sum<4>(b, sm);
-  if (threadIdx.x == 0) {
-    const float gn = sqrtf(a);
-    hyper[6] = gn;
-    const bool bad = !(gn == gn) || fabsf(gn) == INFINITY;
-    hyper[7] = bad ? 1.f : 0.f;
-    if (bad) hyper[10] += 1.f;
-    if (pnorm_out != nullptr) pnorm_out[0] = sqrtf(b);
-#ifdef ZK_STEP_STAMPS
-    {
-      const unsigned int i_ = atomicAdd(&zk_step_stamp_n[1], 1u);
-      if (i_ < 4096) zk_step_stamp_buf[4096 + i_] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
-  }
+  norm_final2_body<false>(psq, gsq, n, hyper, pnorm_out, sm);
 }
 // hyper[6] was written by zk_l2norm on a path whose update does not look at it (per-bucket updates of the
 // data-parallel step): record a non-finite norm in the per-update flag and the sticky count.
@@ -1721,8 +1904,51 @@ int zk_embed_bwd_sorted_pair(const int* rows_a, const int* seg_a, const int* uid
   return 0;
 }
 
-int zk_ce_fused(const float* logits, const int* ids, const float* w, float* ce_out, void* dlogits, int rows,
-                int V, int ld, float label_smooth, hipStream_t stream) {
+// The backward tail in one launch (k_step_tail) + the k_partials_reduce of the bias column sum: what zk_reduce_grouped
+// (red_descs, nred, red_blocks), zk_embed_bwd_sorted_pair and zk_colsum_pair (dbias = colsum(dout_a without the rows
+// r % skip_a == 0) + colsum(dout_b), both [T, H] with ld = H) do, and -- zero_rows_b > 0 -- zeros in every row r <
+// zero_rows_b of dtable_b that the scatter of side b does not write.
+int zk_step_tail(const void* red_descs, int nred, int red_blocks, const int* rows_a, const int* seg_a, const int* uid_a,
+                 const int* n_a, int T_a, const void* dout_a, float* dtable_a, int acc_a, int skip_a, uint32_t sid_a,
+                 const int* rows_b, const int* seg_b, const int* uid_b, const int* n_b, int T_b, const void* dout_b,
+                 float* dtable_b, int acc_b, int skip_b, uint32_t sid_b, int H, float scale, int zero_rows_b, float* dbias,
+                 float drop_p, const uint64_t* seed, void* workspace, size_t ws_bytes, hipStream_t stream) {
+  ZK_CHECK_ARG(H % 8 == 0, "zk_step_tail: H=%d must be a multiple of 8", H);
+  ZK_CHECK_ARG(drop_p == 0.f || seed != nullptr, "zk_step_tail: dropout needs a seed pointer");
+  ZK_CHECK_ARG(dtable_a != dtable_b, "zk_step_tail: the two sides must write different tables");
+  ZK_CHECK_ARG(T_a >= 0 && T_b >= 0, "zk_step_tail: negative row counts (T_a=%d, T_b=%d)", T_a, T_b);
+  ZK_CHECK_ARG(zero_rows_b == 0 || !acc_b, "zk_step_tail: the zero-row role needs an overwriting scatter on side b");
+  ZK_CHECK_ARG(nred == 0 || red_descs != nullptr, "zk_step_tail: %d reductions without descriptors", nred);
+  ZK_CHECK_ARG(ws_bytes >= zk_colsum_workspace(T_a, H) + zk_colsum_workspace(T_b, H), "zk_step_tail: workspace too small");
+  StepTailArgs t;
+  t.ea = EmbedBwdSide{rows_a, seg_a, uid_a, n_a, (const bf16_t*)dout_a, dtable_a, acc_a, sid_a};
+  t.eb = EmbedBwdSide{rows_b, seg_b, uid_b, n_b, (const bf16_t*)dout_b, dtable_b, acc_b, sid_b};
+  t.ca = ColsumSide{(const bf16_t*)dout_a, T_a, H, skip_a, sid_a, zk_colsum_rowchunks(T_a)};
+  t.cb = ColsumSide{(const bf16_t*)dout_b, T_b, H, skip_b, sid_b, zk_colsum_rowchunks(T_b)};
+  t.rdescs = (const ReduceDesc*)red_descs;
+  t.cs_partials = (float*)workspace;
+  t.nred = nred;
+  const int mx = T_a > T_b ? T_a : T_b;
+  t.sc_blocks = (mx + 3) / 4 > 2048 ? 2048 : (mx + 3) / 4;       // (the grid of zk_embed_bwd_sorted_pair, per side)
+  t.red_blocks = nred > 0 ? red_blocks : 0;
+  t.z_blocks = (zero_rows_b + 4 * ZK_TAIL_ZROWS - 1) / (4 * ZK_TAIL_ZROWS);
+  t.cs_gx = (H + 63) / 64;
+  t.H = H;
+  t.zrows = zero_rows_b;
+  t.scale = scale;
+  t.thr = drop_p > 0.f ? zk_drop_threshold(drop_p) : 0;
+  t.inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
+  const int cs_blocks = t.cs_gx * (t.ca.gy + t.cb.gy);
+  hipLaunchKernelGGL(k_step_tail, dim3(2 * t.sc_blocks + t.red_blocks + t.z_blocks + cs_blocks), dim3(256), 0, stream, t, seed);
+  ZK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_partials_reduce, dim3((H + 15) / 16, 1), dim3(256), 0, stream, (const float*)workspace,
+                     t.ca.gy + t.cb.gy, 1, H, dbias, (float*)nullptr, (float*)nullptr, 0);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+static int ce_fused_launch(const float* logits, const int* ids, const float* w, float* ce_out, void* dlogits, int rows,
+                           int V, int ld, float label_smooth, CeTail tail, hipStream_t stream) {
   ZK_CHECK_ARG(ld % 4 == 0 && ld >= V, "zk_ce_fused: ld=%d must be a multiple of 4 and >= V=%d", ld, V);
   if (rows == 0) return 0;
   float p = 1.f, q = 0.f, normalizer = 0.f;
@@ -1734,15 +1960,31 @@ int zk_ce_fused(const float* logits, const int* ids, const float* w, float* ce_o
   }
   if (ld <= 8 * 4096 && ld > 4 * 4096)
     hipLaunchKernelGGL(k_ce_fused_reg<8>, dim3(rows), dim3(1024), 0, stream, logits, ids, w, ce_out,
-                       (bf16_t*)dlogits, V, ld, p, q, normalizer);
+                       (bf16_t*)dlogits, V, ld, p, q, normalizer, tail);
   else if (ld <= 4 * 4096 && ld > 4096)
     hipLaunchKernelGGL(k_ce_fused_reg<4>, dim3(rows), dim3(1024), 0, stream, logits, ids, w, ce_out,
-                       (bf16_t*)dlogits, V, ld, p, q, normalizer);
+                       (bf16_t*)dlogits, V, ld, p, q, normalizer, tail);
   else
     hipLaunchKernelGGL(k_ce_fused, dim3(rows), dim3(256), 0, stream, logits, ids, w, ce_out, (bf16_t*)dlogits,
-                       V, ld, p, q, normalizer);
+                       V, ld, p, q, normalizer, tail);
   ZK_LAUNCH_CHECK();
   return 0;
+}
+int zk_ce_fused(const float* logits, const int* ids, const float* w, float* ce_out, void* dlogits, int rows,
+                int V, int ld, float label_smooth, hipStream_t stream) {
+  return ce_fused_launch(logits, ids, w, ce_out, dlogits, rows, V, ld, label_smooth, CeTail{nullptr, nullptr, nullptr, 0, 0},
+                         stream);
+}
+// zk_ce_fused + zk_loss_reduce in one launch: the block that arrives last (a returning add on `arrive`, a device word the
+// caller zeroed once; every call leaves it zero) forms per_sample [B] and loss (may be NULL) as k_loss_tail does, same
+// code and order.  ids [B, L], rows = B * L.
+int zk_ce_fused_tail(const float* logits, const int* ids, const float* w, float* ce_out, void* dlogits, int rows,
+                     int V, int ld, float label_smooth, float* per_sample, float* loss, int B, int L, uint32_t* arrive,
+                     hipStream_t stream) {
+  ZK_CHECK_ARG(ce_out != nullptr && per_sample != nullptr && arrive != nullptr, "zk_ce_fused_tail: ce_out, per_sample and arrive are required");
+  ZK_CHECK_ARG(B >= 1 && L >= 1 && rows == B * L, "zk_ce_fused_tail: rows=%d must be B*L = %d*%d", rows, B, L);
+  return ce_fused_launch(logits, ids, w, ce_out, dlogits, rows, V, ld, label_smooth,
+                         CeTail{per_sample, loss, (unsigned*)arrive, B, L}, stream);
 }
 
 int zk_target_stats(const int* ids, float* mask, float* w, int B, int L, float loss_scale,
@@ -1912,9 +2154,9 @@ size_t zk_adam_step_workspace(void) { return 2 * 2048 * sizeof(float); }
 // safe_nan): gradient norm (-> hyper[6], flag hyper[7], sticky count hyper[10]), TF1 Adam, bf16 shadow and parameter
 // norm in ONE pass over the buffers + a one-block finish.  norm_free = 0: hyper[6] must already hold the gradient norm
 // (zk_l2norm); the update is skipped when it is not finite / above hyper[9].  seed (device uint64, may be NULL) += 1.
-int zk_adam_step(float* p, const float* g, float* m, float* v, void* shadow, size_t n, float* hyper,
-                 float* pnorm_out, uint64_t* seed, int norm_free, const int* skip_word, void* workspace, size_t ws_bytes,
-                 hipStream_t stream) {
+static int adam_step_launch(float* p, const float* g, float* m, float* v, void* shadow, size_t n, float* hyper,
+                            float* pnorm_out, uint64_t* seed, int norm_free, const int* skip_word, void* workspace,
+                            size_t ws_bytes, unsigned* arrive, hipStream_t stream) {
   ZK_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
                "zk_adam_step: buffers must be 16-byte aligned");
   ZK_CHECK_ARG(ws_bytes >= zk_adam_step_workspace(), "zk_adam_step: workspace too small");
@@ -1928,15 +2170,16 @@ int zk_adam_step(float* p, const float* g, float* m, float* v, void* shadow, siz
     // (default 2); tuning key 10: blocks (default 512; 0 = 2048).  scripts/adam_bench.py: 405 -> 391 us on one box
     // (fewer open DRAM pages); the box-to-box spread of this pass is larger than that (405 .. 477 us)
     const int gb = g_tune[10] > 0 && g_tune[10] <= 2048 ? (grid < g_tune[10] ? grid : g_tune[10]) : grid;
-#define ZK_ADAM_L(...) hipLaunchKernelGGL((k_adam<__VA_ARGS__>), dim3(gb), dim3(256), 0, stream, p, g, m, v, (bf16_t*)shadow, n, hyper, psq, gsq, seed, skip_word, g_tune[18])
+#define ZK_ADAM_L(...) hipLaunchKernelGGL((k_adam<__VA_ARGS__>), dim3(gb), dim3(256), 0, stream, p, g, m, v, (bf16_t*)shadow, n, hyper, psq, gsq, seed, skip_word, g_tune[18], arrive, pnorm_out)
     if (g_tune[9] == 1) ZK_ADAM_L(true, 1, true);
     else if (g_tune[9] == 2) ZK_ADAM_L(true, 2, true);
     else if (g_tune[9] == 4) ZK_ADAM_L(true, 4, true);
     else ZK_ADAM_L(true, 1, false);
 #undef ZK_ADAM_L
     ZK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_norm_final2, dim3(1), dim3(256), 0, stream, (const float*)psq, (const float*)gsq, gb, hyper,
-                       pnorm_out);
+    if (arrive == nullptr)      // (else the pass's last block has done it)
+      hipLaunchKernelGGL(k_norm_final2, dim3(1), dim3(256), 0, stream, (const float*)psq, (const float*)gsq, gb, hyper,
+                         pnorm_out);
   } else {
     hipLaunchKernelGGL(k_adam<false>, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)shadow, n, hyper, psq,
                        (float*)nullptr, seed, skip_word);
@@ -1945,6 +2188,22 @@ int zk_adam_step(float* p, const float* g, float* m, float* v, void* shadow, siz
   }
   ZK_LAUNCH_CHECK();
   return 0;
+}
+int zk_adam_step(float* p, const float* g, float* m, float* v, void* shadow, size_t n, float* hyper,
+                 float* pnorm_out, uint64_t* seed, int norm_free, const int* skip_word, void* workspace, size_t ws_bytes,
+                 hipStream_t stream) {
+  return adam_step_launch(p, g, m, v, shadow, n, hyper, pnorm_out, seed, norm_free, skip_word, workspace, ws_bytes, nullptr,
+                          stream);
+}
+// zk_adam_step whose norm_free form is ONE launch: the block of the pass that arrives last (a returning add on `arrive`)
+// finishes the norms; `arrive` = a device word the caller zeroed once and never touches (every call leaves it zero).
+// norm_free = 0: as zk_adam_step.
+int zk_adam_step_fold(float* p, const float* g, float* m, float* v, void* shadow, size_t n, float* hyper,
+                      float* pnorm_out, uint64_t* seed, int norm_free, const int* skip_word, void* workspace,
+                      size_t ws_bytes, uint32_t* arrive, hipStream_t stream) {
+  ZK_CHECK_ARG(arrive != nullptr && ((uintptr_t)arrive & 3) == 0, "zk_adam_step_fold: arrive must be a device word");
+  return adam_step_launch(p, g, m, v, shadow, n, hyper, pnorm_out, seed, norm_free, skip_word, workspace, ws_bytes,
+                          norm_free ? (unsigned*)arrive : nullptr, stream);
 }
 int zk_norm_flag(float* hyper, hipStream_t stream) {
   ZK_CHECK_ARG(hyper != nullptr, "zk_norm_flag: hyper is required");

@@ -486,12 +486,14 @@ class Engine(object):
         dev, n, total = ent
         self.lib.call("zk_gemm_grouped", dev.data_ptr(), n, total, ta, tb, code, self.stream)
 
-    def reductions_grouped(self, colsums, ln_parts, rpr_parts=()):
+    def reductions_grouped(self, colsums, ln_parts, rpr_parts=(), defer_reduce=False):
         """colsums: [(Mat dY, out fp32 view, private fp32 partial buffer)];
         ln_parts: [(partials buffer, rows, H, dgamma, dbeta, dbias_prev-or-None[, True: written by gemm_ln_bwd])];
         rpr_parts: [(partials fp32 [slices][2][64*64] (device address), slices, n, d rpr_k, d rpr_v)] -- the table-gradient
         partials the folded relative-position backward left behind (attn_bwd(defer_tables=...)).
-        Two launches: column partial sums of every dY, then every final reduction."""
+        Two launches: column partial sums of every dY, then every final reduction.
+        defer_reduce: the second launch is not issued; its (descriptors, problems, blocks) are returned for
+        :meth:`step_tail`, which runs it as one role of the backward's tail launch."""
         key = tuple((a.ptr, o.data_ptr()) for a, o, _ in colsums) + \
             tuple((lp[0].data_ptr(), lp[1], lp[6] if len(lp) > 6 else None, lp[3].data_ptr(), lp[4].data_ptr(), hip.ptr(lp[5])) for lp in ln_parts) + \
             tuple((pp, ns, n, dk.data_ptr()) for pp, ns, n, dk, _ in rpr_parts)
@@ -541,6 +543,8 @@ class Engine(object):
         cdev, nc, cblocks, rdev, nr, rblocks = ent
         if nc:
             self.lib.call("zk_colsum_grouped", cdev.data_ptr(), nc, cblocks, self.stream)
+        if defer_reduce:
+            return (rdev, nr, rblocks)
         if nr:
             self.lib.call("zk_reduce_grouped", rdev.data_ptr(), nr, rblocks, self.stream)
 
@@ -853,6 +857,23 @@ class Engine(object):
         self.lib.call("zk_colsum_pair", A.ptr, A.rows, A.ld, skip_a, sid_a, B.ptr, B.rows, B.ld, skip_b, sid_b, A.cols,
                       out.data_ptr(), float(drop_p), self.seed.data_ptr(), ws.data_ptr(), ws.numel(), self.stream)
 
+    def step_tail(self, red, sort_a, dout_a, dtable_a, acc_a, skip_a, sid_a, sort_b, dout_b, dtable_b, acc_b, skip_b, sid_b,
+                  H, dbias, zero_rows_b=0, drop_p=0.0):
+        """The backward's tail in one launch (zk_step_tail): the deferred reductions `red` (reductions_grouped(...,
+        defer_reduce=True), or None), both embedding-gradient scatters, both sides of the bias column sum (dbias) and --
+        zero_rows_b > 0 -- zeros in the rows of dtable_b that this batch does not touch."""
+        rdev, nr, rblocks = red if red is not None else (None, 0, 0)
+        assert dout_a.ld == H and dout_b.ld == H and dout_a.rows == sort_a["max_uniq"] and dout_b.rows == sort_b["max_uniq"]
+        ws_bytes = self.lib.query("zk_colsum_workspace", dout_a.rows, H) + self.lib.query("zk_colsum_workspace", dout_b.rows, H)
+        ws = self.workspace(ws_bytes)
+        self.lib.call("zk_step_tail", rdev.data_ptr() if nr else None, nr, rblocks,
+                      sort_a["rows"].data_ptr(), sort_a["seg"].data_ptr(), sort_a["uid"].data_ptr(), sort_a["n"].data_ptr(),
+                      dout_a.rows, dout_a.ptr, dtable_a.data_ptr(), 1 if acc_a else 0, skip_a, sid_a,
+                      sort_b["rows"].data_ptr(), sort_b["seg"].data_ptr(), sort_b["uid"].data_ptr(), sort_b["n"].data_ptr(),
+                      dout_b.rows, dout_b.ptr, dtable_b.data_ptr(), 1 if acc_b else 0, skip_b, sid_b, H, float(H) ** 0.5,
+                      int(zero_rows_b), dbias.data_ptr(), float(drop_p), self.seed.data_ptr(), ws.data_ptr(), ws.numel(),
+                      self.stream)
+
     # ---- residual + layer norm (func.py:289-303, 321-324) -------------------------
     def add_ln_fwd(self, x, y, gamma, beta, out, sum_out=None, mean=None, rstd=None, drop_p=0.0, sid=0):
         self.lib.call("zk_add_ln_fwd", x.ptr, y.ptr if y is not None else None, gamma.data_ptr(),
@@ -878,7 +899,22 @@ class Engine(object):
                       hip.ptr(dbias_prev), self.stream)
 
     # ---- loss (util.py:88-103; transformer.py:198-216) ------------------------------
+    def ce_tail_next(self, per_sample, loss, B, L):
+        """The NEXT ce_fused call also forms the per-sentence loss and its mean (zk_ce_fused_tail: its last block does
+        loss_reduce's work); no loss_reduce call follows it.  (A state and not an argument: ce_fused keeps the signature
+        its callers and wrappers use.)"""
+        self._ce_tail = (per_sample, loss, B, L)
+
     def ce_fused(self, logits, ids, w, ce, dlogits, rows, V, label_smooth):
+        tail, self._ce_tail = self.__dict__.get("_ce_tail"), None
+        if tail is not None:
+            if self.__dict__.get("_ce_arrive") is None:
+                self._ce_arrive = torch.zeros(4, dtype=torch.int32, device=self.device)
+            per_sample, loss, B, L = tail
+            self.lib.call("zk_ce_fused_tail", logits.ptr, ids.data_ptr(), hip.ptr(w), hip.ptr(ce),
+                          dlogits.ptr if dlogits is not None else None, rows, V, logits.ld, float(label_smooth),
+                          per_sample.data_ptr(), hip.ptr(loss), B, L, self._ce_arrive.data_ptr(), self.stream)
+            return
         self.lib.call("zk_ce_fused", logits.ptr, ids.data_ptr(), hip.ptr(w), hip.ptr(ce),
                       dlogits.ptr if dlogits is not None else None, rows, V, logits.ld, float(label_smooth),
                       self.stream)

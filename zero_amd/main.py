@@ -73,7 +73,7 @@ class Trainer(object):
         from zero_amd.models._factory import get_core
         self.core = get_core(params, params.model_name, initializer)
         self.store = self.core.store
-        self.train_op = TrainOp(self.store, params, self.core.eng)
+        self.train_op = TrainOp(self.store, params, self.core.eng, fold_final=getattr(self.core, "merge_small", False))      # (the Transformer cores' switch)
         self.reducer = parallel.GradientAllReduce(self.store)
         self.lr = lrs.get_lr(params)
         self.global_step = 0

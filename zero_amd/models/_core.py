@@ -103,6 +103,8 @@ class TransformerCore(object):
         self._ln_next = None           # the LayerNorm below the sub-layer whose backward is being issued
         self._pending_rpr = []         # (partials address, slices, n, d rpr_k, d rpr_v): table gradients of the folded backward
         self._pending_adds = []        # (fp32 gradient view, fp32 temporary): dst += src after the flush
+        self._tail_defer = False       # backward() on the one-launch tail: _flush_wgrads leaves the final reductions ...
+        self._tail_red = None          # ... here (descriptors, problems, blocks) for zk_step_tail
         self._mem_segs = []            # (dK or dV, W) pairs of the cross-attention memory side (see _finish_mem_grad)
         # encoder-output gradient by one K-segmented GEMM (needs the MFMA path: H a multiple of 64, aligned rows)
         self.kseg_mem = True
@@ -119,6 +121,8 @@ class TransformerCore(object):
         self.sync_ln_mode = os.environ.get("ZERO_HIP_SYNC_LN", "1") != "0"
         # round 6: small launches of the step merged pairwise (both input embeddings; their two gradient scatters; the two
         # bias column sums; per-sentence loss + mean): ZERO_HIP_MERGE_SMALL=0 restores the round-5 launches (A/B, tests)
+        # Since then also the backward's tail: grouped reductions, both scatters, the bias column sums and the zero rows of
+        # the source table as ONE launch (zk_step_tail) instead of three launches and a zero fill.
         self.merge_small = os.environ.get("ZERO_HIP_MERGE_SMALL", "1") != "0"
         if self.eng.device.type == "cuda":
             self.eng.lib.raw("zk_tune")(16, 0 if self.merge_small else 1)      # (bit 0: per-sentence loss + mean as two launches)
@@ -144,7 +148,16 @@ class TransformerCore(object):
         if self._pending_colsums or self._pending_lnred or self._pending_rpr:
             cs, ln, rp = self._pending_colsums, self._pending_lnred, self._pending_rpr
             self._pending_colsums, self._pending_lnred, self._pending_rpr = [], [], []
-            self.eng.reductions_grouped(cs, ln, rp)
+            if self._tail_defer:
+                # (the final reductions run as one role of the backward's tail launch, backward(): zk_step_tail)
+                assert self._tail_red is None
+                self._tail_red = self.eng.reductions_grouped(cs, ln, rp, defer_reduce=True)
+            else:
+                self.eng.reductions_grouped(cs, ln, rp)
+        if not self._tail_defer:
+            self._flush_adds()
+
+    def _flush_adds(self):
         if self._pending_adds:
             adds = self._pending_adds
             self._pending_adds = []
@@ -745,10 +758,15 @@ class TransformerCore(object):
         else:
             e.gemm(feat, E, logits, Tt, self.V, self.H, 0, 1)
         dlogits = e.mat("dlogits", Tt, self.Vpad) if need_grad else None
-        e.ce_fused(logits, batch["tgt"], w if need_grad else None, ce, dlogits, Tt, self.V, label_smooth)
         per_sample = e.buf("per_sample", (B,), F32)
         loss = e.buf("loss", (1,), F32)
-        e.loss_reduce(ce, batch["tgt"], per_sample, loss, B, Lt)
+        if self.merge_small and B > 0 and need_grad:
+            # the training step: the cross entropy's last block forms them, no launch of their own (scoring keeps its two)
+            e.ce_tail_next(per_sample, loss, B, Lt)
+            e.ce_fused(logits, batch["tgt"], w if need_grad else None, ce, dlogits, Tt, self.V, label_smooth)
+        else:
+            e.ce_fused(logits, batch["tgt"], w if need_grad else None, ce, dlogits, Tt, self.V, label_smooth)
+            e.loss_reduce(ce, batch["tgt"], per_sample, loss, B, Lt)
         return loss, per_sample, logits, dlogits
 
     def forward(self, batch, train=False, save=False, label_smooth=None):
@@ -796,7 +814,17 @@ class TransformerCore(object):
         st = self.store
         # embedding tables receive dense gradients (zero rows for unseen ids): untouched rows must
         # read as zero.  The softmax table is fully overwritten by its wgrad GEMM instead.
-        if self.src_emb != self.soft_emb:
+        # One rank, tables of their own, no accumulation over micro steps: the tail launch writes the untouched rows of the
+        # source table itself (zk_step_tail's zero-row role) and the 65-MB zero fill is not issued.
+        tail = self.group_all and self.merge_small and self.src_emb != self.tgt_emb and self.src_emb != self.soft_emb and \
+            int(hp.update_cycle) == 1
+        self._tail_defer, self._tail_red = tail, None
+        # (on this path a layer's bias and LayerNorm-parameter gradients are final only behind the tail launch: its keys
+        # are reported there, not behind the weight-gradient launch)
+        report, held = on_ready, []
+        if tail:
+            on_ready = held.append
+        if self.src_emb != self.soft_emb and not tail:
             e.zero(st.g(self.src_emb))
         if self.tgt_emb != self.soft_emb and self.tgt_emb != self.src_emb:
             e.zero(st.g(self.tgt_emb))
@@ -940,13 +968,13 @@ class TransformerCore(object):
                 ready_d, ready_e = [], []
         dxs = Q[cur]
         # round 6 (one rank, different tables): the two gradient scatters as one launch, the two bias column sums as one pair
-        pair = self.group_all and self.merge_small and self.src_emb != self.tgt_emb
+        pair = self.group_all and self.merge_small and self.src_emb != self.tgt_emb and not tail
         if self.group_all:
             if ready_d:                            # a model without encoder layers
                 self._flush_wgrads()
                 for key in ready_d:
                     on_ready(key)
-            if not pair:
+            if not pair and not tail:
                 tgt_embed_grads()   # after the (single) grouped launch that overwrote the shared softmax table
                 tables_ready()
 
@@ -961,7 +989,22 @@ class TransformerCore(object):
             e.embed_bwd_sorted_pair(batch["tgt_sort"], dxt, st.g(self.tgt_emb), self.tgt_emb == self.soft_emb, 9002,
                                     batch["src_sort"], dxs, st.g(self.src_emb), False, 9001, H, drop_p=hp.dropout)
             e.colsum_pair(dxt, Lt, 9002, dxs, 0, 9001, st.g("bias"), drop_p=hp.dropout)
-        if pair:
+        if tail:
+            # reductions | scatters | bias column sums | zero rows of the source table: independent of one another, one grid
+            # (behind the weight-gradient launch: the target scatter may add onto the softmax table that launch wrote)
+            red, self._tail_red, self._tail_defer = self._tail_red, None, False
+            gsrc = st.g(self.src_emb)
+            e.step_tail(red, batch["tgt_sort"], dxt, st.g(self.tgt_emb), self.tgt_emb == self.soft_emb, Lt, 9002,
+                        batch["src_sort"], dxs, gsrc, False, 0, 9001, H, st.g("bias"), zero_rows_b=gsrc.shape[0],
+                        drop_p=hp.dropout)
+            self._flush_adds()
+            on_ready = report
+            for key in held:
+                on_ready(key)
+            tables_ready()
+            on_ready("bias")
+            on_ready(self.src_emb)
+        elif pair:
             both_embed_grads()
             tables_ready()
             on_ready("bias")

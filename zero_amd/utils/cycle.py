@@ -24,7 +24,7 @@ from zero_amd import hip
 
 
 class TrainOp(object):
-    def __init__(self, store, params, engine):
+    def __init__(self, store, params, engine, fold_final=False):
         self.store, self.hp, self.eng = store, params, engine
         dev = store.device
         # [0:6] host scalars, 6 gnorm, 7 skipped (this update), 8 ema decay, 9 gnorm bound, 10 sticky count of
@@ -41,6 +41,10 @@ class TrainOp(object):
         if getattr(params, "ema_decay", -1.) > 0.:
             self.ema = store.master.clone()      # shadows start at the variables' initial values
         self.pnorm = torch.zeros(1, dtype=torch.float32, device=dev)
+        # fold_final (the caller's TransformerCore.merge_small): the norm finish of the norm-free update by the Adam pass's
+        # last block (zk_adam_step_fold) instead of a launch of its own; _arrive = its arrival counter, zeroed here once
+        self.fold_final = bool(fold_final)
+        self._arrive = torch.zeros(4, dtype=torch.int32, device=dev)
         self.count = 0
         _lib = hip.lib()
         self._ws = torch.empty(max(_lib.query("zk_norm_workspace") * 2, _lib.query("zk_adam_step_workspace")),
@@ -124,11 +128,12 @@ class TrainOp(object):
             lib.call("zk_l2norm", st.grad.data_ptr(), st.numel, scale, self.hyper.data_ptr() + 6 * 4,
                      self._ws.data_ptr(), self._ws.numel(), s)
         # parameter norm (cycle.py:95) is accumulated inside the Adam pass over the same data
-        lib.call("zk_adam_step", st.master.data_ptr(), st.grad.data_ptr(), st.m.data_ptr(), st.v.data_ptr(),
-                 st.shadow.data_ptr(), st.numel, self.hyper.data_ptr(), self.pnorm.data_ptr(),
-                 self.eng.seed.data_ptr() if advance_seed else None, 1 if norm_free else 0,
+        fold = self.fold_final and norm_free
+        lib.call("zk_adam_step_fold" if fold else "zk_adam_step", st.master.data_ptr(), st.grad.data_ptr(),
+                 st.m.data_ptr(), st.v.data_ptr(), st.shadow.data_ptr(), st.numel, self.hyper.data_ptr(),
+                 self.pnorm.data_ptr(), self.eng.seed.data_ptr() if advance_seed else None, 1 if norm_free else 0,
                  self.eng.sync_ln_err_ptr(),      # a step whose in-launch exchange gave up is skipped ON the device
-                 self._ws.data_ptr(), self._ws.numel(), s)
+                 self._ws.data_ptr(), self._ws.numel(), *(((self._arrive.data_ptr(),) if fold else ()) + (s,)))
         if self.ema is not None:
             lib.call("zk_ema", self.ema.data_ptr(), st.master.data_ptr(), self.hyper.data_ptr(), st.numel, s)
 
