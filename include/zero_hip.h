@@ -426,6 +426,8 @@ int zk_dropout_mask(float* out, size_t n, float drop_p, const uint64_t* seed, ui
 int zk_seed_advance(uint64_t* seed, uint64_t inc, zk_stream_t stream);
 
 /* ---- search.py:143-176 decode step tail (see zk_decode.hip) */
+/* Precondition of zk_beam_topk / zk_beam_topk_advance and their EOS-ban scalars (forbid_id / forbid_value, stepbuf[2]): the
+   logits are finite everywhere; what the kernels return for inf or NaN logits is undefined. */
 size_t zk_beam_topk_workspace(int B, int K, int k2);
 int zk_beam_topk(const float* logits, const float* prev_log_probs, float* topk_scores, int* topk_index, int B,
                  int K, int V, int ld, int k2, float temperature, float length_penalty, int forbid_id,

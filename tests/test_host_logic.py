@@ -130,21 +130,17 @@ def test_beam_host_step_in_c_matches_the_numpy_bookkeeping():
     ties, EOS symbols and length caps, several steps in a row."""
     import ctypes
     from zero_amd import hip
+    from tests.beam_ref import book_init, book_stop, book_ref
     lib = hip.lib()
     f32 = np.float32
-    F32_MIN = np.finfo(np.float32).min
     rng = np.random.default_rng(5)
     B, K, V, eos, pad, alpha = 5, 3, 50, 2, 0, 0.6
     Tcap = 12
     mtl = np.array([3, 9, 9, 2, 9], dtype=f32); mtl_i = mtl.astype(np.int32)
 
-    def top_k(x, k):
-        idx = np.argsort(-x, axis=-1, kind="stable")[..., :k]
-        return np.take_along_axis(x, idx, axis=-1), idx
-    # numpy state
-    seq = np.full((B, K, 1), pad, dtype=np.int64); fin_seq = np.zeros_like(seq)
-    log_probs = np.tile(np.array([[0.] + [F32_MIN] * (K - 1)], dtype=f32), (B, 1)); scores = np.zeros_like(log_probs)
-    fin_scores = np.full((B, K), F32_MIN, dtype=f32); fin_flags = np.zeros((B, K), dtype=bool)
+    # numpy state (tests/beam_ref.py book_init / book_stop / book_ref: the statements of zero_amd/search.py)
+    st = book_init(B, K, pad)
+    log_probs, scores, fin_scores = st["log_probs"], st["scores"], st["fin_scores"]
     # C state
     c_seq = np.full((B, K, Tcap), pad, dtype=np.int32); c_fin = np.zeros((B, K, Tcap), dtype=np.int32)
     c_lp = log_probs.copy(); c_sc = scores.copy(); c_fs = fin_scores.copy(); c_ff = np.zeros((B, K), dtype=np.uint8)
@@ -152,8 +148,7 @@ def test_beam_host_step_in_c_matches_the_numpy_bookkeeping():
     P = lambda a: ctypes.c_void_p(a.ctypes.data)
     for time in range(8):
         max_lp = np.power((f32(5.) + mtl) / f32(6.), f32(alpha)).astype(f32)
-        worst = (fin_scores * fin_flags.astype(f32)).min(axis=1) + (f32(1.) - fin_flags.any(axis=1).astype(f32)) * F32_MIN
-        want_stop = bool((worst > log_probs[:, 0] / max_lp).all()) or not bool((time < mtl_i).any())
+        want_stop = book_stop(st, max_lp, mtl_i, time)[0]
         got_stop = lib.raw("zk_beam_host_should_stop")(B, K, P(c_lp), P(c_fs), P(c_ff), P(mtl), P(mtl_i), time, alpha)
         assert bool(got_stop) == want_stop
         if want_stop:
@@ -164,21 +159,9 @@ def test_beam_host_step_in_c_matches_the_numpy_bookkeeping():
         ti = rng.integers(0, K * V, (B, 2 * K)).astype(np.int32)
         ti[1, 0] = 1 * V + eos; ti[2, 3] = 0 * V + eos                   # some EOS symbols
         # ---- numpy (search.py:168-228 as in zero_amd/search.py)
-        beam_idx = ti.astype(np.int64) // V; sym = ti.astype(np.int64) % V
-        bpos = np.arange(B)[:, None]
-        curr_seq = np.concatenate([seq[bpos, beam_idx], sym[:, :, None]], axis=2)
-        curr_fin = (sym == eos) | (time >= mtl_i)[:, None]
-        with np.errstate(over="ignore"):
-            alive_scores, alive_idx = top_k(ts + curr_fin.astype(f32) * F32_MIN, K)
-            alive_lp = (alive_scores * penalty).astype(f32)
-            cfs = ts + (f32(1.) - curr_fin.astype(f32)) * F32_MIN
-        all_flags = np.concatenate([fin_flags, curr_fin], axis=1); all_scores = np.concatenate([fin_scores, cfs], axis=1)
-        fin_scores, fin_idx = top_k(all_scores, K)
-        fin_flags = all_flags[bpos, fin_idx]
-        all_seq = np.concatenate([np.concatenate([fin_seq, np.full((B, K, 1), pad, dtype=seq.dtype)], axis=2), curr_seq], axis=1)
-        fin_seq = all_seq[bpos, fin_idx]
-        flat = (np.arange(B)[:, None] * K + beam_idx[bpos, alive_idx]).reshape(-1)
-        seq, log_probs, scores = curr_seq[bpos, alive_idx], alive_lp, alive_scores
+        st = book_ref(st, ts, ti, time, V, mtl_i, eos, pad, penalty)
+        seq, fin_seq, log_probs, scores = st["seq"], st["fin_seq"], st["log_probs"], st["scores"]
+        fin_scores, fin_flags, flat = st["fin_scores"], st["fin_flags"], st["flat_idx"]
         # ---- C
         rc = lib.raw("zk_beam_host_step")(B, K, V, Tcap, time, P(ts), P(ti), P(c_seq), P(c_fin), P(c_lp), P(c_sc), P(c_fs),
                                           P(c_ff), P(mtl_i), eos, pad, float(penalty), P(c_idx), P(c_tok))
