@@ -797,6 +797,24 @@ int zk_rnn_gru_out(const void* rh, int ldr, const void* Uh, int ldu, const float
 int zk_f32_rnn_gru_out(const float* rh, int ldr, const float* Uh, int ldu, const float* bh, const float* xh, int ldx,
                        const float* z, int ldz, const float* h_prev, int ldh, int n_prev, const int* idx, const float* mask,
                        int ldm, float* out, int ldo, float* out_copy, int ldc, int R, int H, zk_stream_t stream);
+/* The ff product of ONE deepnmt layer with its bias and residual add (models/deepnmt.py:73-79 in the encoder, 166-172 in the
+ * decoder: y = func.linear(outputs, embed_size, ln=False, scope="ff"), func.py:14-65; x = func.residual_fn(x, y), func.py:321-324
+ * without dropout; layer_norm off, so the stream is never re-normalised) in ONE launch:
+ *   zk_rnn_ff_residual   out[r, :] = x[r, :] + (a[r, :] W + b);   out_copy = the same in the storage type.
+ *                        a [R, K] and W [K, N] (bf16 shadow / fp32 master) of the storage type; b fp32 [N]; x and out fp32
+ *                        [R, N]: the residual stream is fp32 in BOTH forms, only the matrix-core operands are bf16; out_copy
+ *                        (may be NULL) [R, N] of the storage type.  Every operand has its own row stride, so out_copy can be a
+ *                        column slice of a wider operand buffer.  out == x with ldo == ldx is allowed (in place: an element is
+ *                        read and written by the one lane that owns it); any other overlap of out with x is refused, element
+ *                        by element.  a against out / out_copy and out_copy against x / out are checked CONSERVATIVELY, by the
+ *                        byte ranges that enclose their rows: column slices of one buffer are refused although they share no
+ *                        element -- keep a, and out_copy, in buffers apart from the stream.
+ * bf16 form: K % 8 == 0, N % 8 == 0, K <= 4096 (a [16][K + 8] bf16 image of its columns of W in LDS: 131 KB there), 16-byte
+ * aligned rows of W; anything else is refused by name, nothing launched.  fp32 form: any K and N, k ascending. */
+int zk_rnn_ff_residual(const void* a, int lda, const void* W, int ldw, const float* b, const float* x, int ldx, float* out,
+                       int ldo, void* out_copy, int ldc, int R, int K, int N, zk_stream_t stream);
+int zk_f32_rnn_ff_residual(const float* a, int lda, const float* W, int ldw, const float* b, const float* x, int ldx, float* out,
+                           int ldo, float* out_copy, int ldc, int R, int K, int N, zk_stream_t stream);
 int zk_add_attn(const void* qa, int ldq, const void* pm, int ldpm, long bspm, const void* mem, int ldmem, long bsmem,
                 const float* v, const float* kmask, int ldmask, float* ctx, int ldo, void* ctx_copy, int ldc, int R,
                 int kv_group, int Ls, int M, float neg, zk_stream_t stream);

@@ -1,6 +1,8 @@
 // zk_rnn.hip -- the recurrent family at inference: `rnnsearch` (models/rnnsearch.py; rnns/rnn.py, rnns/atr.py,
 // func.py:107-161 additive_attention) and `rnnsearch_deepatt` (models/rnnsearch_deepatt.py; the same launches plus the GRU
-// cell of rnns/gru.py, whose two launches are described where they are defined).  bf16 forms (bf16 GEMM operands, fp32 arithmetic) and fp32 forms (zk_f32_*).
+// cell of rnns/gru.py, whose two launches are described where they are defined) and `deepnmt` (models/deepnmt.py; the same
+// launches plus a layer's ff product with its residual add, zk_rnn_ff_residual, described where it is defined).  bf16 forms
+// (bf16 GEMM operands, fp32 arithmetic) and fp32 forms (zk_f32_*).
 //
 // ATR cell (rnns/atr.py:32-60, twin gates) for one time step of R rows, with the mask carry of rnns/rnn.py:41-49:
 //     q = h_prev U + b      i = sigmoid(p + q)      f = sigmoid(p - q)      h = i p + f h_prev
@@ -231,15 +233,15 @@ static bool rnn_rows_overlap(const float* a, long lda, long ra, const float* b, 
 // zk_f32_rnn_atr_step (lane = column, k ascending) and take any H.
 #define GRU_MAX_H 2048
 
-// sT [16][KS] = U[0 .. H - 1][c0 + n0 .. c0 + n0 + 15] transposed; the columns n0 + c >= H and the rows k >= H are zero
-__device__ __forceinline__ void gru_stage_slab(bf16_t* sT, int KS, const bf16_t* __restrict__ U, int ldu, int c0, int n0, int H,
+// sT [16][KS] = U[0 .. K - 1][n0 .. n0 + 15] transposed; the columns n0 + c >= N and the rows k >= K are zero
+__device__ __forceinline__ void rnn_stage_slab(bf16_t* sT, int KS, const bf16_t* __restrict__ U, int ldu, int n0, int K, int N,
                                                int Kr) {
   for (int k = threadIdx.x; k < Kr; k += 256) {
     uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = lo;
-    if (k < H) {                                               // (H % 8 == 0: a group of 8 columns is inside or outside)
-      const bf16_t* up = U + (size_t)k * ldu + c0 + n0;
-      if (n0 < H) lo = *reinterpret_cast<const uint4*>(up);
-      if (n0 + 8 < H) hi = *reinterpret_cast<const uint4*>(up + 8);
+    if (k < K) {                                               // (N % 8 == 0: a group of 8 columns is inside or outside)
+      const bf16_t* up = U + (size_t)k * ldu + n0;
+      if (n0 < N) lo = *reinterpret_cast<const uint4*>(up);
+      if (n0 + 8 < N) hi = *reinterpret_cast<const uint4*>(up + 8);
     }
     const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
@@ -250,9 +252,9 @@ __device__ __forceinline__ void gru_stage_slab(bf16_t* sT, int KS, const bf16_t*
   }
 }
 
-// acc[t] += A[row] . sU tile t for the 16 rows of a wave; A_F32: the row is fp32 (rounded here), else bf16 already
+// acc[t] += A[row][0 .. K - 1] . sU tile t for the 16 rows of a wave; A_F32: the row is fp32 (rounded here), else bf16 already
 template <int NT, bool A_F32>
-__device__ __forceinline__ void gru_product(rf32x4_t (&acc)[NT], const bf16_t* sU, int KS, int Kr, int H, const void* arow,
+__device__ __forceinline__ void rnn_product(rf32x4_t (&acc)[NT], const bf16_t* sU, int KS, int Kr, int K, const void* arow,
                                             bool valid, int vec_a, int lane) {
   const bf16_t* bt = sU + (lane & 15) * KS + (lane >> 4) * 8;
   for (int kk = 0; kk < Kr; kk += 32) {
@@ -263,24 +265,24 @@ __device__ __forceinline__ void gru_product(rf32x4_t (&acc)[NT], const bf16_t* s
       float a[8];
       if (vec_a) {
         float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
-        if (valid && k < H) {
+        if (valid && k < K) {
           x0 = *reinterpret_cast<const float4*>(hp + k);
           x1 = *reinterpret_cast<const float4*>(hp + k + 4);
         }
         a[0] = x0.x; a[1] = x0.y; a[2] = x0.z; a[3] = x0.w; a[4] = x1.x; a[5] = x1.y; a[6] = x1.z; a[7] = x1.w;
       } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = (valid && k + e < H) ? hp[k + e] : 0.f;
+        for (int e = 0; e < 8; ++e) a[e] = (valid && k + e < K) ? hp[k + e] : 0.f;
       }
       af = pack8(a);
     } else {
       const bf16_t* ap = reinterpret_cast<const bf16_t*>(arow);
       if (vec_a) {
-        if (valid && k < H) af = *reinterpret_cast<const uint4*>(ap + k);
+        if (valid && k < K) af = *reinterpret_cast<const uint4*>(ap + k);
       } else {
         float a[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) a[e] = (valid && k + e < H) ? bf2f(ap[k + e]) : 0.f;
+        for (int e = 0; e < 8; ++e) a[e] = (valid && k + e < K) ? bf2f(ap[k + e]) : 0.f;
         af = pack8(a);                                         // (exact: the values are bf16 already)
       }
     }
@@ -305,15 +307,15 @@ __global__ void __launch_bounds__(256) k_rnn_gru_gates(const float* __restrict__
   const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
   rf32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   if (h_prev != nullptr) {
-    gru_stage_slab(sU, KS, Ug, ldu, 0, n0, H, Kr);
-    gru_stage_slab(sU + (size_t)ATR_BN * KS, KS, Ug, ldu, H, n0, H, Kr);
+    rnn_stage_slab(sU, KS, Ug, ldu, n0, H, H, Kr);
+    rnn_stage_slab(sU + (size_t)ATR_BN * KS, KS, Ug + H, ldu, n0, H, H, Kr);
     __syncthreads();
     if (r0 < R) {                                              // wave-uniform: the MFMA runs with all 64 lanes
       const int row = r0 + (lane & 15);
       const bool valid = row < R;
       int src = valid ? (idx != nullptr ? idx[row] : row) : 0;
       src = min(max(src, 0), n_prev - 1);
-      gru_product<2, true>(acc, sU, KS, Kr, H, h_prev + (size_t)src * ldh, valid, vec_a, lane);
+      rnn_product<2, true>(acc, sU, KS, Kr, H, h_prev + (size_t)src * ldh, valid, vec_a, lane);
     }
   }
   const int col = n0 + (lane & 15);
@@ -348,12 +350,12 @@ __global__ void __launch_bounds__(256) k_rnn_gru_out(const bf16_t* __restrict__ 
   const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
   rf32x4_t acc[1] = {{0.f, 0.f, 0.f, 0.f}};
   if (h_prev != nullptr) {                                     // (the zero state: rh = 0, no product)
-    gru_stage_slab(sU, KS, Uh, ldu, 0, n0, H, Kr);
+    rnn_stage_slab(sU, KS, Uh, ldu, n0, H, H, Kr);
     __syncthreads();
     if (r0 < R) {
       const int row = r0 + (lane & 15);
       const bool valid = row < R;
-      gru_product<1, false>(acc, sU, KS, Kr, H, rh + (size_t)(valid ? row : 0) * ldr, valid, vec_a, lane);
+      rnn_product<1, false>(acc, sU, KS, Kr, H, rh + (size_t)(valid ? row : 0) * ldr, valid, vec_a, lane);
     }
   }
   const int col = n0 + (lane & 15);
@@ -380,18 +382,18 @@ __global__ void __launch_bounds__(256) k_rnn_gru_out(const bf16_t* __restrict__ 
   }
 }
 
-// fp32 forms: acc[j] += sum_k A[row j of the wave][k] U[k][col]; the block's 32 rows of A pass through LDS in chunks of 64 k.
-// arow: the row this thread stages (NULL: a row past R, zeros)
-__device__ __forceinline__ void gru_f32_product(float (&acc)[8], float (*sh)[64], const float* arow, const float* __restrict__ U,
-                                                int ldu, int H, int col, int wave) {
+// fp32 forms: acc[j] += sum_k A[row j of the wave][k] U[k][col], k < K, col < N; the block's 32 rows of A pass through LDS in
+// chunks of 64 k.  arow: the row this thread stages (NULL: a row past R, zeros)
+__device__ __forceinline__ void rnn_f32_product(float (&acc)[8], float (*sh)[64], const float* arow, const float* __restrict__ U,
+                                                int ldu, int K, int N, int col, int wave) {
   const int lr = threadIdx.x >> 3, lk = (threadIdx.x & 7) * 8;
-  for (int k0 = 0; k0 < H; k0 += 64) {
+  for (int k0 = 0; k0 < K; k0 += 64) {
     __syncthreads();
 #pragma unroll
-    for (int e = 0; e < 8; ++e) sh[lr][lk + e] = (arow != nullptr && k0 + lk + e < H) ? arow[k0 + lk + e] : 0.f;
+    for (int e = 0; e < 8; ++e) sh[lr][lk + e] = (arow != nullptr && k0 + lk + e < K) ? arow[k0 + lk + e] : 0.f;
     __syncthreads();
-    const int kn = min(64, H - k0);
-    if (col < H) {
+    const int kn = min(64, K - k0);
+    if (col < N) {
       int kk = 0;
       for (; kk + 8 <= kn; kk += 8) {                          // eight rows of U in flight per lane, then their products
         float u[8];
@@ -435,7 +437,7 @@ __global__ void __launch_bounds__(256) k_f32_rnn_gru_gates(const float* __restri
     const int grow = r0 + (threadIdx.x >> 3);
     int src = grow < R ? (idx != nullptr ? idx[grow] : grow) : 0;
     src = min(max(src, 0), n_prev - 1);
-    gru_f32_product(acc, sh, grow < R ? h_prev + (size_t)src * ldh : nullptr, Ug + (second ? H : 0), ldu, H, col, wave);
+    rnn_f32_product(acc, sh, grow < R ? h_prev + (size_t)src * ldh : nullptr, Ug + (second ? H : 0), ldu, H, H, col, wave);
   }
   if (col >= H) return;
   const float bias = bg[gcol];
@@ -472,7 +474,7 @@ __global__ void __launch_bounds__(256) k_f32_rnn_gru_out(const float* __restrict
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
   if (h_prev != nullptr) {
     const int grow = r0 + (threadIdx.x >> 3);
-    gru_f32_product(acc, sh, grow < R ? rh + (size_t)grow * ldr : nullptr, Uh, ldu, H, col, wave);
+    rnn_f32_product(acc, sh, grow < R ? rh + (size_t)grow * ldr : nullptr, Uh, ldu, H, H, col, wave);
   }
   if (col >= H) return;
   const float bias = bh[col];
@@ -531,12 +533,108 @@ __global__ void __launch_bounds__(256) k_f32_rnn_gru_out(const float* __restrict
                "16-byte aligned rows of the matrix (H=%d ldu=%d); " F32NAME " takes any H", GRU_MAX_H, H, ldu)
 
 template <typename Kern>
-static int gru_lds_attr(const char* name, Kern kern, size_t lds) {
+static int rnn_lds_attr(const char* name, Kern kern, size_t lds) {
   if (lds < 64 * 1024) return 0;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return zk_set_error((int)e, "%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
   return 0;
 }
+
+// ---------------------------------------------------------------- ff + residual of a deepnmt layer
+// models/deepnmt.py:73-79 (encoder) and 166-172 (decoder): y = linear(outputs, embed_size, scope="ff"); x = x + y, with
+// layer_norm off -- so NOTHING re-normalises x from the embedding to the last layer.  One launch:
+//     out[r, :] = x[r, :] + (a[r, :] W + b)          out_copy = the same in the storage type (the next product's operand)
+// The stream x / out is fp32 in BOTH forms for the reason the recurrent state is: a bf16 stream would drop every layer's
+// update below half an ulp of x, and the loss would add up over the layers (6j has the same argument for
+// transformer_fixup).  In the bf16 form only the MFMA operands a and W are bf16.  out may BE x (same address, same stride):
+// an element is read and written by the one lane that owns it, and no lane reads another's.
+// bf16 form: the tile scheme of k_rnn_atr_step -- 16 output columns x 64 rows per workgroup, the slab W[:, n0 .. n0 + 15]
+// streamed once into the transposed LDS image [16][K + 8] (131 KB for K = 4096, the largest K), the A fragments 16-byte
+// global loads of a (bf16 already), v_mfma_f32_16x16x32_bf16; edge tiles in rows, columns and K are zero-filled.
+// fp32 form: the scheme of k_f32_rnn_atr_step -- 64 columns x 32 rows, lane = column, k ascending.
+// No workgroup waits for another in either form.
+__global__ void __launch_bounds__(256) k_rnn_ff_residual(const bf16_t* __restrict__ a, int lda, const bf16_t* __restrict__ W,
+                                                         int ldw, const float* __restrict__ b, const float* x, int ldx,
+                                                         float* out, int ldo, bf16_t* __restrict__ out_copy, int ldc, int R,
+                                                         int K, int N, int vec_a) {
+  extern __shared__ __align__(16) unsigned char ff_lds[];
+  bf16_t* sW = reinterpret_cast<bf16_t*>(ff_lds);            // [ATR_BN][KS]
+  const int Kr = (K + 31) / 32 * 32, KS = Kr + 8;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
+  rf32x4_t acc[1] = {{0.f, 0.f, 0.f, 0.f}};
+  rnn_stage_slab(sW, KS, W, ldw, n0, K, N, Kr);
+  __syncthreads();
+  if (r0 < R) {                                                // wave-uniform: the MFMA runs with all 64 lanes
+    const int row = r0 + (lane & 15);
+    const bool valid = row < R;
+    rnn_product<1, false>(acc, sW, KS, Kr, K, a + (size_t)(valid ? row : 0) * lda, valid, vec_a, lane);
+  }
+  const int col = n0 + (lane & 15);
+  if (col >= N) return;
+  const float bias = b[col];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = r0 + (lane >> 4) * 4 + r;
+    if (row >= R) continue;
+    const float o = x[(size_t)row * ldx + col] + (acc[0][r] + bias);
+    out[(size_t)row * ldo + col] = o;
+    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = f2bf(o);
+  }
+}
+
+__global__ void __launch_bounds__(256) k_f32_rnn_ff_residual(const float* __restrict__ a, int lda, const float* __restrict__ W,
+                                                             int ldw, const float* __restrict__ b, const float* x, int ldx,
+                                                             float* out, int ldo, float* __restrict__ out_copy, int ldc, int R,
+                                                             int K, int N) {
+  __shared__ __align__(16) float sh[ATRF_BM][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int col = blockIdx.x * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  const int grow = r0 + (threadIdx.x >> 3);
+  rnn_f32_product(acc, sh, grow < R ? a + (size_t)grow * lda : nullptr, W, ldw, K, N, col, wave);
+  if (col >= N) return;
+  const float bias = b[col];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = r0 + wave * 8 + j;
+    if (row >= R) continue;
+    const float o = x[(size_t)row * ldx + col] + (acc[j] + bias);
+    out[(size_t)row * ldo + col] = o;
+    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = o;
+  }
+}
+
+// true when the byte ranges that ENCLOSE the rows of p ([rp, wp] elements of ep bytes, stride ldp) and of q meet.  Conservative:
+// two column slices of one wider buffer share no element and are refused all the same (their operands differ in width and
+// element size, which rnn_rows_overlap does not take); no caller lays a, out and out_copy out that way
+static bool rnn_spans_meet(const void* p, long ldp, long rp, long wp, long ep, const void* q, long ldq, long rq, long wq, long eq) {
+  if (p == nullptr || q == nullptr || rp <= 0 || rq <= 0) return false;
+  const uintptr_t p0 = (uintptr_t)p, p1 = p0 + (uintptr_t)(((rp - 1) * ldp + wp) * ep);
+  const uintptr_t q0 = (uintptr_t)q, q1 = q0 + (uintptr_t)(((rq - 1) * ldq + wq) * eq);
+  return p0 < q1 && q0 < p1;
+}
+
+// ESZ: bytes of an element of the storage type (a, W, out_copy)
+#define FF_CHECK_COMMON(NAME, ESZ)                                                                                          \
+  ZK_CHECK_ARG(a != nullptr && W != nullptr && b != nullptr && x != nullptr && out != nullptr,                              \
+               NAME ": a, W, b, x and out are required");                                                                   \
+  ZK_CHECK_ARG(R >= 0 && K >= 1 && N >= 1, NAME ": bad shape (R=%d K=%d N=%d)", R, K, N);                                   \
+  ZK_CHECK_ARG(lda >= K && ldw >= N && ldx >= N && ldo >= N && (out_copy == nullptr || ldc >= N),                           \
+               NAME ": a leading dimension is too small for K=%d N=%d (lda=%d ldw=%d ldx=%d ldo=%d ldc=%d)", K, N, lda,     \
+               ldw, ldx, ldo, ldc);                                                                                         \
+  ZK_CHECK_ARG((out == x && ldo == ldx) || !rnn_rows_overlap(out, ldo, R, x, ldx, R, N),                                    \
+               NAME ": out overlaps x without being x (in place needs the same address and the same stride: then every "   \
+               "element is read and written by the one lane that owns it)");                                                \
+  ZK_CHECK_ARG(!rnn_spans_meet(a, lda, R, K, ESZ, out, ldo, R, N, 4) &&                                                     \
+               !rnn_spans_meet(a, lda, R, K, ESZ, out_copy, ldc, R, N, ESZ),                                                \
+               NAME ": the span of out or out_copy meets the span of a (every column tile reads whole rows of a while "    \
+               "others write; the check is by enclosing byte ranges: keep a in a buffer of its own)");                      \
+  ZK_CHECK_ARG(!rnn_spans_meet(out_copy, ldc, R, N, ESZ, out, ldo, R, N, 4) &&                                              \
+               !rnn_spans_meet(out_copy, ldc, R, N, ESZ, x, ldx, R, N, 4),                                                  \
+               NAME ": the span of out_copy meets the span of x or out (by enclosing byte ranges)")
 
 // ---------------------------------------------------------------- additive attention
 #define ADD_RB 4          // beam rows per workgroup (1 when a sentence has a single row)
@@ -813,7 +911,7 @@ int zk_rnn_gru_gates(const float* h_prev, int ldh, int n_prev, const int* idx, c
   if (R == 0) return 0;
   const int Kr = (H + 31) / 32 * 32;
   const size_t lds = (size_t)2 * ATR_BN * (Kr + 8) * sizeof(bf16_t);
-  if (gru_lds_attr("zk_rnn_gru_gates", k_rnn_gru_gates, lds) != 0) return -1;
+  if (rnn_lds_attr("zk_rnn_gru_gates", k_rnn_gru_gates, lds) != 0) return -1;
   const int vec_a = h_prev != nullptr && ldh % 4 == 0 && (((uintptr_t)h_prev) & 15) == 0;
   hipLaunchKernelGGL(k_rnn_gru_gates, dim3((unsigned)((H + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)),
                      dim3(256), lds, stream, h_prev, ldh, n_prev, idx, reinterpret_cast<const bf16_t*>(Ug), ldu, bg,
@@ -841,7 +939,7 @@ int zk_rnn_gru_out(const void* rh, int ldr, const void* Uh, int ldu, const float
   if (R == 0) return 0;
   const int Kr = (H + 31) / 32 * 32;
   const size_t lds = (size_t)ATR_BN * (Kr + 8) * sizeof(bf16_t);
-  if (gru_lds_attr("zk_rnn_gru_out", k_rnn_gru_out, lds) != 0) return -1;
+  if (rnn_lds_attr("zk_rnn_gru_out", k_rnn_gru_out, lds) != 0) return -1;
   const int vec_a = ldr % 8 == 0 && (((uintptr_t)rh) & 15) == 0;
   hipLaunchKernelGGL(k_rnn_gru_out, dim3((unsigned)((H + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)), dim3(256),
                      lds, stream, reinterpret_cast<const bf16_t*>(rh), ldr, reinterpret_cast<const bf16_t*>(Uh), ldu, bh,
@@ -862,6 +960,37 @@ int zk_f32_rnn_gru_out(const float* rh, int ldr, const float* Uh, int ldu, const
   hipLaunchKernelGGL(k_f32_rnn_gru_out, dim3((unsigned)((H + ATRF_BN - 1) / ATRF_BN), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
                      dim3(256), 0, stream, rh, ldr, Uh, ldu, bh, xh, ldx, z, ldz, h_prev, ldh, n_prev, idx, mask, ldm, out, ldo,
                      out_copy, ldc, R, H);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_rnn_ff_residual(const void* a, int lda, const void* W, int ldw, const float* b, const float* x, int ldx, float* out,
+                       int ldo, void* out_copy, int ldc, int R, int K, int N, hipStream_t stream) {
+  FF_CHECK_COMMON("zk_rnn_ff_residual", 2);
+  ZK_CHECK_ARG(K % 8 == 0 && N % 8 == 0 && K <= 4096,
+               "zk_rnn_ff_residual: the bf16 form needs K and N multiples of 8 and K at most 4096 (its LDS image of 16 columns "
+               "of W: 131 KB there) -- got K=%d N=%d; zk_f32_rnn_ff_residual takes any K and N", K, N);
+  ZK_CHECK_ARG(ldw % 8 == 0 && (((uintptr_t)W) & 15) == 0,
+               "zk_rnn_ff_residual: the bf16 form reads W 16 bytes at a time: its rows must be 16-byte aligned (ldw=%d, W %% 16 "
+               "= %d)", ldw, (int)(((uintptr_t)W) & 15));
+  if (R == 0) return 0;
+  const int Kr = (K + 31) / 32 * 32;
+  const size_t lds = (size_t)ATR_BN * (Kr + 8) * sizeof(bf16_t);
+  if (rnn_lds_attr("zk_rnn_ff_residual", k_rnn_ff_residual, lds) != 0) return -1;
+  const int vec_a = lda % 8 == 0 && (((uintptr_t)a) & 15) == 0;
+  hipLaunchKernelGGL(k_rnn_ff_residual, dim3((unsigned)((N + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)),
+                     dim3(256), lds, stream, reinterpret_cast<const bf16_t*>(a), lda, reinterpret_cast<const bf16_t*>(W), ldw, b, x,
+                     ldx, out, ldo, reinterpret_cast<bf16_t*>(out_copy), ldc, R, K, N, vec_a);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+int zk_f32_rnn_ff_residual(const float* a, int lda, const float* W, int ldw, const float* b, const float* x, int ldx, float* out,
+                           int ldo, float* out_copy, int ldc, int R, int K, int N, hipStream_t stream) {
+  FF_CHECK_COMMON("zk_f32_rnn_ff_residual", 4);
+  if (R == 0) return 0;
+  hipLaunchKernelGGL(k_f32_rnn_ff_residual, dim3((unsigned)((N + ATRF_BN - 1) / ATRF_BN), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
+                     dim3(256), 0, stream, a, lda, W, ldw, b, x, ldx, out, ldo, out_copy, ldc, R, K, N);
   ZK_LAUNCH_CHECK();
   return 0;
 }

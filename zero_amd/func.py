@@ -652,6 +652,15 @@ class Engine(object):
         self.lib.call(name, *mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx), U.ptr, U.ld,
                       b.data_ptr(), p.ptr, p.ld, *mp(mask), out.ptr, out.ld, *mp(out_copy), out.rows, out.cols, self.stream)
 
+    def rnn_ff_residual(self, a, W, b, x, out, out_copy=None):
+        """models/deepnmt.py:73-79, 166-172 in one launch (zk_rnn_ff_residual; the fp32 form by a's dtype): out = x + (a W + b)
+        on the fp32 residual stream.  a: Mat [R, K] and W: Mat [K, N] of the storage type; b: fp32 [N]; x, out: fp32 Mats
+        [R, N] (out may be x itself); out_copy: storage-type Mat [R, N] -- e.g. a column slice of the next operand -- or None."""
+        name = "zk_f32_rnn_ff_residual" if a.t.dtype == torch.float32 else "zk_rnn_ff_residual"
+        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
+        self.lib.call(name, a.ptr, a.ld, W.ptr, W.ld, b.data_ptr(), x.ptr, x.ld, out.ptr, out.ld, *mp(out_copy), out.rows,
+                      W.rows, out.cols, self.stream)
+
     def rnn_gru_step(self, h_prev, Ug, bg, Uh, bh, xg, xh, z, rh, out, out_copy=None, idx=None, mask=None):
         """rnns/gru.py:32-57 + the carry of rnns/rnn.py:41-49, one time step of one cell as TWO launches (zk_rnn_gru_gates,
         zk_rnn_gru_out; the fp32 forms by xh's dtype): [z | r] = sigmoid(xg + h Ug + bg), out = carry(mask, z h + (1 - z)

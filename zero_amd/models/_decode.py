@@ -376,6 +376,12 @@ VARIANT_LIMITS = {
         member=(NotImplementedError, "ensemble member %d is a rnnsearch_deepatt: the ensemble step is built from the "
                                      "Transformer's fused attention launches and shares per-layer caches between members; "
                                      "composing a recurrent member is not built")),
+    "deepnmt": dict(
+        cache_only="deepnmt decodes with search_mode=cache only: search_mode=dev re-runs the encoder stack and the "
+                   "training-path decoder over the whole prefix each step, which is not built for it",
+        member=(NotImplementedError, "ensemble member %d is a deepnmt: the ensemble step is built from the Transformer's "
+                                     "fused attention launches and shares per-layer caches between members; composing a "
+                                     "recurrent member is not built")),
 }
 
 

@@ -71,6 +71,9 @@ def _core_class(model_name):
     if model_name == "rnnsearch_deepatt":
         from zero_amd.models._deepatt import DeepAttCore
         return DeepAttCore
+    if model_name == "deepnmt":
+        from zero_amd.models._deepnmt import DeepNmtCore
+        return DeepNmtCore
     return TransformerCore
 
 

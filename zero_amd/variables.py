@@ -183,6 +183,76 @@ def _deepatt_specs(params):
     return [(n, s, k, None) for n, s, k in v]
 
 
+def _deepnmt_specs(params):
+    """models/deepnmt.py:16-100, 103-194 + rnns/rnn.py + rnns/{atr,gru,cell}.py + func.py:14-65, 107-161, 289-303 in creation
+    order (cell "atr" or "gru", layer_norm off).  Cells own their variables as in _deepatt_specs; a plain rnn.rnn creates its
+    input projections in front of tf.scan and its recurrent maps inside it, a cond_rnn both input projections (one2one) or
+    the lower one and context_att (attention) in front and the rest inside, in the order the step body runs.  Every layer
+    ends with ff (func.linear to embed_size).  x_map and its layer_norm are created after the `encoder` scope is left
+    (deepnmt.py:83-84), and so are the initial-state maps layer_l_init: the `decoder_initializer` scope holds only the
+    construction of the cell (deepnmt.py:86-89), get_init_state(x=z, scope="layer_l") runs in the return statement behind it
+    (deepnmt.py:91-98; rnns/cell.py:35-38), at model scope.  The dl4mt_redict ff comes after the `decoder` scope
+    (deepnmt.py:176-177).  Embeddings and `bias` as
+    _rnnsearch_specs."""
+    H, E = params.hidden_size, params.embed_size
+    Vs, Vt = params.src_vocab.size(), params.tgt_vocab.size()
+    shared = params.shared_source_target_embedding
+    ca, NE, ND = bool(params.caencoder), int(params.num_encoder_layer), int(params.num_decoder_layer)
+    c = str(params.cell).lower()
+    if c not in ("atr", "gru"):
+        raise NotImplementedError("deepnmt: the variables of cell=%s are not laid out (atr and gru are)" % c)
+
+    def fetch(pre, s, width):
+        p = pre + "fetch_state_%s/" % s
+        gate = [(p + "gate_x/W_0_0", (width, 2 * H), "w")] if c == "gru" else []
+        return gate + [(p + "hide_x/W_0_0", (width, H), "w")]
+
+    def cell(pre, s):
+        p = pre + "cell_%s/" % s
+        gate = [(p + "gate_h/W_0_0", (H, 2 * H), "w"), (p + "gate_h/b_0", (2 * H,), "zeros")] if c == "gru" else []
+        return gate + [(p + "hide_h/W_0_0", (H, H), "w"), (p + "hide_h/b_0", (H,), "zeros")]
+
+    def one2one(pre, low_in, high_in):
+        return fetch(pre, c + "_lower", low_in) + fetch(pre, c + "_higher", high_in) + cell(pre, c + "_lower") + \
+            cell(pre, c + "_higher")
+
+    def ff(pre, width):
+        return [(pre + "ff/W_0_0", (width, E), "w"), (pre + "ff/b_0", (E,), "zeros")]
+    v = [("embedding" if shared else "src_embedding", (Vs, E), "embed_w"), ("bias", (E,), "w")]
+    for l in range(NE):
+        pre = "encoder/layer_%d/" % l
+        v += fetch(pre + "forward/", c, E) + cell(pre + "forward/", c)
+        if l == 0:
+            v += one2one(pre + "backward/", E, H) if ca else fetch(pre + "backward/", c, E) + cell(pre + "backward/", c)
+        v += ff(pre, 2 * H if l == 0 and not ca else H)
+    if E != H:
+        v += [("x_map/W_0_0", (E, H), "w"), ("x_map/b_0", (H,), "zeros"),
+              ("layer_norm/scale", (H,), "ones"), ("layer_norm/offset", (H,), "zeros")]
+    Z = 2 * H if NE == 1 and not ca else H
+    for l in range(ND):
+        i = "layer_%d_init/" % l      # (model scope: the `decoder_initializer` scope only builds the cell, deepnmt.py:86-98)
+        v += [(i + "W_0_0", (Z, H), "w"), (i + "b_0", (H,), "zeros")]
+    if not shared:
+        v.append(("tgt_embedding", (Vt, E), "embed_w"))
+    for l in range(ND):
+        pre = "decoder/layer_%d/" % l
+        if l == 0 or params.use_deep_att:
+            v += fetch(pre, c + "_lower", E) + [(pre + "context_att/W_0_0", (H, H), "w")] + cell(pre, c + "_lower")
+            v += [(pre + "attention/feed_query/W_0_0", (H, H), "w"), (pre + "attention/feed_query/b_0", (H,), "zeros"),
+                  (pre + "attention/feed_logits/W_0_0", (H, 1), "w"), (pre + "attention/feed_logits/b_0", (1,), "zeros")]
+            v += fetch(pre, c + "_higher", H) + cell(pre, c + "_higher")
+        elif ca:
+            v += one2one(pre, E, H)
+        else:
+            v += fetch(pre, c, E + H) + cell(pre, c)
+        v += ff(pre, H)
+    if params.dl4mt_redict:
+        v += ff("", E + H)
+    if not shared and not params.shared_target_softmax_embedding:
+        v.append(("softmax_embedding", (Vt, E), "embed_w"))
+    return [(n, s, k, None) for n, s, k in v]
+
+
 def variable_specs(params, model_name):
     """[(name, logical_shape, kind, layer)] in the reference's creation order
     (transformer.py:16-33,88-102,184-192; transformer_aan.py:165-192;
@@ -193,6 +263,8 @@ def variable_specs(params, model_name):
         return _rnnsearch_specs(params)
     if model_name == "rnnsearch_deepatt":
         return _deepatt_specs(params)
+    if model_name == "deepnmt":
+        return _deepnmt_specs(params)
     H, E, F = params.hidden_size, params.embed_size, params.filter_size
     if H != E:
         raise ValueError("hidden_size must equal embed_size for the Transformer models "
