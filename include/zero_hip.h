@@ -829,6 +829,32 @@ int zk_rnn_bias_tanh(const float* x, int ldx, const float* bias, float* out_f32,
                      int cols, int rep, zk_stream_t stream);
 int zk_f32_rnn_bias_tanh(const float* x, int ldx, const float* bias, float* out_f32, int ldo, float* out_copy, int ldc,
                          int rows, int cols, int rep, zk_stream_t stream);
+/* LRN / OLRN cells (rnns/lrn.py:32-53, rnns/olrn.py:32-58) with the mask carry of rnns/rnn.py:41-49 and the lower / higher pair of
+ * cond_rnn(one2one=True) (rnns/rnn.py:119-146): T >= 1 time steps of one cell, or of a pair, for R rows and H channels in ONE
+ * launch.  The cells have no recurrent product; [p | q | r (| s)] is the input projection (x W, no bias, 3 H or 4 H wide):
+ *   cell(h_, [p|q|r])   = sigmoid(p + h_) r + sigmoid(q - h_) h_                          (lrn, gated = 0)
+ *   cell(h_, [p|q|r|s]) = u sigmoid(s - u),  u = sigmoid(p + h_) r + sigmoid(q - h_) h_   (olrn, gated = 1; the gated value is carried)
+ *   single (hi == NULL):  h = carry(m_t, cell(h, lo_t), h)
+ *   paired:               s = carry(m_t, cell(h, lo_t), h);   h = carry(m_t, cell(s, hi_t), s)      carry(m, a, b) = m a + (1 - m) b
+ * for t = 0 .. T-1, or t = T-1 .. 0 with reverse != 0 (positions are never re-ordered in memory).
+ *   h_prev, ldh, n_prev, idx   the initial state h = h_prev[idx[r]] as in zk_rnn_atr_step: fp32 [n_prev, H] or NULL (zero state),
+ *                              idx int32 [R] or NULL, values clamped to 0 .. n_prev - 1.
+ *   lo, hi                     storage type; element (t, r, c) at  base + t * ps + r * rs + c  (strides in elements, as ld / bs of
+ *                              zk_add_attn): [B * Ls, W] sequence buffers and a [R, W] step operand (T = 1) pass without a copy.
+ *   mask, m_ps, m_rs           fp32 or NULL (all ones); a position with m == 0 leaves the state bit for bit.
+ *   out, ldo                   fp32 [R, H]: the state after the last scanned position; always written.
+ *   seq, seq_ps, seq_rs        NULL, or the carried state of EVERY position in the storage type, written at that position (with
+ *                              T = 1: the out_copy of the other cell launches; may be a column slice).
+ * The state is fp32 in both forms; every product and sum is rounded on its own, so a T-step launch equals T chained one-step
+ * launches bit for bit.  Refused (-1, nothing launched): T < 1; H % 8 != 0 or bases / strides of lo, hi, seq that are not
+ * 16-byte aligned in the bf16 form (the message names zk_f32_rnn_lrn_scan); H % 4 != 0 or unaligned operands in the fp32 form;
+ * out overlapping h_prev; seq overlapping lo / hi / h_prev / out (by enclosing byte ranges); negative strides. */
+int zk_rnn_lrn_scan(const float* h_prev, int ldh, int n_prev, const int* idx, const void* lo, long lo_ps, long lo_rs,
+                    const void* hi, long hi_ps, long hi_rs, const float* mask, long m_ps, long m_rs, float* out, int ldo,
+                    void* seq, long seq_ps, long seq_rs, int R, int H, int T, int reverse, int gated, zk_stream_t stream);
+int zk_f32_rnn_lrn_scan(const float* h_prev, int ldh, int n_prev, const int* idx, const float* lo, long lo_ps, long lo_rs,
+                        const float* hi, long hi_ps, long hi_rs, const float* mask, long m_ps, long m_rs, float* out, int ldo,
+                        float* seq, long seq_ps, long seq_rs, int R, int H, int T, int reverse, int gated, zk_stream_t stream);
 
 /* hipGraph plumbing: capture a sequence of the calls above once, replay per step */
 int zk_graph_begin(zk_stream_t stream);

@@ -1,8 +1,9 @@
 // zk_rnn.hip -- the recurrent family at inference: `rnnsearch` (models/rnnsearch.py; rnns/rnn.py, rnns/atr.py,
 // func.py:107-161 additive_attention) and `rnnsearch_deepatt` (models/rnnsearch_deepatt.py; the same launches plus the GRU
 // cell of rnns/gru.py, whose two launches are described where they are defined) and `deepnmt` (models/deepnmt.py; the same
-// launches plus a layer's ff product with its residual add, zk_rnn_ff_residual, described where it is defined).  bf16 forms
-// (bf16 GEMM operands, fp32 arithmetic) and fp32 forms (zk_f32_*).
+// launches plus a layer's ff product with its residual add, zk_rnn_ff_residual, described where it is defined); and the lrn /
+// olrn cells of both (rnns/lrn.py, rnns/olrn.py: no recurrent product, so a WHOLE scan is one launch, zk_rnn_lrn_scan, described
+// where it is defined).  bf16 forms (bf16 GEMM operands, fp32 arithmetic) and fp32 forms (zk_f32_*).
 //
 // ATR cell (rnns/atr.py:32-60, twin gates) for one time step of R rows, with the mask carry of rnns/rnn.py:41-49:
 //     q = h_prev U + b      i = sigmoid(p + q)      f = sigmoid(p - q)      h = i p + f h_prev
@@ -36,6 +37,7 @@
 // A masked key's logit is about -inf_const, its weight exp(-inf_const - max) is exactly 0.  tanhf saturates to +-1.
 #include <float.h>
 #include <math.h>
+#include <type_traits>
 #include "zk_common.h"
 
 typedef __bf16 rbf16x8_t __attribute__((ext_vector_type(8)));
@@ -871,6 +873,223 @@ static int rnn_bias_tanh_launch(const char* name, const float* x, int ldx, const
   return 0;
 }
 
+// ---------------------------------------------------------------- LRN / OLRN scans (rnns/lrn.py:32-53, rnns/olrn.py:32-58)
+// These cells have NO recurrent product: the input projection [p | q | r (| s)] = x W of the whole sequence is one GEMM and
+// the recurrence is element-wise per channel,
+//     u = sigmoid(p + h_) r + sigmoid(q - h_) h_            cell = u  (lrn)      cell = u sigmoid(s - u)  (olrn, `gated`)
+// so T time steps of one cell -- or of a lower / higher pair, cond_rnn(one2one=True), rnns/rnn.py:119-146 -- are ONE launch:
+//     single:  h = carry(m_t, cell(h, lo_t), h)
+//     paired:  s = carry(m_t, cell(h, lo_t), h);   h = carry(m_t, cell(s, hi_t), s)          carry(m, a, b) = m a + (1 - m) b
+// for t = 0 .. T-1, or T-1 .. 0 with `reverse` (positions stay where they are in memory).  A thread owns ONE row and one
+// 16-byte group of channels (8 in the bf16 form, 4 in the fp32 form) and walks the time axis with the state in registers; a
+// workgroup is one wave, so the R H / 8 threads of a scan spread over as many CUs as there are waves (32 rows x 512 channels:
+// 32 waves) -- the scan is a latency chain per thread, not a throughput problem, and nothing is shared between threads.
+// The operands of the positions after t do not depend on the state: they sit in a register ring of LRN_PD stages of raw
+// 16-byte vectors (3 or 4 per cell, and the mask word), each refilled as soon as its arithmetic is done, so the loads of the
+// next LRN_PD - 1 positions are in flight under the arithmetic of this one (counted vmcnt waits: loads return in order).  The
+// state is fp32 in BOTH forms; only the reads of lo / hi and the writes of seq are of the storage type.  Every product and
+// sum is rounded on its own (`#pragma clang fp contract(off)` in the cell: the loop body exists in LRN_PD unrolled copies,
+// and the compiler, where it may, fuses a product into an add in some copies and not in others), so a T-step launch equals T
+// chained one-step launches bit for bit and the tests' bound can be derived term by term.  A position with m = 0 leaves the
+// state untouched bit for bit.
+#define LRN_PD 4          // stages of the operand ring: LRN_PD - 1 positions in flight under the arithmetic of one
+
+template <bool F32, int NV>
+__device__ __forceinline__ void lrn_unpack(const uint4& v, float (&f)[NV]) {
+  if constexpr (F32) {
+    f[0] = __uint_as_float(v.x); f[1] = __uint_as_float(v.y); f[2] = __uint_as_float(v.z); f[3] = __uint_as_float(v.w);
+  } else {
+    unpack8(v, f);
+  }
+}
+
+// one cell on the NV channels of a thread: h <- carry(m, cell(h, [p | q | r (| s)]), h)
+template <bool F32, bool GATED, int NV>
+__device__ __forceinline__ void lrn_cell(float (&h)[NV], const uint4 (&in)[4], float m, bool has_mask) {
+#pragma clang fp contract(off)      // every product and sum below is rounded on its own, in every unrolled copy of the loop body
+  float p[NV], q[NV], r[NV], s[NV];
+  lrn_unpack<F32, NV>(in[0], p);
+  lrn_unpack<F32, NV>(in[1], q);
+  lrn_unpack<F32, NV>(in[2], r);
+  if constexpr (GATED) lrn_unpack<F32, NV>(in[3], s);
+  const bool carried = has_mask && m == 0.f;                    // the state bit for bit (a select: no branch in the scan loop)
+#pragma unroll
+  for (int e = 0; e < NV; ++e) {
+    const float hv = h[e];
+    const float i = rnn_sigmoid(p[e] + hv);
+    const float f = rnn_sigmoid(q[e] - hv);
+    float u = i * r[e] + f * hv;
+    if constexpr (GATED) u = u * rnn_sigmoid(s[e] - u);
+    if (has_mask) u = m * u + (1.f - m) * hv;
+    h[e] = carried ? hv : u;
+  }
+}
+
+struct LrnStage {
+  uint4 lo[4], hi[4];
+  float m;
+};
+
+template <bool F32, bool PAIRED, bool GATED>
+__global__ void __launch_bounds__(64) k_rnn_lrn_scan(const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                     const int* __restrict__ idx, const void* __restrict__ lo, long lo_ps,
+                                                     long lo_rs, const void* __restrict__ hi, long hi_ps, long hi_rs,
+                                                     const float* __restrict__ mask, long m_ps, long m_rs,
+                                                     float* __restrict__ out, int ldo, void* __restrict__ seq, long sq_ps,
+                                                     long sq_rs, int R, int H, int T, int reverse, int vec_h, int vec_o) {
+  constexpr int NV = F32 ? 4 : 8, NG = GATED ? 4 : 3;
+  typedef typename std::conditional<F32, float, bf16_t>::type st_t;
+  const int groups = H / NV;
+  const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+  if (gid >= (long)R * groups) return;
+  const int row = (int)(gid / groups), c0 = (int)(gid % groups) * NV;
+  const st_t* plo = reinterpret_cast<const st_t*>(lo) + (size_t)row * lo_rs + c0;
+  const st_t* phi = PAIRED ? reinterpret_cast<const st_t*>(hi) + (size_t)row * hi_rs + c0 : nullptr;
+  // (the loop below has no branch around a load, so that the waits are counted: without a mask the thread reads a word of its
+  // own lo operand in its place and drops it)
+  const bool has_mask = mask != nullptr;
+  const float* pm = has_mask ? mask + (size_t)row * m_rs : reinterpret_cast<const float*>(plo);
+  const long mps = has_mask ? m_ps : 0;
+
+  auto fetch = [&](LrnStage& s, int n) {                        // the operands of the n-th scanned position (n clamped)
+    n = min(n, T - 1);
+    const long t = reverse ? T - 1 - n : n;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) s.lo[g] = *reinterpret_cast<const uint4*>(plo + t * lo_ps + (size_t)g * H);
+    if constexpr (PAIRED) {
+#pragma unroll
+      for (int g = 0; g < NG; ++g) s.hi[g] = *reinterpret_cast<const uint4*>(phi + t * hi_ps + (size_t)g * H);
+    }
+    s.m = pm[t * mps];
+  };
+
+  LrnStage ring[LRN_PD];
+
+  float h[NV];
+#pragma unroll
+  for (int e = 0; e < NV; ++e) h[e] = 0.f;
+  if (h_prev != nullptr) {
+    const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
+    const float* hp = h_prev + (size_t)src * ldh + c0;
+    if (vec_h) {
+#pragma unroll
+      for (int e = 0; e < NV; e += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(hp + e);
+        h[e] = v.x; h[e + 1] = v.y; h[e + 2] = v.z; h[e + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < NV; ++e) h[e] = hp[e];
+    }
+  }
+
+  st_t* pseq = seq != nullptr ? reinterpret_cast<st_t*>(seq) + (size_t)row * sq_rs + c0 : nullptr;
+  // (the state has arrived before the loop: a load still pending at its head would be waited for in every trip)
+#pragma unroll
+  for (int e = 0; e < NV; ++e) asm volatile("" : "+v"(h[e]));
+  // unrolled by the ring: a stage is a fixed set of registers.  The first trip (n0 = -LRN_PD) only fills the ring, so every
+  // load of the ring is issued from ONE place in the loop and the compiler's wait counts are exact at the loop's head
+  for (int n0 = -LRN_PD; n0 < T; n0 += LRN_PD) {
+#pragma unroll
+    for (int k = 0; k < LRN_PD; ++k) {
+      const int n = n0 + k;
+      if (n0 >= 0 && n < T) {                                   // (uniform; no load inside)
+        lrn_cell<F32, GATED, NV>(h, ring[k].lo, ring[k].m, has_mask);
+        if constexpr (PAIRED) lrn_cell<F32, GATED, NV>(h, ring[k].hi, ring[k].m, has_mask);
+        if (pseq != nullptr) {
+          const long t = reverse ? T - 1 - n : n;
+          if constexpr (F32) *reinterpret_cast<float4*>(pseq + t * sq_ps) = make_float4(h[0], h[1], h[2], h[3]);
+          else *reinterpret_cast<uint4*>(pseq + t * sq_ps) = pack8(h);
+        }
+      }
+      // refill the stage its arithmetic has just freed, into the SAME registers (no copies at the loop's back edge, which
+      // would wait for every load): consumed LRN_PD positions on, under the arithmetic of LRN_PD - 1.  Past the end: the
+      // last position again, dropped
+      fetch(ring[k], n + LRN_PD);
+    }
+  }
+
+  float* po = out + (size_t)row * ldo + c0;
+  if (vec_o) {
+#pragma unroll
+    for (int e = 0; e < NV; e += 4) *reinterpret_cast<float4*>(po + e) = make_float4(h[e], h[e + 1], h[e + 2], h[e + 3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < NV; ++e) po[e] = h[e];
+  }
+}
+
+// the bytes [base, end) that enclose an operand of T positions x R rows x w elements of esz bytes
+static void lrn_span(const void* p, long ps, long rs, long T, long R, long w, long esz, uintptr_t* b0, uintptr_t* b1) {
+  *b0 = (uintptr_t)p;
+  *b1 = *b0 + (uintptr_t)(((T - 1) * ps + (R - 1) * rs + w) * esz);
+}
+
+template <bool F32>
+static int lrn_scan_launch(const char* name, const char* other, const float* h_prev, int ldh, int n_prev, const int* idx,
+                           const void* lo, long lo_ps, long lo_rs, const void* hi, long hi_ps, long hi_rs, const float* mask,
+                           long m_ps, long m_rs, float* out, int ldo, void* seq, long sq_ps, long sq_rs, int R, int H, int T,
+                           int reverse, int gated, hipStream_t stream) {
+  const int NV = F32 ? 4 : 8, esz = F32 ? 4 : 2;
+  const long W = (long)(gated ? 4 : 3) * H;
+  if (!(lo != nullptr && out != nullptr)) return zk_set_error(-1, "%s: lo and out are required", name);
+  if (T < 1) return zk_set_error(-1, "%s: a scan has at least one position (T=%d)", name, T);
+  if (!(R >= 0 && H >= 1)) return zk_set_error(-1, "%s: bad shape (R=%d H=%d)", name, R, H);
+  if (H % NV != 0) {
+    if (F32) return zk_set_error(-1, "%s: the fp32 form needs H a multiple of 4 (H=%d): a thread owns 16 bytes of channels", name, H);
+    return zk_set_error(-1, "%s: the bf16 form needs H a multiple of 8 (H=%d): a thread owns 16 bytes of channels; %s takes "
+                        "multiples of 4", name, H, other);
+  }
+  const bool al = (((uintptr_t)lo) & 15) == 0 && lo_ps % NV == 0 && lo_rs % NV == 0 &&
+                  (hi == nullptr || ((((uintptr_t)hi) & 15) == 0 && hi_ps % NV == 0 && hi_rs % NV == 0)) &&
+                  (seq == nullptr || ((((uintptr_t)seq) & 15) == 0 && sq_ps % NV == 0 && sq_rs % NV == 0));
+  if (!al) {
+    if (F32) return zk_set_error(-1, "%s: lo, hi and seq are read and written 16 bytes at a time: their bases must be 16-byte "
+                                 "aligned and their strides multiples of 4 elements", name);
+    return zk_set_error(-1, "%s: the bf16 form reads lo / hi and writes seq 16 bytes at a time: unaligned rows (bases must be "
+                        "16-byte aligned, strides multiples of 8 elements); %s takes strides that are multiples of 4", name, other);
+  }
+  if (!(lo_ps >= 0 && lo_rs >= 0 && hi_ps >= 0 && hi_rs >= 0 && sq_ps >= 0 && sq_rs >= 0 && m_ps >= 0 && m_rs >= 0))
+    return zk_set_error(-1, "%s: strides must not be negative (reverse walks the positions backwards)", name);
+  if (!(ldo >= H && (h_prev == nullptr || ldh >= H))) return zk_set_error(-1, "%s: ldo=%d or ldh=%d is smaller than H=%d", name, ldo, ldh, H);
+  if (!(h_prev == nullptr || (idx != nullptr ? n_prev >= 1 : n_prev >= R)))
+    return zk_set_error(-1, "%s: h_prev has n_prev=%d rows (R=%d without an index, at least 1 with one)", name, n_prev, R);
+  if (rnn_rows_overlap(out, ldo, R, h_prev, ldh, n_prev, H))
+    return zk_set_error(-1, "%s: out overlaps h_prev (a row of h_prev may be gathered by several rows while others write out)", name);
+  if (seq != nullptr) {
+    uintptr_t s0, s1, a0, a1;
+    lrn_span(seq, sq_ps, sq_rs, T, R, H, esz, &s0, &s1);
+    lrn_span(lo, lo_ps, lo_rs, T, R, W, esz, &a0, &a1);
+    bool meet = s0 < a1 && a0 < s1;
+    if (hi != nullptr) {
+      lrn_span(hi, hi_ps, hi_rs, T, R, W, esz, &a0, &a1);
+      meet = meet || (s0 < a1 && a0 < s1);
+    }
+    if (meet) return zk_set_error(-1, "%s: seq overlaps lo / hi (by enclosing byte ranges: later positions are read while earlier "
+                                  "ones are written)", name);
+    if (rnn_spans_meet(seq, sq_rs, R, (T - 1) * sq_ps + H, esz, h_prev, ldh, n_prev, H, 4) ||
+        rnn_spans_meet(seq, sq_rs, R, (T - 1) * sq_ps + H, esz, out, ldo, R, H, 4))
+      return zk_set_error(-1, "%s: seq overlaps h_prev or out (by enclosing byte ranges)", name);
+  }
+  if (R == 0) return 0;
+  const long threads = (long)R * (H / NV), blocks = (threads + 63) / 64;
+  if (blocks > 0x7fffffffL) return zk_set_error(-1, "%s: %ld workgroups exceed the grid", name, blocks);
+  const int vec_h = h_prev != nullptr && ldh % 4 == 0 && (((uintptr_t)h_prev) & 15) == 0;
+  const int vec_o = ldo % 4 == 0 && (((uintptr_t)out) & 15) == 0;
+#define LRN_LAUNCH(P, G)                                                                                                    \
+  hipLaunchKernelGGL((k_rnn_lrn_scan<F32, P, G>), dim3((unsigned)blocks), dim3(64), 0, stream, h_prev, ldh, n_prev, idx, lo,  \
+                     lo_ps, lo_rs, hi, hi_ps, hi_rs, mask, m_ps, m_rs, out, ldo, seq, sq_ps, sq_rs, R, H, T, reverse ? 1 : 0, \
+                     vec_h, vec_o)
+  if (hi != nullptr) {
+    if (gated) LRN_LAUNCH(true, true); else LRN_LAUNCH(true, false);
+  } else {
+    if (gated) LRN_LAUNCH(false, true); else LRN_LAUNCH(false, false);
+  }
+#undef LRN_LAUNCH
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" {
 
 int zk_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const void* U, int ldu, const float* b,
@@ -1038,6 +1257,20 @@ int zk_rnn_bias_tanh(const float* x, int ldx, const float* bias, float* out_f32,
 int zk_f32_rnn_bias_tanh(const float* x, int ldx, const float* bias, float* out_f32, int ldo, float* out_copy, int ldc,
                          int rows, int cols, int rep, hipStream_t stream) {
   return rnn_bias_tanh_launch<true>("zk_f32_rnn_bias_tanh", x, ldx, bias, out_f32, ldo, out_copy, ldc, rows, cols, rep, stream);
+}
+
+int zk_rnn_lrn_scan(const float* h_prev, int ldh, int n_prev, const int* idx, const void* lo, long lo_ps, long lo_rs,
+                    const void* hi, long hi_ps, long hi_rs, const float* mask, long m_ps, long m_rs, float* out, int ldo,
+                    void* seq, long seq_ps, long seq_rs, int R, int H, int T, int reverse, int gated, hipStream_t stream) {
+  return lrn_scan_launch<false>("zk_rnn_lrn_scan", "zk_f32_rnn_lrn_scan", h_prev, ldh, n_prev, idx, lo, lo_ps, lo_rs, hi, hi_ps,
+                                hi_rs, mask, m_ps, m_rs, out, ldo, seq, seq_ps, seq_rs, R, H, T, reverse, gated, stream);
+}
+
+int zk_f32_rnn_lrn_scan(const float* h_prev, int ldh, int n_prev, const int* idx, const float* lo, long lo_ps, long lo_rs,
+                        const float* hi, long hi_ps, long hi_rs, const float* mask, long m_ps, long m_rs, float* out, int ldo,
+                        float* seq, long seq_ps, long seq_rs, int R, int H, int T, int reverse, int gated, hipStream_t stream) {
+  return lrn_scan_launch<true>("zk_f32_rnn_lrn_scan", "zk_rnn_lrn_scan", h_prev, ldh, n_prev, idx, lo, lo_ps, lo_rs, hi, hi_ps,
+                               hi_rs, mask, m_ps, m_rs, out, ldo, seq, seq_ps, seq_rs, R, H, T, reverse, gated, stream);
 }
 
 }  // extern "C"

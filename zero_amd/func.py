@@ -675,6 +675,27 @@ class Engine(object):
         self.lib.call("zk_f32_rnn_gru_out" if f32 else "zk_rnn_gru_out", rh.ptr, rh.ld, Uh.ptr, Uh.ld, bh.data_ptr(), xh.ptr,
                       xh.ld, z.ptr, z.ld, *state, *mp(mask), out.ptr, out.ld, *mp(out_copy), out.rows, out.cols, self.stream)
 
+    def rnn_lrn_scan(self, h_prev, lo, hi, out, seq=None, idx=None, mask=None, T=1, reverse=False, gated=False):
+        """rnns/lrn.py:32-53 / rnns/olrn.py:32-58 (gated) with the carry of rnns/rnn.py:41-49, T time steps of one cell (hi
+        None) or of the lower / higher pair of cond_rnn(one2one=True) (rnns/rnn.py:119-146) in ONE launch (zk_rnn_lrn_scan;
+        the fp32 form by lo's dtype); reverse walks t = T-1 .. 0.  h_prev, idx, out as in rnn_atr_step.  lo, hi: the input
+        projections [p | q | r (| s)], storage type; seq: the carried state of every position in the storage type, or None.
+        Each is a Mat [R * T, width] with rows in sentence-major order (row r T + t: the encoder's layout; with T = 1 a plain
+        [R, width] Mat, column slices included), or a tuple (Mat, position stride, row stride) in elements.  mask: fp32 Mat
+        [R, T] (ld = the stride between rows, positions adjacent), a tuple as above, or None."""
+        name = "zk_f32_rnn_lrn_scan" if (lo[0] if isinstance(lo, tuple) else lo).t.dtype == torch.float32 else "zk_rnn_lrn_scan"
+        T = int(T)
+
+        def sq(m, ps=None):
+            if m is None:
+                return (None, 0, 0)
+            if isinstance(m, tuple):
+                return (m[0].ptr, int(m[1]), int(m[2]))
+            return (m.ptr, m.ld if ps is None else ps, T * m.ld if ps is None else m.ld)
+        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
+        self.lib.call(name, *mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx), *sq(lo), *sq(hi), *sq(mask, 1),
+                      out.ptr, out.ld, *sq(seq), out.rows, out.cols, T, 1 if reverse else 0, 1 if gated else 0, self.stream)
+
     def add_attn(self, qa, pm, mem, v, kmask, ctx, ctx_copy, kv_group, Ls):
         """func.py:107-161 for one decode step (zk_add_attn / zk_f32_add_attn): qa Mat [R, M]; pm, mem Mats [R / kv_group *
         Ls, M] (projected memory, memory) of the storage type; v fp32 [M]; kmask fp32 [R / kv_group, Ls] or None; ctx fp32

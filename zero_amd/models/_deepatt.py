@@ -1,6 +1,6 @@
 # coding: utf-8
 """``rnnsearch_deepatt`` at inference: the encoder stack and the cached deep-attention decoder step on the kernels of
-zero_amd/csrc/zk_rnn.hip, in the bf16 mode and in ``decode_dtype=float32``, for ``cell`` in {atr, gru}.
+zero_amd/csrc/zk_rnn.hip, in the bf16 mode and in ``decode_dtype=float32``, for ``cell`` in {atr, gru, lrn, olrn}.
 
 Reference: models/rnnsearch_deepatt.py:68-128, 132-236, 240-303; rnns/rnn.py (rnn, cond_rnn one2one); rnns/atr.py, rnns/gru.py,
 rnns/cell.py; func.py:14-65, 107-161.  With carry(m, a, b) = m a + (1 - m) b, NE = num_encoder_layer, D = num_decoder_layer:
@@ -18,12 +18,16 @@ rnns/cell.py; func.py:14-65, 107-161.  With carry(m, a, b) = m a + (1 - m) b, NE
 A cell is its input projections (products over all rows at once) and its recurrence per time step:
   atr   p = x Wp;                      one launch  (zk_rnn_atr_step)
   gru   xg = x Wg [., 2 H], xh = x Wh;  two launches (zk_rnn_gru_gates, zk_rnn_gru_out: Engine.rnn_gru_step)
+  lrn   [p | q | r] = x W [., 3 H];  olrn  [p | q | r | s] = x W [., 4 H]      (rnns/lrn.py, rnns/olrn.py: NO recurrent product)
+        one launch for a WHOLE scan, single or lower / higher pair (zk_rnn_lrn_scan: Engine.rnn_lrn_scan); a step is T = 1
 `Cells` is that dispatch, shared by encode() and step().  Launches of a captured decoder step (without the search's own):
-  atr   embed, 1 projection, lower cell, D x (feed_query, attention, 1 projection, higher cell), ff, tanh, logits = 6 + 4 D
+  atr, lrn, olrn   embed, 1 projection, lower cell, D x (feed_query, attention, 1 projection, higher cell), ff, tanh, logits
+        = 6 + 4 D
   gru   embed, 2 projections, 2 cell launches, D x (feed_query, attention, 2 projections, 2 cell launches), ff, tanh, logits
         = 8 + 6 D
 and of the encoder: 1 embed + (1 + 2 NE) x n_p projections + (1 + 2 NE) x Ls x n_c cell launches (n_p = n_c = 1 for atr, 2 for
-gru) + the initial state (1 product, 1 row gather) + the projected memory.
+gru) + the initial state (1 product, 1 row gather) + the projected memory.  With lrn / olrn the cell launches of the encoder
+are 1 + NE scans, whatever Ls: 1 embed + (1 + 2 NE) projections + (1 + NE) scans + the same tail.
 
 The state is models/_rnnsearch.py's: a ping-pong pair of fp32 [BK, H] buffers (RnnState), the beam reorder is the row index
 of the step's first cell launch.  The attention contexts and the final state are written straight into column slices of one
@@ -41,6 +45,7 @@ from zero_amd.models._rnnsearch import RN, RnnSearchCore, RnnState, _at
 
 F32 = torch.float32
 GRU_MAX_H = 2048        # zk_rnn_gru_gates: the LDS image of its columns of the gate matrix (include/zero_hip.h)
+LRN_CELLS = ("lrn", "olrn")      # the cells without a recurrent product: a whole scan is one launch
 
 
 class DeepAttCore(RnnSearchCore):
@@ -76,15 +81,19 @@ def _ops(core, f32):
 
 class Cells(object):
     """The cell of the model (core.cell) on the ops `o`: fetch() = the input projections of a whole block of rows,
-    step() = one time step.  `tag` names the buffers, so that the encoder's and the step's never alias."""
+    step() = one time step; for lrn / olrn also scan() = a whole scan and pair() = one step of a lower / higher pair, each
+    ONE launch.  `tag` names the buffers, so that the encoder's and the step's never alias."""
 
     def __init__(self, core, o):
         self.c, self.o, self.e, self.H = core.cell, o, core.eng, core.H
+        self.lrn, self.gated = self.c in LRN_CELLS, self.c == "olrn"
 
     def fetch(self, x, pre, s, tag):
-        """rnns/{atr,gru}.py fetch_states of the scope pre + "fetch_state_<s>" on x: Mat [rows, in] -> the tuple of Mats the
-        cell's step takes (atr: (p,); gru: (xg [rows, 2 H], xh))."""
+        """rnns/{atr,gru,lrn,olrn}.py fetch_states of the scope pre + "fetch_state_<s>" on x: Mat [rows, in] -> the tuple of
+        Mats the cell's step takes (atr: (p,); gru: (xg [rows, 2 H], xh); lrn: ([p | q | r],); olrn: ([p | q | r | s],))."""
         o, H, p = self.o, self.H, pre + "fetch_state_%s/" % s
+        if self.lrn:
+            return (o.project(x, p + "hide_x/W_0_0", o.mat(tag + ".pqr", x.rows, (4 if self.gated else 3) * H)),)
         if self.c == "atr":
             return (o.project(x, p + "hide_x/W_0_0", o.mat(tag + ".p", x.rows, H)),)
         return (o.project(x, p + "gate_x/W_0_0", o.mat(tag + ".xg", x.rows, 2 * H)),
@@ -94,6 +103,9 @@ class Cells(object):
         """out = carry(mask, cell(h_prev[idx], inp), h_prev[idx]) with the scope pre + "cell_<s>"; the arguments of
         Engine.rnn_atr_step."""
         o, e, p = self.o, self.e, pre + "cell_%s/" % s
+        if self.lrn:                  # (no variable under cell_<s>)
+            e.rnn_lrn_scan(h_prev, inp[0], None, out, out_copy, idx, mask, 1, False, self.gated)
+            return
         if self.c == "atr":
             e.rnn_atr_step(h_prev, o.W(p + "hide_h/W_0_0"), o.b(p + "hide_h/b_0"), inp[0], out, out_copy, idx, mask)
             return
@@ -101,6 +113,16 @@ class Cells(object):
         rh = o.mat(tag + "gru.rh", out.rows, self.H)
         e.rnn_gru_step(h_prev, o.W(p + "gate_h/W_0_0"), o.b(p + "gate_h/b_0"), o.W(p + "hide_h/W_0_0"), o.b(p + "hide_h/b_0"),
                        inp[0], inp[1], z, rh, out, out_copy, idx, mask)
+
+    def pair(self, h_prev, lo, hi, out, out_copy=None, idx=None):
+        """lrn / olrn: out = higher(lower(h_prev[idx], lo), hi), one step of a one-to-one pair in ONE launch."""
+        self.e.rnn_lrn_scan(h_prev, lo[0], hi[0], out, out_copy, idx, None, 1, False, self.gated)
+
+    def scan(self, lo, hi, out, seq, mask, T, reverse):
+        """lrn / olrn: a whole scan from the zero state in ONE launch -- rnn.rnn (hi None) or cond_rnn(one2one=True) -- over
+        the T positions of sentence-major [R * T, .] Mats, backwards with `reverse`; seq: the state of every position in the
+        storage type (may be a column slice), out: the fp32 state after the last scanned position; mask: fp32 Mat [R, T]."""
+        self.e.rnn_lrn_scan(None, lo[0], hi[0] if hi is not None else None, out, seq, None, mask, T, reverse, self.gated)
 
 
 def encode(core, o, batch, K):
@@ -118,17 +140,24 @@ def encode(core, o, batch, K):
     seq_of = lambda l: enc if l == NE else o.mat("enc.seq%d" % (l & 1), T, H)      # h^l in the storage type
     hs = [Mat(e.buf(o.pre + "enc.h%d" % i, (B, H), F32), B, H) for i in (0, 1)]
     at = lambda inp, t: tuple(_at(m, B, t, Ls) for m in inp)
+    whole = Mat(smask, B, Ls, Ls)       # the mask of a whole scan: lrn / olrn issue ONE launch per scan, whatever Ls
     pre = "encoder/layer_0/"
     inp = cells.fetch(x, pre, c, "enc.lo")
-    prev = None
-    for t in range(Ls):
-        cells.step(pre, c, prev, at(inp, t), hs[t & 1], _at(seq_of(0), B, t, Ls), mask=mask_at(t), tag="enc.")
-        prev = hs[t & 1]
+    if cells.lrn:
+        cells.scan(inp, None, hs[0], seq_of(0), whole, Ls, False)
+    else:
+        prev = None
+        for t in range(Ls):
+            cells.step(pre, c, prev, at(inp, t), hs[t & 1], _at(seq_of(0), B, t, Ls), mask=mask_at(t), tag="enc.")
+            prev = hs[t & 1]
     for l in range(1, NE + 1):          # cond_rnn(one2one=True): the lower cell on x_t, the higher on h^{l-1}_t
         pre = "encoder/layer_%d/" % l
         lo = cells.fetch(x, pre, c + "_lower", "enc.lo")
         hi = cells.fetch(seq_of(l - 1), pre, c + "_higher", "enc.hi")
         g, s = hs
+        if cells.lrn:
+            cells.scan(lo, hi, g, seq_of(l), whole, Ls, l % 2 == 1)
+            continue
         order = range(Ls - 1, -1, -1) if l % 2 == 1 else range(Ls)
         for n, t in enumerate(order):
             cells.step(pre, c + "_lower", None if n == 0 else g, at(lo, t), s, mask=mask_at(t), tag="enc.")

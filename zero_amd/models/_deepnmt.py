@@ -1,6 +1,6 @@
 # coding: utf-8
 """``deepnmt`` at inference: the encoder stack and the cached decoder step on the kernels of zero_amd/csrc/zk_rnn.hip, in the
-bf16 mode and in ``decode_dtype=float32``, for ``cell`` in {atr, gru}.
+bf16 mode and in ``decode_dtype=float32``, for ``cell`` in {atr, gru, lrn, olrn}.
 
 Reference: models/deepnmt.py:16-100 (encoder), 103-194 (decoder); rnns/rnn.py (rnn, cond_rnn); rnns/atr.py, rnns/gru.py,
 rnns/cell.py; func.py:14-65, 107-161, 289-303.  With carry(m, a, b) = m a + (1 - m) b, NE = num_encoder_layer, ND =
@@ -33,6 +33,8 @@ launch runs in place.  Launches of a captured step, without the search's own (n_
   one-to-one layer     2 n_p + 2 n_c + 1
   plain layer          n_p + n_c + 1
   tail                 3 with dl4mt_redict (product, tanh, logits), else 1
+With lrn / olrn (n_p = n_c = 1, no recurrent product: models/_deepatt.py Cells) a one-to-one layer is 2 projections + ONE paired
+launch + 1, and every scan of the encoder -- plain or one-to-one pair -- is one launch whatever Ls.
 
 The state is one fp32 ping-pong pair [BK, H] per decoder layer (DeepNmtState); the beam reorder is the row index of every
 layer's first cell launch.  A step that follows no reorder (time 0 of the host-side search, an eager decoding_fn call) reads
@@ -112,6 +114,7 @@ def encode(core, o, batch, K):
     mask_at = lambda t: Mat(smask, B, 1, Ls, t)
     at = lambda inp, t: tuple(_at(m, B, t, Ls) for m in inp)
     cells = Cells(core, o)
+    whole = Mat(smask, B, Ls, Ls)
     xc = o.mat("enc.x", T, E)
     xs = xc if f32 else o.mat("enc.xs", T, E, F32)
     embed(core, o, batch["src"], T, core.src_emb, xs, xc)
@@ -119,19 +122,22 @@ def encode(core, o, batch, K):
     hf = o.mat("enc.hf", T, H)
     y2 = None if ca else o.mat("enc.y2", T, 2 * H)           # [forward | backward] of layer 0
 
-    def scan(pre, s, x, order, copy_of, tag):
-        """A plain rnn.rnn scan of x over the positions in `order` from the zero state; copy_of(t): where position t's state
-        goes in the storage type."""
+    def scan(pre, s, x, reverse, dest, tag):
+        """A plain rnn.rnn scan of x from the zero state, over t = Ls-1 .. 0 with `reverse`; dest: the [B * Ls, H] Mat (maybe a
+        column slice) that takes every position's state in the storage type."""
         inp = cells.fetch(x, pre, s, tag)
+        if cells.lrn:
+            cells.scan(inp, None, hs[0], dest, whole, Ls, reverse)
+            return
         prev = None
-        for n, t in enumerate(order):
-            cells.step(pre, s, prev, at(inp, t), hs[n & 1], copy_of(t), mask=mask_at(t), tag="enc.")
+        for n, t in enumerate(range(Ls - 1, -1, -1) if reverse else range(Ls)):
+            cells.step(pre, s, prev, at(inp, t), hs[n & 1], _at(dest, B, t, Ls), mask=mask_at(t), tag="enc.")
             prev = hs[n & 1]
     for l in range(NE):
         pre = "encoder/layer_%d/" % l
         first = l == 0
         fw = y2.cols_slice(0, H) if first and not ca else hf
-        scan(pre + "forward/", c, xc, range(Ls), lambda t: _at(fw, B, t, Ls), "enc.lo")
+        scan(pre + "forward/", c, xc, False, fw, "enc.lo")
         y = fw
         if first and ca:              # cond_rnn(one2one=True) on the reversed sequence: the lower cell on x_t, the higher on f_t
             b = pre + "backward/"
@@ -139,12 +145,15 @@ def encode(core, o, batch, K):
             lo = cells.fetch(xc, b, c + "_lower", "enc.lo")
             hi = cells.fetch(hf, b, c + "_higher", "enc.hi")
             g, s = hs
-            for t in range(Ls - 1, -1, -1):
-                cells.step(b, c + "_lower", None if t == Ls - 1 else g, at(lo, t), s, mask=mask_at(t), tag="enc.")
-                cells.step(b, c + "_higher", s, at(hi, t), g, _at(y, B, t, Ls), mask=mask_at(t), tag="enc.")
+            if cells.lrn:
+                cells.scan(lo, hi, g, y, whole, Ls, True)
+            else:
+                for t in range(Ls - 1, -1, -1):
+                    cells.step(b, c + "_lower", None if t == Ls - 1 else g, at(lo, t), s, mask=mask_at(t), tag="enc.")
+                    cells.step(b, c + "_higher", s, at(hi, t), g, _at(y, B, t, Ls), mask=mask_at(t), tag="enc.")
         elif first:
             bw = y2.cols_slice(H, 2 * H)
-            scan(pre + "backward/", c, xc, range(Ls - 1, -1, -1), lambda t: _at(bw, B, t, Ls), "enc.lo")
+            scan(pre + "backward/", c, xc, True, bw, "enc.lo")
             y = y2
         if l == NE - 1:               # z: the state after the last scanned position, before y's buffer is used again
             if first and ca:
@@ -226,6 +235,8 @@ def step(state, target, time, time_dev, hp):
         form = core.form(l)
         if form == "plain":
             cells.step(pre, c, src, cells.fetch(xcc, pre, c, "lo"), dst, hc, idx=idx)
+        elif form == "one2one" and cells.lrn:         # no attention between the two cells: ONE paired launch
+            cells.pair(src, cells.fetch(xc, pre, c + "_lower", "lo"), cells.fetch(cc, pre, c + "_higher", "hi"), dst, hc, idx)
         else:
             att = form == "att"
             cells.step(pre, c + "_lower", src, cells.fetch(xc, pre, c + "_lower", "lo"), s, sc if att else None, idx=idx)

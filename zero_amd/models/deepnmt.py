@@ -4,7 +4,7 @@ residual stream.  Every encoder and decoder layer is a recurrent scan followed b
 scope="ff")``; encoder layer 0 is bidirectional (or context-aware, ``caencoder``), decoder layer 0 -- every decoder layer
 under ``use_deep_att`` -- attends over the encoder output, the other decoder layers read the context of the last attention.
 
-Decode only, ``cell`` in {atr, gru}, ``layer_norm=False``, ``num_heads=1``, ``search_mode="cache"`` (zero_amd/models/_deepnmt.py
+Decode only, ``cell`` in {atr, gru, lrn, olrn}, ``layer_norm=False``, ``num_heads=1``, ``search_mode="cache"`` (zero_amd/models/_deepnmt.py
 holds the schedule, zero_amd/csrc/zk_rnn.hip the kernels).  Everything else says what is missing when it is asked for, before a
 core is built.
 """
@@ -14,7 +14,7 @@ import copy
 from zero_amd.models import model
 from zero_amd.models._factory import closing_dropout
 
-CELLS = ("atr", "gru")
+CELLS = ("atr", "gru", "lrn", "olrn")
 
 
 def train_fn(features, params, initializer=None, on_ready=None):
@@ -34,8 +34,8 @@ def check_params(params):
     from zero_amd.models._decode import check_search_mode
     cell = str(params.cell).lower()
     if cell not in CELLS:
-        raise NotImplementedError("deepnmt is built for cell=atr (rnns/atr.py) and cell=gru (rnns/gru.py) only: the %s cell "
-                                  "has no step kernel here" % cell)
+        raise NotImplementedError("deepnmt is built for cell=atr (rnns/atr.py), cell=gru (rnns/gru.py), cell=lrn (rnns/lrn.py) "
+                                  "and cell=olrn (rnns/olrn.py) only: the %s cell has no step kernel here" % cell)
     if params.layer_norm:
         raise NotImplementedError("deepnmt with layer_norm=True is not built: it needs a LayerNorm behind every product of "
                                   "func.linear inside the cells, their input projections and the attention (func.py:36-53) "

@@ -4,7 +4,7 @@
 ``num_encoder_layer`` conditional scans (cond_rnn(one2one=True), alternately reversed); the decoder step is a lower cell
 followed by ``num_decoder_layer`` pairs (additive attention over ONE shared projected memory, higher cell).
 
-Decode only, ``cell`` in {atr, gru}, ``layer_norm=False``, ``num_heads=1``, ``search_mode="cache"`` (zero_amd/models/_deepatt.py
+Decode only, ``cell`` in {atr, gru, lrn, olrn}, ``layer_norm=False``, ``num_heads=1``, ``search_mode="cache"`` (zero_amd/models/_deepatt.py
 holds the schedule, zero_amd/csrc/zk_rnn.hip the kernels).  Everything else says what is missing when it is asked for, before a
 core is built.  The published recipe trains with ``layer_norm=True``: its checkpoints do not decode here yet.
 """
@@ -14,7 +14,7 @@ import copy
 from zero_amd.models import model
 from zero_amd.models._factory import closing_dropout
 
-CELLS = ("atr", "gru")
+CELLS = ("atr", "gru", "lrn", "olrn")
 
 
 def train_fn(features, params, initializer=None, on_ready=None):
@@ -34,8 +34,8 @@ def check_params(params):
     from zero_amd.models._decode import check_search_mode
     cell = str(params.cell).lower()
     if cell not in CELLS:
-        raise NotImplementedError("rnnsearch_deepatt is built for cell=atr (rnns/atr.py) and cell=gru (rnns/gru.py) only: the "
-                                  "%s cell has no step kernel here" % cell)
+        raise NotImplementedError("rnnsearch_deepatt is built for cell=atr (rnns/atr.py), cell=gru (rnns/gru.py), cell=lrn "
+                                  "(rnns/lrn.py) and cell=olrn (rnns/olrn.py) only: the %s cell has no step kernel here" % cell)
     if params.layer_norm:
         raise NotImplementedError("rnnsearch_deepatt with layer_norm=True is not built: it needs a LayerNorm behind every "
                                   "product of func.linear -- inside the cells, their input projections and the attention "

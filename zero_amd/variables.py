@@ -136,10 +136,12 @@ def _rnnsearch_specs(params):
 
 def _deepatt_specs(params):
     """models/rnnsearch_deepatt.py:68-128, 132-236, 240-303 + rnns/rnn.py + rnns/{atr,gru,cell}.py + func.py:107-161 in
-    creation order (cell "atr" or "gru", layer_norm off).  A cell `s` owns its input projections fetch_state_<s>/... (no
+    creation order (cell "atr", "gru", "lrn" or "olrn", layer_norm off).  A cell `s` owns its input projections fetch_state_<s>/... (no
     bias) and its recurrent maps cell_<s>/... :
         atr   fetch: hide_x/W_0_0 [in, H]                            cell: hide_h/{W_0_0 [H, H], b_0}
         gru   fetch: gate_x/W_0_0 [in, 2 H], hide_x/W_0_0 [in, H]    cell: gate_h/{W_0_0 [H, 2 H], b_0}, hide_h/{W_0_0 [H, H], b_0}
+        lrn   fetch: hide_x/W_0_0 [in, 3 H]                          cell: nothing (rnns/lrn.py: no recurrent map)
+        olrn  fetch: hide_x/W_0_0 [in, 4 H]                          cell: nothing (rnns/olrn.py)
     Every scan creates the input projections of its cells (and, in the decoder, context_att) IN FRONT of tf.scan and the
     recurrent maps -- in the decoder also each deep_attention_l and fetch_state_<c>_higher_l, which act on values computed
     inside the step -- INSIDE it, in the order the step body runs.  The memory is H wide.  Embeddings and `bias` as
@@ -148,15 +150,18 @@ def _deepatt_specs(params):
     Vs, Vt = params.src_vocab.size(), params.tgt_vocab.size()
     shared = params.shared_source_target_embedding
     c = str(params.cell).lower()
-    if c not in ("atr", "gru"):
-        raise NotImplementedError("rnnsearch_deepatt: the variables of cell=%s are not laid out (atr and gru are)" % c)
+    if c not in ("atr", "gru", "lrn", "olrn"):
+        raise NotImplementedError("rnnsearch_deepatt: the variables of cell=%s are not laid out (atr, gru, lrn and olrn are)" % c)
+    XW = {"lrn": 3 * H, "olrn": 4 * H}.get(c, H)       # the width of hide_x: [p | q | r (| s)] for lrn / olrn
 
     def fetch(pre, s, width):
         p = pre + "fetch_state_%s/" % s
         gate = [(p + "gate_x/W_0_0", (width, 2 * H), "w")] if c == "gru" else []
-        return gate + [(p + "hide_x/W_0_0", (width, H), "w")]
+        return gate + [(p + "hide_x/W_0_0", (width, XW), "w")]
 
     def cell(pre, s):
+        if c in ("lrn", "olrn"):      # (rnns/lrn.py:44-51, rnns/olrn.py:46-56: the scope is opened, no variable is created)
+            return []
         p = pre + "cell_%s/" % s
         gate = [(p + "gate_h/W_0_0", (H, 2 * H), "w"), (p + "gate_h/b_0", (2 * H,), "zeros")] if c == "gru" else []
         return gate + [(p + "hide_h/W_0_0", (H, H), "w"), (p + "hide_h/b_0", (H,), "zeros")]
@@ -185,7 +190,7 @@ def _deepatt_specs(params):
 
 def _deepnmt_specs(params):
     """models/deepnmt.py:16-100, 103-194 + rnns/rnn.py + rnns/{atr,gru,cell}.py + func.py:14-65, 107-161, 289-303 in creation
-    order (cell "atr" or "gru", layer_norm off).  Cells own their variables as in _deepatt_specs; a plain rnn.rnn creates its
+    order (cell "atr", "gru", "lrn" or "olrn", layer_norm off).  Cells own their variables as in _deepatt_specs; a plain rnn.rnn creates its
     input projections in front of tf.scan and its recurrent maps inside it, a cond_rnn both input projections (one2one) or
     the lower one and context_att (attention) in front and the rest inside, in the order the step body runs.  Every layer
     ends with ff (func.linear to embed_size).  x_map and its layer_norm are created after the `encoder` scope is left
@@ -199,15 +204,18 @@ def _deepnmt_specs(params):
     shared = params.shared_source_target_embedding
     ca, NE, ND = bool(params.caencoder), int(params.num_encoder_layer), int(params.num_decoder_layer)
     c = str(params.cell).lower()
-    if c not in ("atr", "gru"):
-        raise NotImplementedError("deepnmt: the variables of cell=%s are not laid out (atr and gru are)" % c)
+    if c not in ("atr", "gru", "lrn", "olrn"):
+        raise NotImplementedError("deepnmt: the variables of cell=%s are not laid out (atr, gru, lrn and olrn are)" % c)
+    XW = {"lrn": 3 * H, "olrn": 4 * H}.get(c, H)       # the width of hide_x: [p | q | r (| s)] for lrn / olrn
 
     def fetch(pre, s, width):
         p = pre + "fetch_state_%s/" % s
         gate = [(p + "gate_x/W_0_0", (width, 2 * H), "w")] if c == "gru" else []
-        return gate + [(p + "hide_x/W_0_0", (width, H), "w")]
+        return gate + [(p + "hide_x/W_0_0", (width, XW), "w")]
 
     def cell(pre, s):
+        if c in ("lrn", "olrn"):      # (rnns/lrn.py:44-51, rnns/olrn.py:46-56: the scope is opened, no variable is created)
+            return []
         p = pre + "cell_%s/" % s
         gate = [(p + "gate_h/W_0_0", (H, 2 * H), "w"), (p + "gate_h/b_0", (2 * H,), "zeros")] if c == "gru" else []
         return gate + [(p + "hide_h/W_0_0", (H, H), "w"), (p + "hide_h/b_0", (H,), "zeros")]
