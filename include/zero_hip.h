@@ -663,6 +663,24 @@ int zk_f32_cumavg(const float* x, int ldx, const float* mask, const float* add, 
 int zk_f32_embed_shift(const int* ids, int rows, int L, const float* table, const float* bias, const float* timing,
                        int timing_rows, float* out, int H, float scale, zk_stream_t stream);
 
+/* ---- lexical shortlist decoding (zero_amd/shortlist.py; see zk_shortlist.hip): the per-batch output vocabulary.  The
+ * candidates of search.py:143-176 are then the ids of the shortlist instead of the whole target vocabulary.
+ *   src      int32 [rows, ld_src], the first Ls columns of a row are its source ids; ids outside (0, Vsrc) are skipped
+ *            (0 = pad)
+ *   lex_off  int32 [Vsrc + 1], lex_ids int32 [lex_off[Vsrc]]: the lexical table as CSR, row s = the target ids of source
+ *            id s by falling probability; entries outside [0, V) are skipped
+ *   S = {0 .. min(first, V)}  U  {the first min(best, len) entries of the row of every source id of the batch};  n = |S|;
+ *   Vs = min(V, roundup(n, round)); the lowest ids not in S are added until |S| = Vs.
+ *   ids[0 .. Vs) = S ascending, ids[Vs .. cap) = -1, count = {n, Vs}.     Exact and deterministic.
+ * Argument errors (nothing launched, every buffer untouched): first < 3; round not a positive multiple of 8;
+ * V outside 3 .. zk_shortlist_max_vocab() (4 194 304: the bit mask one finishing workgroup scans); cap < min(V,
+ * roundup(V, round)) = V; ws_bytes < zk_shortlist_workspace(V) (the mask: 4 bytes per 32 ids). */
+int zk_shortlist_max_vocab(void);
+size_t zk_shortlist_workspace(int V);
+int zk_shortlist_build(const int* src, int rows, int ld_src, int Ls, const int* lex_off, const int* lex_ids, int Vsrc,
+                       int best, int first, int V, int round, int* ids, int cap, int* count, void* workspace,
+                       size_t ws_bytes, zk_stream_t stream);
+
 /* ---- transformer_l0drop at inference (models/transformer_l0drop.py:16-135, 244-273; modules/l0norm.py:75-96, 166-177)
  * A learned hard-concrete gate drops encoder outputs; cross-attention runs over the kept ones plus ONE slot (index 0, a
  * zero key / value) that carries the number of dropped positions as its softmax weight.

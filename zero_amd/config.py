@@ -63,6 +63,12 @@ _DEFAULTS = [
     ("score_dtype", "bfloat16"),
     ("l0_norm_reg_scalar", 1.0), ("l0_norm_start_reg_ramp_up", 0),
     ("l0_norm_end_reg_ramp_up", 10000), ("l0_norm_warm_up", True),
+    # build-specific: lexical shortlist decoding (zero_amd/shortlist.py).  shortlist_file: the lexical table, lines of
+    # "tgt_token src_token probability"; "" = off.  Per batch the output vocabulary is the shortlist_first lowest target
+    # ids (at least 3: pad / unk / eos) plus the shortlist_best most probable translations of every source token, filled
+    # with the lowest missing ids up to a multiple of shortlist_round (a multiple of 8; the size is part of the step
+    # graphs' shape)
+    ("shortlist_file", ""), ("shortlist_first", 100), ("shortlist_best", 100), ("shortlist_round", 1024),
 ]
 
 
@@ -98,6 +104,10 @@ class SyntheticVocab(object):
 
     def size(self):
         return self._size
+
+    def find(self, token):
+        """The token of id i is its decimal spelling; None for anything else (Vocab.find)."""
+        return int(token) if token.isdigit() and int(token) < self._size else None
 
     def pad(self):
         return 0

@@ -860,6 +860,16 @@ class Engine(object):
                       logits.ld, k2, float(temperature), float(penalty), int(forbid_id), float(forbid_value),
                       hip.ptr(scal_dev), ws.data_ptr(), ws.numel(), self.stream)
 
+    def shortlist_build(self, src, rows, ld_src, Ls, lex_off, lex_ids, best, first, V, round_to, ids, count, workspace=None):
+        """The per-batch output vocabulary (zk_shortlist_build, include/zero_hip.h): src int32 [rows, ld_src] source ids,
+        lex_off / lex_ids the lexical table as CSR -> ids int32 [cap] (the set ascending, -1 behind) and count int32 [2] =
+        {size before the fill, Vs}.  workspace: a byte tensor (default: the stream's scratch)."""
+        ws = self.workspace(self.lib.query("zk_shortlist_workspace", int(V))) if workspace is None else workspace
+        self.lib.call("zk_shortlist_build", hip.ptr(src), int(rows), int(ld_src), int(Ls), lex_off.data_ptr(),
+                      hip.ptr(lex_ids), int(lex_off.numel()) - 1, int(best), int(first), int(V), int(round_to),
+                      ids.data_ptr(), int(ids.numel()), count.data_ptr(), hip.ptr(ws), int(ws.numel() * ws.element_size()),
+                      self.stream)
+
     def embed_bwd(self, ids, dout, dtable, dbias, B, L, H, shift=False, drop_p=0.0, sid=0):
         self.lib.call("zk_embed_bwd", ids.data_ptr(), dout.ptr, dtable.data_ptr(), dbias.data_ptr(), B, L, H,
                       float(H) ** 0.5, 1 if shift else 0, float(drop_p), self.seed.data_ptr(), sid, self.stream)

@@ -31,6 +31,7 @@ import threading
 import numpy as np
 import torch
 
+from zero_amd import shortlist as _shortlist
 from zero_amd.func import Mat
 from zero_amd.hip import ZeroHipError
 from zero_amd.models._core import trim_columns
@@ -96,6 +97,8 @@ def _graph_pointers(state, book):
     ptrs += [m.ptr for _, m in sorted(state.get("wt", {}).items())]
     if state.get("kbias") is not None:          # transformer_l0drop: the log-count bias of the cross-attention keys
         ptrs.append(state["kbias"].data_ptr())
+    if state.get("shortlist") is not None:      # the compact target-side tables (zero_amd/shortlist.py)
+        ptrs += state["shortlist"].pointers()
     return tuple(ptrs) + (tuple(book) if book is not None else ())
 
 
@@ -114,6 +117,8 @@ def adopt_graphs(state, book, temperature, forbid_value, noise):
     # 16 rows per workgroup -- must not be adopted by a single-stream decode, nor the reverse)
     key = (state["B"], state["K"], state["Ls"], state["Tmax"], book is not None, float(temperature),
            float(forbid_value), bool(noise), int(e.lib.raw("zk_dec_group")(-1)), bool(state.get("f32")))
+    if state.get("shortlist") is not None:      # the size of the output vocabulary is part of a step's shape
+        key += (("shortlist", state["shortlist"].Vs),)
     state["_gkey"] = key
     if os.environ.get("ZERO_HIP_DECODE_GRAPH_CACHE", "1") == "0":
         return
@@ -250,6 +255,12 @@ def _fuse_att_ok(core, hp, K):
             and (not core.aan or os.environ.get("ZERO_HIP_DECODE_FUSE_LN", "1") != "0") and not hp.use_ffn)
 
 
+def vocab_size(state):
+    """The number of candidates per beam row of a step: the target vocabulary, or the state's shortlist."""
+    sl = state.get("shortlist")
+    return state["_core"].V if sl is None else sl.Vs
+
+
 def search_tail(state, core, logits, noise, temperature, forbid_value):
     """search.py:143-176 (+ 198-228 with the device-resident bookkeeping) on the step's fp32 ``logits`` Mat [B*K, ld]:
     optional Gumbel noise, then temperature, log-softmax, EOS ban, length penalty and top-2K in the fused tail.  Launches
@@ -258,8 +269,9 @@ def search_tail(state, core, logits, noise, temperature, forbid_value):
     e = core.eng
     book = state.get("book")
     sb = state["stepbuf"]
+    V = vocab_size(state)
     if noise:      # search.py:143-145; a fresh stream position every step
-        e.lib.call("zk_add_gumbel", logits.ptr, state["BK"], core.V, logits.ld, float(zdtype.epsilon()),
+        e.lib.call("zk_add_gumbel", logits.ptr, state["BK"], V, logits.ld, float(zdtype.epsilon()),
                    e.seed.data_ptr(), 7001, e.stream)
         e.lib.call("zk_seed_advance", e.seed.data_ptr(), 1, e.stream)
     fused_tail = False
@@ -274,7 +286,7 @@ def search_tail(state, core, logits, noise, temperature, forbid_value):
                        ws.data_ptr(), ws.numel(), *book, e.stream)      # raises with the library's message
         fused_tail = rc == 0
     if not fused_tail:
-        e.beam_topk(logits, state["prev"], state["ts"], state["ti"], state["B"], state["K"], core.V,
+        e.beam_topk(logits, state["prev"], state["ts"], state["ti"], state["B"], state["K"], V,
                     2 * state["K"], temperature, 1.0, -1, forbid_value, scal_dev=sb[1:3])
         if book is not None:
             e.lib.call("zk_beam_dev_advance", *book, e.stream)
@@ -472,6 +484,8 @@ def build_state(core, hp, model_name, source, K, max_steps):
     st = o.storage
     batch, max_steps = shape_batch(core, hp, source, max_steps)
     B, Ls = batch["B"], batch["Ls"]
+    # the batch's output vocabulary is built from the source ids while the encoder runs (zero_amd/shortlist.py)
+    sl = _shortlist.launch(core, hp, batch["src"], B, Ls, Ls, o.pre) if _shortlist.wanted(hp) else None
     enc, smask = encode(core, hp, batch, o)
     kbias = None
     if core.l0drop:
@@ -490,6 +504,8 @@ def build_state(core, hp, model_name, source, K, max_steps):
                   "mask": mask_keep, "time_filled": 0, "decoder": {"state": {}}, "f32": f32, "wt": {}, "_pp": 0})
     if kbias is not None:
         state["kbias"] = kbias
+    if sl is not None:
+        state["shortlist"] = _shortlist.finish(core, hp, sl, o)
     for l in range(nl):
         p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
         kv = o.mat("%d.kv" % l, B * Ls, 2 * H)
@@ -633,6 +649,7 @@ def static_step(state, hp, logits_of, fast_capture, temperature, forbid_value, d
 
 def make_infer_fns(params, model_name):
     hp = params
+    _shortlist.check(hp, model_name)
     check_search_mode(model_name, hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
@@ -731,7 +748,9 @@ def make_infer_fns(params, model_name):
         lay0 = state["decoder"]["state"]["layer_0"]
         aan0 = core.aan
         gat = state.pop("_aan_gather", None)       # the beam reorder of the running sums, deferred to this launch
-        e.lib.call("zk_dec_embed", target.data_ptr(), hp.tgt_vocab.pad(), core.store.s(core.tgt_emb).data_ptr(),
+        sl = state.get("shortlist")
+        tgt_table = core.store.s(core.tgt_emb) if sl is None else sl.table(core.tgt_emb)
+        e.lib.call("zk_dec_embed", target.data_ptr(), hp.tgt_vocab.pad(), tgt_table.data_ptr(),
                    core.b("bias").data_ptr(), e.timing(Tmax + 1, H).data_ptr(), x.ptr, BK, H, float(H) ** 0.5,
                    0 if time_dev is not None else time, time_dev.data_ptr() if time_dev is not None else None,
                    lay0["aan"].data_ptr() if aan0 else None, e.mat("dc.cat", BK, 2 * H).ptr if aan0 else None,
@@ -852,7 +871,12 @@ def make_infer_fns(params, model_name):
             else:
                 x = core._ffn_fwd(x, pre + "/feed_forward", "dc%d.ff" % l, False, 0, False)
         logits = e.mat("dc.logits", BK, core.Vpad, F32)
-        e.gemm(x, core.W(core.soft_emb), logits, BK, core.V, H, 0, 1)
+        if sl is None:
+            e.gemm(x, core.W(core.soft_emb), logits, BK, core.V, H, 0, 1)
+        else:      # the same buffer as [BK, Vs] against the compact softmax table
+            logits = sl.logits(logits.t, BK)
+            soft = sl.table(core.soft_emb)
+            e.gemm(x, Mat(soft, soft.shape[0], soft.shape[1]), logits, BK, sl.Vs, H, 0, 1)
         if time_dev is None:
             state["time_filled"] = time + 1
         return logits, state

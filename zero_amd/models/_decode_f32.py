@@ -70,7 +70,7 @@ def step_cache(target, state, time, time_dev, hp):
     fp32 [B*K, Vpad].  time_dev: the step counter lives in device memory (hipGraph replay)."""
     from zero_amd.models._decode import append_kv
     core = state["_core"]
-    o = ops_for(core, True)
+    o = ops_for(core, True, shortlist=state.get("shortlist"))
     e, H = core.eng, core.H
     BK, K, B, Ls, Tmax = state["BK"], state["K"], state["B"], state["Ls"], state["Tmax"]
     if time_dev is None and time >= Tmax:
@@ -157,7 +157,7 @@ def step_cache(target, state, time, time_dev, hp):
         x = o.add_ln(x, y, pre + "/" + core.cross, o.mat("d%d.ca.o" % l, BK, H))
         x = o.ffn(x, pre + "/feed_forward", "d%d.ff" % l, aan_next=aan_next, time=t_host, time_dev=tdev)
     logits = o.logits_mat(BK)
-    o.gemm(x, o.W(core.soft_emb), logits, BK, core.V, H, tb=1)
+    o.gemm(x, o.W(core.soft_emb), logits, BK, o.V, H, tb=1)
     if time_dev is None:
         state["time_filled"] = time + 1
     return logits, state

@@ -141,6 +141,9 @@ def combine(core, logits, rows):
 def make_infer_fns(total_graphs, total_params):
     """-> (encoding_fn, decoding_fn, search params): one pair for ``search.beam_search`` over all members.  The search
     parameters are member 0's (main.py:66) in member 0's scope, so that the search finds member 0's core and stream."""
+    from zero_amd import shortlist
+    for p in total_params:
+        shortlist.check(p, ensemble=True)
     check_members(total_params)
     hps = [member_params(p, i) for i, p in enumerate(total_params)]
     names = [p.model_name for p in total_params]

@@ -38,10 +38,14 @@ class Ops(object):
 
     storage = None
 
-    def __init__(self, core, prefix=None):
+    def __init__(self, core, prefix=None, shortlist=None):
         self.core, self.e, self.lib = core, core.eng, core.eng.lib
         self.H, self.nh, self.d = core.H, getattr(core, "nh", None), getattr(core, "d", None)      # (rnnsearch has no heads)
         self.pre = self.storage.prefix if prefix is None else prefix
+        # the decode state's shortlist (zero_amd/shortlist.py), or None: its compact tables stand in for the target-side
+        # tables and its size for V
+        self.sl = shortlist
+        self.V = core.V if shortlist is None else shortlist.Vs
 
     def mat(self, name, rows, cols, dt=None):
         """Named persistent matrix of the storage type (or of dt)."""
@@ -49,7 +53,14 @@ class Ops(object):
 
     def logits_mat(self, rows):
         """The fp32 logits of a decode step, under the storage's own prefix (models/_decode.py _graph_pointers)."""
-        return Mat(self.e.buf(self.storage.prefix + "logits", (rows, self.core.Vpad), F32), rows, self.core.Vpad)
+        return self.logits_view(self.e.buf(self.storage.prefix + "logits", (rows, self.core.Vpad), F32), rows)
+
+    def logits_view(self, buf, rows):
+        """buf fp32 [rows, Vpad] as the step's logits Mat: as it is, or [rows, ld of the shortlist] of the same memory."""
+        return Mat(buf, rows, self.core.Vpad) if self.sl is None else self.sl.logits(buf, rows)
+
+    def _compact(self, name):
+        return self.sl.table(name) if self.sl is not None else None
 
     def W(self, name):
         """The weight of the storage type (physical shape)."""
@@ -78,7 +89,8 @@ class Bf16Ops(Ops):
     storage = BF16_CACHES
 
     def table(self, name):
-        return self.core.store.s(name)
+        t = self._compact(name)
+        return self.core.store.s(name) if t is None else t
 
     def gemm(self, A, B, C, M, N, K, tb=0, bias=None, act=0):
         """C = A op(B) (+ bias).  C may be an fp32 Mat (the input of a tanh, the logits)."""
@@ -118,14 +130,15 @@ class F32Ops(Ops):
 
     storage = F32_CACHES
 
-    def __init__(self, core, prefix=None):
-        Ops.__init__(self, core, prefix)
+    def __init__(self, core, prefix=None, shortlist=None):
+        Ops.__init__(self, core, prefix, shortlist)
         # round 6: row-local launches folded into their neighbours (ZERO_HIP_F32_FUSE=0: one launch per op, as in round 5 --
         # the two forms are compared in tests/test_gpu_decode_f32.py)
         self.fold = os.environ.get("ZERO_HIP_F32_FUSE", "1") != "0"
 
     def table(self, name):
-        return self.core.store.w(name)
+        t = self._compact(name)
+        return self.core.store.w(name) if t is None else t
 
     def embed(self, ids, rows, L, table, out, max_pos, pos0=0, pos_dev=None, zero_flag=None):
         """func.py:341-369: out = table[ids] * sqrt(H) + bias + timing signal of the row's position (row % L + pos0, or
@@ -248,7 +261,7 @@ class F32Ops(Ops):
         return self.add_ln(x, y, scope, self.mat(tag + ".o", x.rows, self.H))
 
 
-def ops_for(core, f32, prefix=None):
+def ops_for(core, f32, prefix=None, shortlist=None):
     """The ops object of ``core`` in fp32 (``f32``) or bf16 storage, over buffers named prefix + name (default: the
-    storage's own prefix, ``dq.`` / ``dc.``)."""
-    return (F32Ops if f32 else Bf16Ops)(core, prefix)
+    storage's own prefix, ``dq.`` / ``dc.``).  shortlist: the decode state's, for the ops of a decode STEP."""
+    return (F32Ops if f32 else Bf16Ops)(core, prefix, shortlist)

@@ -27,6 +27,7 @@ stored once per sentence (kv_group = K).
 import numpy as np
 import torch
 
+from zero_amd import shortlist as _shortlist
 from zero_amd.func import Engine, Mat
 from zero_amd.models import _decode as _dec
 from zero_amd.models import _decode_f32 as _f32
@@ -94,8 +95,8 @@ def check_shape(core, f32):
 RN = "rn."        # this model's buffers: the decode mode's prefix + "rn." (RnnState.graph_pointers selects them by it)
 
 
-def _ops(core, f32):
-    return ops_for(core, f32, (_dec.F32_CACHES if f32 else _dec.BF16_CACHES).prefix + RN)
+def _ops(core, f32, shortlist=None):
+    return ops_for(core, f32, (_dec.F32_CACHES if f32 else _dec.BF16_CACHES).prefix + RN, shortlist)
 
 
 def cell(o, scope, h_prev, p, out, out_copy=None, idx=None, mask=None):
@@ -192,7 +193,7 @@ class RnnState(_dec.DecodeState):
 def step(state, target, time, time_dev, hp):
     """One cached decoder step -> (logits Mat fp32 [BK, Vpad], state)."""
     core = state["_core"]
-    o = _ops(core, state["f32"])
+    o = _ops(core, state["f32"], state.get("shortlist"))
     f32 = o.storage.dtype == F32
     e, H, E, M = core.eng, core.H, core.E, core.M
     BK, K, Ls = state["BK"], state["K"], state["Ls"]
@@ -220,8 +221,8 @@ def step(state, target, time, time_dev, hp):
     pre = o.project(cat, "pre_logits/W_0_0", o.mat("pre", BK, E, F32))
     feat = o.mat("feat", BK, E)
     e.rnn_bias_tanh(pre, o.b("pre_logits/b_0"), out_copy=feat, f32=f32)
-    logits = o.mat("logits", BK, core.Vpad, F32)
-    o.gemm(feat, o.W(core.soft_emb), logits, BK, core.V, E, 1)
+    logits = o.logits_view(o.mat("logits", BK, core.Vpad, F32).t, BK)
+    o.gemm(feat, o.W(core.soft_emb), logits, BK, o.V, E, 1)
     if time_dev is None:
         state["time_filled"] = time + 1
     return logits, state
@@ -237,6 +238,8 @@ def build_state(core, hp, source, K, max_steps):
     e = core.eng
     batch, max_steps = _dec.shape_batch(core, hp, source, max_steps)
     B, Ls = batch["B"], batch["Ls"]
+    # the batch's output vocabulary is built from the source ids while the encoder runs (zero_amd/shortlist.py)
+    sl = _shortlist.launch(core, hp, batch["src"], B, Ls, Ls, o.pre) if _shortlist.wanted(hp) else None
     enc, pm = encode(core, o, batch, K)
     mask_keep = e.buf(o.pre + "smask", (B, Ls), F32)
     mask_keep.copy_(batch["smask"])
@@ -244,6 +247,8 @@ def build_state(core, hp, source, K, max_steps):
     state.storage = o.storage
     state.update({"_core": core, "B": B, "K": K, "BK": B * K, "Ls": Ls, "Tmax": max_steps, "encodes": enc, "pm": pm,
                   "mask": mask_keep, "time_filled": 0, "decoder": {}, "f32": f32, "_pp": 0})
+    if sl is not None:
+        state["shortlist"] = _shortlist.finish(core, hp, sl, o)
     state.bind_caches()
     return _dec.finish_state(state)
 

@@ -41,6 +41,8 @@ def check_params(params):
 
 def infer_fn(params):
     params = closing_dropout(copy.copy(params))
+    from zero_amd import shortlist
+    shortlist.check(params, "rnnsearch")
     check_params(params)
     from zero_amd.models._rnnsearch import make_infer_fns
     return make_infer_fns(params, "rnnsearch")

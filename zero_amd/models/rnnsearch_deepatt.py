@@ -54,6 +54,8 @@ def check_params(params):
 
 def infer_fn(params):
     params = closing_dropout(copy.copy(params))
+    from zero_amd import shortlist
+    shortlist.check(params, "rnnsearch_deepatt")
     check_params(params)
     from zero_amd.models._deepatt import make_infer_fns
     return make_infer_fns(params, "rnnsearch_deepatt")

@@ -56,7 +56,13 @@ def beam_search(features, encoding_fn, decoding_fn, params):
 def _beam_search(features, encoding_fn, decoding_fn, params):
     box = []
     try:
-        return _beam_search_body(features, encoding_fn, decoding_fn, params, box)
+        out = _beam_search_body(features, encoding_fn, decoding_fn, params, box)
+        sl = box[0].get("shortlist") if box and hasattr(box[0], "get") else None
+        if sl is not None:
+            # the search ran in shortlist space (zero_amd/shortlist.py): ids go back through S once, here, whichever of
+            # the three bookkeeping paths produced them
+            out["seq"] = sl.map_back(out["seq"])
+        return out
     finally:
         # the batch's start-up lock (models/_decode.py: allocations and graph captures of concurrent batches are
         # serialised) must not outlive the search, whatever happened
@@ -92,6 +98,7 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
         state["_startup_held"] = True
         box.append(state)
         core = state["_core"]
+        V = _dec.vocab_size(state)        # the candidates per beam row: the vocabulary, or the batch's shortlist
     else:
         from zero_amd.models._factory import get_core
         core = get_core(params, params.model_name)

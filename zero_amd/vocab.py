@@ -62,6 +62,10 @@ class Vocab(object):
     def get_id(self, token):
         return self._index.get(token, self._index[self.unk_sym])
 
+    def find(self, token):
+        """The id of a token, None when the vocabulary does not have it (get_id answers <unk> then)."""
+        return self._index.get(token)
+
     def get_token(self, idx):
         return self._tokens[idx] if 0 <= idx < len(self._tokens) else self.unk_sym
 
