@@ -596,7 +596,8 @@ int zk_beam_dev_run(void* graph_even, void* graph_odd, int parity, const int* ct
  *                     first *nkeys_dev + 1 keys exist (the self-attention cache of decode position *nkeys_dev).
  *                     rpr_k / rpr_v (may be NULL; modules/rpr.py:10-75): relative-position tables [2 max_rel + 1, d] --
  *                     logits += q . r_k[clip(i - j) + max_rel], o += sum_j p_j r_v[...], i = q_pos0 (or *q_pos_dev) + row.
- *   zk_f32_add_rows   out[r] = a[r] + b[r]: the merged attention's o + aan_o (func.py:258-275, transformer_fuse).
+ *   zk_f32_add_rows   out[r] = a[r] + b[r]: the merged attention's o + aan_o (func.py:258-275, transformer_fuse).  Row strides
+ *                     lda, ldb, ldo in elements, each >= cols (refused otherwise); out == a with ldo == lda is in place.
  *   zk_f32_aan_step   transformer_aan.py:110-112: cat[r] = [x[r] | (x[r] + cache[r]) / (t + 1)], cache[r] += x[r].
  *   zk_f32_gate       transformer_aan.py:186-189: g = sigmoid(z[:, :H]) cat[:, :H] + sigmoid(z[:, H:]) cat[:, H:].
  * (cache appends and beam reorders are byte moves: zk_cache_rows / zk_gather_rows_ex with 4-byte elements.) */
@@ -783,7 +784,8 @@ int zk_f32_fixup_relu_shift(const float* h, int ldh, const float* offset, float*
  *                     ctx fp32 [R, M]; ctx_copy (may be NULL) the same in the storage type.  Any Ls (online softmax over
  *                     tiles of 64 keys); M <= 2048; bf16 form: M, ldpm, bspm multiples of 8.
  *   zk_rnn_embed      out[r] = table[ids[r]] + bias (no scale, no timing signal); zeros where pad >= 0 and EVERY id of
- *                     the launch equals pad (rnnsearch.py:101-103).  table [V, E] of the storage type, bias fp32.
+ *                     the launch equals pad (rnnsearch.py:101-103).  table [V, E] of the storage type, bias fp32.  An id
+ *                     outside [0, V) is CLAMPED: a negative id reads row 0, an id >= V reads row V - 1 (no fault, no error).
  *   zk_rnn_bias_tanh  y = tanh(x + bias) for fp32 rows x (bias may be NULL); input row r is written to the output rows
  *                     r rep .. r rep + rep - 1 of out_f32 (fp32) and / or out_copy (storage type). */
 int zk_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const void* U, int ldu, const float* b,

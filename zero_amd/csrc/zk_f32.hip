@@ -851,6 +851,8 @@ __global__ void __launch_bounds__(256) k_f32_add_rows(const float* __restrict__ 
 extern "C" int zk_f32_add_rows(const float* a, int lda, const float* b, int ldb, float* out, int ldo, int rows, int cols,
                                hipStream_t stream) {
   ZK_CHECK_ARG(a != nullptr && b != nullptr && out != nullptr && cols >= 1, "zk_f32_add_rows: bad arguments");
+  ZK_CHECK_ARG(lda >= cols && ldb >= cols && ldo >= cols,
+               "zk_f32_add_rows: a leading dimension is smaller than cols=%d (lda=%d ldb=%d ldo=%d)", cols, lda, ldb, ldo);
   if (rows <= 0) return 0;
   const size_t n = (size_t)rows * cols;
   hipLaunchKernelGGL(k_f32_add_rows, dim3((unsigned)min((size_t)2048, (n + 255) / 256)), dim3(256), 0, stream, a, lda, b, ldb, out,

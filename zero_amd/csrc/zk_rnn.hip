@@ -809,7 +809,8 @@ static int add_attn_launch(const void* qa, int ldq, const void* pm, int ldpm, lo
 
 // ---------------------------------------------------------------- row-local launches
 // out[r] = table[ids[r]] + bias, or zeros where EVERY id of the launch equals pad (models/rnnsearch.py:101-103); pad < 0:
-// no such rule (the encoder input, rnnsearch.py:28-29).  No sqrt(H) scale, no timing signal.
+// no such rule (the encoder input, rnnsearch.py:28-29).  No sqrt(H) scale, no timing signal.  An id outside [0, V) is
+// clamped: a negative id reads row 0, an id >= V reads row V - 1.
 template <bool F32>
 __global__ void __launch_bounds__(256) k_rnn_embed(const int* __restrict__ ids, int rows, const void* __restrict__ table,
                                                    int V, const float* __restrict__ bias, void* __restrict__ out, int ldo, int E,
