@@ -45,6 +45,19 @@ def _cases():
         for tag, ca in (("", True), ("-caencoder0", False)):
             out["rnnsearch-%s%s" % (dt, tag)] = dict(models=("rnnsearch",), dtype=dt,
                                                     hp={"cell": "atr", "caencoder": ca, "layer_norm": False})
+    # the deep recurrent models at the sizes of their model tests, 9 source positions (no padding: a scan is a launch or two per
+    # position).  rnnsearch_deepatt: NE = D = 2 takes the forward scan, the reversed and the un-reversed pair
+    pad1 = {"ZERO_HIP_DECODE_PAD_LEN": "1"}
+    for dt in ("bfloat16", "float32"):
+        for c in ("atr", "gru", "lrn", "olrn"):
+            out["rnnsearch_deepatt-%s-%s" % (dt, c)] = dict(
+                models=("rnnsearch_deepatt",), dtype=dt, env=pad1,
+                hp={"cell": c, "embed_size": 64, "num_heads": 1, "num_encoder_layer": 2, "num_decoder_layer": 2,
+                    "layer_norm": False})
+        # deepnmt_ref.CONFIGS: (A) caencoder, one-to-one layers, dl4mt_redict, x_map + LayerNorm; (B) the plain [x | c] form
+        # with the feature gather; (C) gru, use_deep_att, E == H; (A) with olrn: the paired one-launch layers; (B) with lrn
+        for tag, config, c in (("A", "A", None), ("B", "B", None), ("C", "C", None), ("A-olrn", "A", "olrn"), ("B-lrn", "B", "lrn")):
+            out["deepnmt-%s-%s" % (dt, tag)] = dict(models=("deepnmt",), dtype=dt, env=pad1, deepnmt=(config, c))
     # score_fn: the fp32 scorer of every model that has one and both of its switches, the bf16 scorer of transformer_fixup
     for m in ("transformer", "transformer_aan", "transformer_rpr", "transformer_fuse"):
         out["score-%s-float32" % m] = dict(models=(m,), dtype="float32", score=True)
@@ -70,6 +83,19 @@ def summary(trace):
     return text + (", graph of %d nodes" % trace["graph_nodes"] if "graph_nodes" in trace else "")
 
 
+def _overrides(case):
+    """The hparams a case sets; a deepnmt case names its configuration of tests/deepnmt_ref.py and, maybe, another cell."""
+    if "deepnmt" not in case:
+        return case.get("hp", {})
+    from tests import deepnmt_ref
+    config, cell = case["deepnmt"]
+    cfg = dict(deepnmt_ref.CONFIGS[config], layer_norm=False, num_heads=1)
+    cfg["hidden_size"], cfg["embed_size"] = cfg.pop("H"), cfg.pop("E")
+    if cell is not None:
+        cfg["cell"] = cell
+    return cfg
+
+
 def _batch(hp, seed):
     from tests.common import make_batch
     return make_batch(np.random.default_rng(seed), 5, 9, 11, hp.src_vocab.size(), hp.tgt_vocab.size())
@@ -93,6 +119,12 @@ def _params(hp, model, src, seed):
     elif model == "rnnsearch":
         from tests import rnnsearch_ref
         Pn = rnnsearch_ref.init_params(hp, seed)
+    elif model == "rnnsearch_deepatt":
+        from tests import deepatt_ref
+        Pn = deepatt_ref.init_params(hp, seed)
+    elif model == "deepnmt":
+        from tests import deepnmt_ref
+        Pn = deepnmt_ref.init_params(hp, seed)
     else:
         Pn = perturb(rt.init_params(hp, model, seed=seed + 1), np.random.default_rng(seed))
     Pn["tgt_embedding"] = (Pn["tgt_embedding"] * 6.0).astype(np.float32)
@@ -160,7 +192,7 @@ def run_case(name, patch):
     for i, m in enumerate(models):
         hp = make_hp(m, beam_size=K, search_mode="cache",
                      **{"score_dtype" if case.get("score") else "decode_dtype": case.get("dtype", "bfloat16")})
-        hp.override_from_dict(case.get("hp", {}))
+        hp.override_from_dict(_overrides(case))
         if i == 0:
             src, tgt = _batch(hp, 21)
         hps.append(hp)

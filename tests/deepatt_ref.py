@@ -26,7 +26,6 @@ gaps).  The bf16-storage restatement keeps the fp32 best hypotheses of the x 6 s
 model on both.
 """
 import copy
-import functools
 
 import numpy as np
 import torch
@@ -152,20 +151,26 @@ _w, _carry, _names = RS._w, RS._carry, RS._names
 
 
 def cell_fetch(x, P, pre, s, c):
-    """rnns/{atr,gru}.py fetch_states under pre + "fetch_state_<s>": the input projections (no bias), stored."""
+    """rnns/{atr,gru,lrn,olrn}.py fetch_states under pre + "fetch_state_<s>": the input projections (no bias), stored; lrn /
+    olrn have ONE, 3 H or 4 H wide."""
     p = pre + "fetch_state_%s/" % s
-    if c == "atr":
+    if c in ("atr", "lrn", "olrn"):
         return (rt.linear(x, P, p + "hide_x", bias=False),)
     return (rt.linear(x, P, p + "gate_x", bias=False), rt.linear(x, P, p + "hide_x", bias=False))
 
 
 def cell_call(h, inp, P, pre, s, c):
     """rnns/atr.py:32-60 / rnns/gru.py:32-57 under pre + "cell_<s>".  Storage sites of the kernels: the operands of the
-    recurrent products are the stored (rounded) state and the stored r h; z, the blend and the carry use the fp32 state."""
+    recurrent products are the stored (rounded) state and the stored r h; z, the blend and the carry use the fp32 state.
+    rnns/lrn.py:32-53 / rnns/olrn.py:32-58: no variable, no product; the state is fp32, the projection is the stored one."""
     p = pre + "cell_%s" % s
     if c == "atr":
         return RS.atr_cell(h, inp[0], P, p)
     H = h.shape[-1]
+    if c in ("lrn", "olrn"):
+        x = inp[0]
+        u = torch.sigmoid(x[..., :H] + h) * x[..., 2 * H:3 * H] + torch.sigmoid(x[..., H:2 * H] - h) * h
+        return u * torch.sigmoid(x[..., 3 * H:] - u) if c == "olrn" else u
     g = inp[0] + (torch.matmul(rt._st(h, "rnn_state"), _w(P, p + "/gate_h/W_0_0")) + P[p + "/gate_h/b_0"])
     z, r = torch.sigmoid(g[..., :H]), torch.sigmoid(g[..., H:])
     q = torch.matmul(rt._st(r * h, "rnn_state"), _w(P, p + "/hide_h/W_0_0")) + P[p + "/hide_h/b_0"]
@@ -264,31 +269,12 @@ def full_decoder(target, state, hp, P):
 
 
 def init_params(hp, seed):
-    """Every variable of zero_amd.variables.variable_specs(hp, "rnnsearch_deepatt") from its initial distribution, with the
-    biases perturbed so that every term is exercised."""
-    from tests.common import perturb
-    from zero_amd.variables import variable_specs
-    rng = np.random.default_rng(seed)
-    Pn = {}
-    for name, shape, kind, _ in variable_specs(hp, "rnnsearch_deepatt"):
-        v = np.zeros(shape) if kind == "zeros" else rt._scope_init(rng, shape, hp.initializer, hp.initializer_gain)
-        Pn[name] = np.asarray(v, np.float32)
-    return perturb(Pn, rng)
+    return V.init_params(hp, "rnnsearch_deepatt", seed)
 
 
 def make_fixture(hp, src, seed, factor=4.0):
-    """rnnsearch_ref.make_fixture on this model: candidate_margin (float64 and fp32 runs identical, gap > factor x err, rel)
-    for beam 1 and 4, and the bf16-storage restatement keeps the fp32 best hypotheses of the x 6 sharpened model.
-    -> dict Pn, gap, err, rel."""
-    Pn = init_params(hp, seed)
-    search = functools.partial(V.search, decoding_fns)
-    m = V.candidate_margin(search, hp, Pn, src, factor=factor, tol=(ATOL, RTOL), seed=seed)
-    Ps = V.sharpen(hp, Pn)
-    for K in (1, 4):
-        a, _ = search(hp, Ps, src, K, torch.float32)
-        b, _ = search(hp, Ps, src, K, torch.float32, store_bf16=True)
-        assert rt.decode_hypothesis(a["seq"], hp) == rt.decode_hypothesis(b["seq"], hp), ("bf16 storage model", K, seed)
-    return dict(m, Pn=Pn)
+    """variant_ref.make_fixture on this model -> dict Pn, gap, err, rel (the worst over beam 1 and 4)."""
+    return V.make_fixture("rnnsearch_deepatt", decoding_fns, (ATOL, RTOL), hp, src, seed, factor)
 
 
 LENGTHS = (14, 5, 9, 11)

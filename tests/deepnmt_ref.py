@@ -25,7 +25,6 @@ gap, err, rel as in tests/rnnsearch_ref.py.  The bf16-storage restatement keeps 
 model on all three.
 """
 import copy
-import functools
 
 import numpy as np
 import torch
@@ -301,36 +300,12 @@ def full_decoder(target, state, hp, P):
 
 
 def init_params(hp, seed):
-    """Every variable of zero_amd.variables.variable_specs(hp, "deepnmt") from its initial distribution, with the biases
-    (and the LayerNorm pair of x_map) perturbed so that every term is exercised."""
-    from tests.common import perturb
-    from zero_amd.variables import variable_specs
-    rng = np.random.default_rng(seed)
-    Pn = {}
-    for name, shape, kind, _ in variable_specs(hp, "deepnmt"):
-        if kind == "zeros":
-            v = np.zeros(shape)
-        elif kind == "ones":
-            v = np.ones(shape)
-        else:
-            v = rt._scope_init(rng, shape, hp.initializer, hp.initializer_gain)
-        Pn[name] = np.asarray(v, np.float32)
-    return perturb(Pn, rng)
+    return V.init_params(hp, "deepnmt", seed)
 
 
 def make_fixture(hp, src, seed, factor=4.0):
-    """rnnsearch_ref.make_fixture on this model: candidate_margin (float64 and fp32 runs identical, gap > factor x err, rel)
-    for beam 1 and 4, and the bf16-storage restatement keeps the fp32 best hypotheses of the x 6 sharpened model.
-    -> dict Pn, gap, err, rel."""
-    Pn = init_params(hp, seed)
-    search = functools.partial(V.search, decoding_fns)
-    m = V.candidate_margin(search, hp, Pn, src, factor=factor, tol=(ATOL, RTOL), seed=seed)
-    Ps = V.sharpen(hp, Pn)
-    for K in (1, 4):
-        a, _ = search(hp, Ps, src, K, torch.float32)
-        b, _ = search(hp, Ps, src, K, torch.float32, store_bf16=True)
-        assert rt.decode_hypothesis(a["seq"], hp) == rt.decode_hypothesis(b["seq"], hp), ("bf16 storage model", K, seed)
-    return dict(m, Pn=Pn)
+    """variant_ref.make_fixture on this model -> dict Pn, gap, err, rel (the worst over beam 1 and 4)."""
+    return V.make_fixture("deepnmt", decoding_fns, (ATOL, RTOL), hp, src, seed, factor)
 
 
 LENGTHS = (14, 5, 9, 11)

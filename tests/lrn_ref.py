@@ -10,9 +10,8 @@ Reference arithmetic (rnns/lrn.py:32-53, rnns/olrn.py:32-58, rnns/rnn.py:41-49, 
 ``lrn_scan``      the float64 numpy statement of zk_rnn_lrn_scan with every intermediate; ``defect=`` plants ONE defect.
 ``lrn_bound``     the element-wise bound propagated along the scan (derivation in its docstring).
 ``lrn_standin``   what a correct kernel computes, in torch float32 with another evaluation order.
-``deepatt`` / ``deepnmt``   the model restatements of tests/deepatt_ref.py and tests/deepnmt_ref.py with the cell dispatch
-                  widened to lrn / olrn: the same functions (encoder, decoder_step, decoding_fns, full_decoder, init_params,
-                  make_fixture) bound to this module's cell_fetch / cell_call; neither module is changed.
+``deepatt_hp`` / ``deepnmt_hp``   the model fixtures; the models themselves are restated in tests/deepatt_ref.py and
+                  tests/deepnmt_ref.py, whose cell_fetch / cell_call run all four cells.
 
 make_fixture on the fixtures of tests/test_gpu_lrn_model.py (vocabularies 120 / 104, sources of 14, 5, 9 and 11 tokens, beams 1
 and 4), measured on the CPU (tests/test_lrn_host.py re-measures and asserts gap > 4 err and the score_tol rule, not the figures;
@@ -24,8 +23,6 @@ picked as deepatt_ref.SEEDS were:
 gap, err, rel as in tests/rnnsearch_ref.py.  The bf16-storage restatement keeps the fp32 best hypotheses of the x 6 sharpened
 model on all four.
 """
-import types
-
 import numpy as np
 import torch
 
@@ -35,7 +32,6 @@ from tests import deepnmt_ref as DN
 from tests import rnnsearch_ref as RS
 from tests import variant_ref as V
 
-LRN_CELLS = ("lrn", "olrn")
 LRN_DEFECTS = ("pq_swapped", "q_plus_h", "gate_reads_old_state", "ungated_carried", "mask_ignored", "mask_once_per_pair",
                "reverse_ignored", "seq_at_scan_index", "idx_ignored", "bf16_state", "last_dropped", "r_neighbour")
 # fixture -> the seed of its model fixture
@@ -233,42 +229,7 @@ def scan_inputs(T, R, H, form, seed, gated, paired, n_prev=None, mask="mixed"):
     return x
 
 
-# ---------------------------------------------------------------------------------------------- ref_torch models
-def cell_fetch(x, P, pre, s, c):
-    """rnns/{lrn,olrn}.py fetch_states under pre + "fetch_state_<s>": ONE input projection, 3 H or 4 H wide (no bias), stored;
-    the other cells as tests/deepatt_ref.py."""
-    if c in LRN_CELLS:
-        return (rt.linear(x, P, pre + "fetch_state_%s/hide_x" % s, bias=False),)
-    return DA.cell_fetch(x, P, pre, s, c)
-
-
-def cell_call(h, inp, P, pre, s, c):
-    """rnns/lrn.py:32-53 / rnns/olrn.py:32-58: no variable, no product; the state is fp32, the projection is the stored one."""
-    if c not in LRN_CELLS:
-        return DA.cell_call(h, inp, P, pre, s, c)
-    H = h.shape[-1]
-    x = inp[0]
-    p, q, r = x[..., :H], x[..., H:2 * H], x[..., 2 * H:3 * H]
-    u = torch.sigmoid(p + h) * r + torch.sigmoid(q - h) * h
-    return u * torch.sigmoid(x[..., 3 * H:] - u) if c == "olrn" else u
-
-
-def _rebound(module, names):
-    """The functions `names` of `module` over a copy of its globals in which cell_fetch / cell_call are this module's: the
-    restatements run unchanged with the wider cell dispatch, and `module` itself is left as it is."""
-    ns = dict(vars(module), cell_fetch=cell_fetch, cell_call=cell_call)
-    for n in names:
-        f = getattr(module, n)
-        ns[n] = types.FunctionType(f.__code__, ns, n, f.__defaults__, f.__closure__)
-        ns[n].__kwdefaults__ = f.__kwdefaults__
-    return types.SimpleNamespace(**{n: ns[n] for n in names})
-
-
-_MODEL_FNS = ("encoder", "decoder_step", "decoding_fns", "full_decoder", "init_params", "make_fixture")
-deepatt = _rebound(DA, _MODEL_FNS)
-deepnmt = _rebound(DN, _MODEL_FNS)
-
-
+# ---------------------------------------------------------------------------------------------- the model fixtures
 def deepatt_hp(cell, **kw):
     """The fixture of tests/test_gpu_deepatt_model.py (H 128, E 64, NE = D = 2) with an lrn / olrn cell."""
     return DA.fixture_hp(cell, **kw)                  # (scope t_deepatt_<cell>: no other fixture uses these cells)

@@ -326,37 +326,12 @@ def full_decoder(target, state, hp, P):
 
 
 def init_params(hp, seed):
-    """Every variable of zero_amd.variables.variable_specs(hp, "rnnsearch") from its initial distribution (weights and
-    embeddings from the scope initialiser), with the biases perturbed so that every term is exercised."""
-    from tests.common import perturb
-    from zero_amd.variables import variable_specs
-    rng = np.random.default_rng(seed)
-    Pn = {}
-    for name, shape, kind, _ in variable_specs(hp, "rnnsearch"):
-        v = np.zeros(shape) if kind == "zeros" else rt._scope_init(rng, shape, hp.initializer, hp.initializer_gain)
-        Pn[name] = np.asarray(v, np.float32)
-    return perturb(Pn, rng)
+    return V.init_params(hp, "rnnsearch", seed)
 
 
 def make_fixture(hp, src, seed, factor=4.0):
-    """The tiny model of the GPU model tests with what the REFERENCE ALONE shows on it, measured on the CPU and asserted,
-    for beam 1 and 4:
-      * variant_ref.candidate_margin: the float64 and the fp32 run give identical hypotheses and candidate orders, and the
-        smallest gap between a kept candidate and its runner-up exceeds factor x err, the largest fp32 - float64 score
-        difference;  rel: that difference as a share of ATOL + RTOL |score_float64| -- how much of the project's fp32 score
-        tolerance the fp32 reference itself uses up (score_tol);
-      * with the output embedding sharpened x 6, the bf16-storage restatement (rt.Cfg.store_bf16) keeps the best hypothesis
-        of every sentence of the fp32 run.
-    -> dict Pn, gap, err, rel (the worst over both beams)."""
-    Pn = init_params(hp, seed)
-    search = functools.partial(V.search, decoding_fns)
-    m = V.candidate_margin(search, hp, Pn, src, factor=factor, tol=(ATOL, RTOL), seed=seed)
-    Ps = V.sharpen(hp, Pn)
-    for K in (1, 4):
-        a, _ = search(hp, Ps, src, K, torch.float32)
-        b, _ = search(hp, Ps, src, K, torch.float32, store_bf16=True)
-        assert rt.decode_hypothesis(a["seq"], hp) == rt.decode_hypothesis(b["seq"], hp), ("bf16 storage model", K, seed)
-    return dict(m, Pn=Pn)
+    """variant_ref.make_fixture on this model -> dict Pn, gap, err, rel (the worst over beam 1 and 4)."""
+    return V.make_fixture("rnnsearch", decoding_fns, (ATOL, RTOL), hp, src, seed, factor)
 
 
 LENGTHS = (14, 5, 9, 11)

@@ -1,7 +1,8 @@
 """The host side of decoding issues the launches pinned in tests/golden/decode_launch_trace.json: the same entry points
 in the same order with the same scalar arguments and the same pointer pattern, for every model in both decode dtypes, for
-both forms of every decode switch, on the launch-per-op path, for an ensemble, for rnnsearch with both encoder forms and
-for the score_fn of the fp32 scorer and of transformer_fixup (tests/decode_trace.py; the file is written by
+both forms of every decode switch, on the launch-per-op path, for an ensemble, for rnnsearch with both encoder forms, for
+rnnsearch_deepatt with each of its four cells, for deepnmt in five configurations (tests/deepnmt_ref.CONFIGS (A), (B), (C),
+(A) with olrn, (B) with lrn) and for the score_fn of the fp32 scorer and of transformer_fixup (tests/decode_trace.py; the file is written by
 tests/golden/make_decode_launch_trace.py).  The library itself runs: nothing is faked."""
 import pytest
 

@@ -16,12 +16,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from oracle import ref_torch as rt  # noqa: E402
 from tests import deepatt_ref as D  # noqa: E402
 from tests import variant_gpu as G  # noqa: E402
 from tests import variant_ref as V  # noqa: E402
 from zero_amd.models import load_all  # noqa: E402
-from zero_amd.models._factory import get_core, reset_cores  # noqa: E402
 
 load_all()
 MODEL = "rnnsearch_deepatt"
@@ -42,27 +40,13 @@ def fx(request):
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_fp32_mode_is_token_exact(fx, K):
-    ref = fx["ref"](K, key=("plain", K))
-    seqs, scores, _ = G.decode(G.beam_hp(fx["hp"], K, "float32"), MODEL, fx["Pn"], fx["src"])
-    G.assert_tokens(seqs, ref["seq"])
-    fin = ref["score"] > -1e30
-    rtol, atol = fx["tol"]
-    print("K=%d: largest score difference %.3e" % (K, np.abs(scores - ref["score"])[fin].max()))
-    assert np.allclose(scores[fin], ref["score"][fin], rtol=rtol, atol=atol), np.abs(scores - ref["score"])[fin].max()
+    G.fp32_exact(fx, MODEL, K)
 
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_bf16_mode(fx, K):
-    from zero_amd.search import decode_hypothesis
-    Pn = V.sharpen(fx["hp"], fx["Pn"])
-    ref = fx["ref"](K, Pn=Pn, key=("sharp", K))
-    hp = G.beam_hp(fx["hp"], K, "bfloat16")
-    seqs, scores, core = G.decode(hp, MODEL, Pn, fx["src"])
+    core = G.bf16_best(fx, MODEL, K, "%d launches of the model's own, " % STEP_LAUNCHES[fx["cell"]])
     assert core.__dict__.get("_decode_step_launches", 0) >= STEP_LAUNCHES[fx["cell"]]      # the step ran from captured graphs
-    print("K=%d: %d launches per captured step (%d of them the model's), top score diff %.3e"
-          % (K, core._decode_step_launches, STEP_LAUNCHES[fx["cell"]], np.abs(scores[:, 0] - ref["score"][:, 0]).max()))
-    hyp, hyp_ref = decode_hypothesis(seqs, hp), rt.decode_hypothesis(ref["seq"], hp)
-    assert hyp == hyp_ref, (hyp, hyp_ref)
 
 
 def test_fp32_source_padding(fx, monkeypatch):
@@ -70,16 +54,7 @@ def test_fp32_source_padding(fx, monkeypatch):
     encoder stack carries the state over it -- in either direction -- and the attentions give it the weight 0.  Tokens equal,
     scores within the fp32 tolerance -- not bitwise: the K-slicing of the fp32 GEMM depends on its row count, and the encoder's
     products have B * Ls rows."""
-    out = []
-    for pad in ("1", "8"):
-        monkeypatch.setenv("ZERO_HIP_DECODE_PAD_LEN", pad)
-        seqs, scores, _ = G.decode(G.beam_hp(fx["hp"], 4, "float32"), MODEL, fx["Pn"], fx["src"])
-        out.append((seqs, scores))
-    G.assert_tokens(out[0][0], out[1][0])
-    fin = out[0][1] > -1e30
-    rtol, atol = fx["tol"]
-    print("largest score difference between the paddings %.3e" % np.abs(out[0][1] - out[1][1])[fin].max())
-    assert np.array_equal(fin, out[1][1] > -1e30) and np.allclose(out[0][1][fin], out[1][1][fin], rtol=rtol, atol=atol)
+    G.assert_padding_within_tol(fx, MODEL, monkeypatch)
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
@@ -92,29 +67,14 @@ def test_step_graphs_are_reused_across_batches(fx, dtype):
 
 
 def test_four_lanes_equal_one_lane(fx):
-    from zero_amd.evalu import decode_many
-    hp = G.beam_hp(fx["hp"], 4, "bfloat16")
-    reset_cores(); get_core(hp, MODEL, V.sharpen(fx["hp"], fx["Pn"]))
-    batches = [V.ragged(tuple(int(x) for x in np.random.default_rng(i).integers(5, 15, 3 + i % 2)), hp.src_vocab.size(), 10 + i)
-               for i in range(6)]
-    work = G.lane_worker(MODEL, hp)
-    one = decode_many(batches, work, streams=1)
-    four = decode_many(batches, work, streams=4)
-    for i, (a, b) in enumerate(zip(one, four)):
-        assert a[2] == b[2] and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), i
+    G.assert_four_lanes_equal_one(fx, MODEL)
 
 
 @pytest.mark.parametrize("mode", ["eager", "host_book"])
 def test_the_other_search_modes_equal_the_device_resident_one(fx, monkeypatch, mode):
     """The step without graphs (decoding_fn + state.reorder per step) and the graph step with the bookkeeping on the host
     decode what the device-resident search decodes: reorder() / bind_caches() of the ping-pong state serve all three."""
-    hp = G.beam_hp(fx["hp"], 4, "float32")
-    base = G.decode(hp, MODEL, fx["Pn"], fx["src"])
-    monkeypatch.setenv("ZERO_HIP_DECODE_GRAPH" if mode == "eager" else "ZERO_HIP_DECODE_DEVICE_BOOK", "0")
-    seqs, scores, _ = G.decode(hp, MODEL, fx["Pn"], fx["src"])
-    G.assert_tokens(seqs, base[0])
-    fin = base[1] > -1e30
-    assert np.allclose(scores[fin], base[1][fin], rtol=fx["tol"][0], atol=fx["tol"][1])
+    G.assert_search_mode_equals_device(fx, MODEL, monkeypatch, mode)
 
 
 def _small(H, E, name, cell):
@@ -144,27 +104,5 @@ def test_cli_mode_test(tmp_path):
     """The reference's command line in a fresh interpreter: `--mode test` on files with model_name=rnnsearch_deepatt and
     cell=gru (freshly initialised weights: there is no training to make a checkpoint), hidden_size != embed_size, in both
     decode modes; the evaluation loop decodes its batches on lanes and writes one translation per source line."""
-    import os
-    import subprocess
-    import sys
-    rng = np.random.default_rng(3)
-    words = ["w%d" % i for i in range(12)]
-    (tmp_path / "vocab.txt").write_text("\n".join(words) + "\n")
-    lines = [" ".join(rng.choice(words, size=int(rng.integers(2, 7)))) for _ in range(8)]
-    for name in ("test.src", "test.tgt"):
-        (tmp_path / name).write_text("\n".join(lines) + "\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYTHONPATH=root)
-    common = "model_name=rnnsearch_deepatt,scope_name=deepatt,cell=gru,num_heads=1,num_encoder_layer=2,num_decoder_layer=2," \
-             "hidden_size=32,embed_size=24,eval_batch_size=3,beam_size=2," \
-             "decode_length=4,initializer=uniform_unit_scaling,initializer_gain=1.0,output_dir=%s," % (tmp_path / "out") + \
-             ",".join("%s=%s" % (k, tmp_path / v) for k, v in dict(
-                 src_vocab_file="vocab.txt", tgt_vocab_file="vocab.txt", src_test_file="test.src", tgt_test_file="test.tgt").items())
-    for dtype in ("bfloat16", "float32"):
-        out = tmp_path / ("t_%s.txt" % dtype)
-        r = subprocess.run([sys.executable, "-m", "zero_amd.run", "--mode", "test", "--parameters",
-                            common + ",decode_dtype=%s,test_output=%s" % (dtype, out)],
-                           env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        assert "bleu" in r.stdout
-        assert len(out.read_text().splitlines()) == 8
+    G.cli_mode_test(tmp_path, "model_name=rnnsearch_deepatt,scope_name=deepatt,cell=gru,num_heads=1,num_encoder_layer=2,"
+                              "num_decoder_layer=2,hidden_size=32,embed_size=24")

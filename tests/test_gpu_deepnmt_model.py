@@ -21,12 +21,10 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from oracle import ref_torch as rt  # noqa: E402
 from tests import deepnmt_ref as D  # noqa: E402
 from tests import variant_gpu as G  # noqa: E402
 from tests import variant_ref as V  # noqa: E402
 from zero_amd.models import load_all  # noqa: E402
-from zero_amd.models._factory import get_core, reset_cores  # noqa: E402
 
 load_all()
 MODEL = "deepnmt"
@@ -67,29 +65,15 @@ def test_step_launch_formula():
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_fp32_mode_is_token_exact(fx, K):
-    ref = fx["ref"](K, key=("plain", K))
-    seqs, scores, core = G.decode(G.beam_hp(fx["hp"], K, "float32"), MODEL, fx["Pn"], fx["src"])
-    G.assert_tokens(seqs, ref["seq"])
-    fin = ref["score"] > -1e30
-    rtol, atol = fx["tol"]
-    print("(%s) K=%d: largest score difference %.3e" % (fx["config"], K, np.abs(scores - ref["score"])[fin].max()))
-    assert np.allclose(scores[fin], ref["score"][fin], rtol=rtol, atol=atol), np.abs(scores - ref["score"])[fin].max()
+    core = G.fp32_exact(fx, MODEL, K, "(%s) " % fx["config"])
     assert core.__dict__.get("_decode_step_launches", 0) >= step_launches(fx["hp"], True)
 
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_bf16_mode(fx, K):
-    from zero_amd.search import decode_hypothesis
-    Pn = V.sharpen(fx["hp"], fx["Pn"])
-    ref = fx["ref"](K, Pn=Pn, key=("sharp", K))
-    hp = G.beam_hp(fx["hp"], K, "bfloat16")
-    seqs, scores, core = G.decode(hp, MODEL, Pn, fx["src"])
     own = step_launches(fx["hp"], False)
+    core = G.bf16_best(fx, MODEL, K, "(%s) %d launches of the model's own, " % (fx["config"], own))
     assert core.__dict__.get("_decode_step_launches", 0) >= own                  # the step ran from captured graphs
-    print("(%s) K=%d: %d launches per captured step (%d of them the model's), top score diff %.3e"
-          % (fx["config"], K, core._decode_step_launches, own, np.abs(scores[:, 0] - ref["score"][:, 0]).max()))
-    hyp, hyp_ref = decode_hypothesis(seqs, hp), rt.decode_hypothesis(ref["seq"], hp)
-    assert hyp == hyp_ref, (hyp, hyp_ref)
 
 
 def test_fp32_source_padding(fa, monkeypatch):
@@ -97,16 +81,7 @@ def test_fp32_source_padding(fa, monkeypatch):
     encoder stack carries the state over it -- in either direction -- and the attention gives it the weight 0; its rows of the
     residual stream are computed and never read.  Tokens equal, scores within the fp32 tolerance -- not bitwise: the K-slicing
     of the fp32 GEMM depends on its row count, and the encoder's products have B * Ls rows."""
-    out = []
-    for pad in ("1", "8"):
-        monkeypatch.setenv("ZERO_HIP_DECODE_PAD_LEN", pad)
-        seqs, scores, _ = G.decode(G.beam_hp(fa["hp"], 4, "float32"), MODEL, fa["Pn"], fa["src"])
-        out.append((seqs, scores))
-    G.assert_tokens(out[0][0], out[1][0])
-    fin = out[0][1] > -1e30
-    rtol, atol = fa["tol"]
-    print("largest score difference between the paddings %.3e" % np.abs(out[0][1] - out[1][1])[fin].max())
-    assert np.array_equal(fin, out[1][1] > -1e30) and np.allclose(out[0][1][fin], out[1][1][fin], rtol=rtol, atol=atol)
+    G.assert_padding_within_tol(fa, MODEL, monkeypatch)
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
@@ -119,16 +94,7 @@ def test_step_graphs_are_reused_across_batches(fa, dtype):
 
 
 def test_four_lanes_equal_one_lane(fa):
-    from zero_amd.evalu import decode_many
-    hp = G.beam_hp(fa["hp"], 4, "bfloat16")
-    reset_cores(); get_core(hp, MODEL, V.sharpen(fa["hp"], fa["Pn"]))
-    batches = [V.ragged(tuple(int(x) for x in np.random.default_rng(i).integers(5, 15, 3 + i % 2)), hp.src_vocab.size(), 10 + i)
-               for i in range(6)]
-    work = G.lane_worker(MODEL, hp)
-    one = decode_many(batches, work, streams=1)
-    four = decode_many(batches, work, streams=4)
-    for i, (a, b) in enumerate(zip(one, four)):
-        assert a[2] == b[2] and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), i
+    G.assert_four_lanes_equal_one(fa, MODEL)
 
 
 @pytest.mark.parametrize("mode", ["eager", "host_book"])
@@ -138,14 +104,7 @@ def test_the_other_search_modes_equal_the_device_resident_one(monkeypatch, mode,
     decode what the device-resident search decodes: reorder() / bind_caches() of the per-layer ping-pong state serve all three.
     (B) has the plain-form layer, whose single cell launch must never run in place: the eager search's first step follows no
     reorder."""
-    f = _fixture(config)
-    hp = G.beam_hp(f["hp"], 4, "float32")
-    base = G.decode(hp, MODEL, f["Pn"], f["src"])
-    monkeypatch.setenv("ZERO_HIP_DECODE_GRAPH" if mode == "eager" else "ZERO_HIP_DECODE_DEVICE_BOOK", "0")
-    seqs, scores, _ = G.decode(hp, MODEL, f["Pn"], f["src"])
-    G.assert_tokens(seqs, base[0])
-    fin = base[1] > -1e30
-    assert np.allclose(scores[fin], base[1][fin], rtol=f["tol"][0], atol=f["tol"][1])
+    G.assert_search_mode_equals_device(_fixture(config), MODEL, monkeypatch, mode)
 
 
 def test_bf16_mode_names_its_limit_and_fp32_decodes_the_same_model():
@@ -168,27 +127,5 @@ def test_cli_mode_test(tmp_path):
     """The reference's command line in a fresh interpreter: `--mode test` on files with model_name=deepnmt (freshly
     initialised weights: there is no training to make a checkpoint), hidden_size != embed_size, three decoder layers, in both
     decode modes; the evaluation loop decodes its batches on lanes and writes one translation per source line."""
-    import os
-    import subprocess
-    import sys
-    rng = np.random.default_rng(3)
-    words = ["w%d" % i for i in range(12)]
-    (tmp_path / "vocab.txt").write_text("\n".join(words) + "\n")
-    lines = [" ".join(rng.choice(words, size=int(rng.integers(2, 7)))) for _ in range(8)]
-    for name in ("test.src", "test.tgt"):
-        (tmp_path / name).write_text("\n".join(lines) + "\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYTHONPATH=root)
-    common = "model_name=deepnmt,scope_name=deepnmt,cell=atr,num_heads=1,num_encoder_layer=2,num_decoder_layer=3," \
-             "hidden_size=32,embed_size=24,eval_batch_size=3,beam_size=2," \
-             "decode_length=4,initializer=uniform_unit_scaling,initializer_gain=1.0,output_dir=%s," % (tmp_path / "out") + \
-             ",".join("%s=%s" % (k, tmp_path / v) for k, v in dict(
-                 src_vocab_file="vocab.txt", tgt_vocab_file="vocab.txt", src_test_file="test.src", tgt_test_file="test.tgt").items())
-    for dtype in ("bfloat16", "float32"):
-        out = tmp_path / ("t_%s.txt" % dtype)
-        r = subprocess.run([sys.executable, "-m", "zero_amd.run", "--mode", "test", "--parameters",
-                            common + ",decode_dtype=%s,test_output=%s" % (dtype, out)],
-                           env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        assert "bleu" in r.stdout
-        assert len(out.read_text().splitlines()) == 8
+    G.cli_mode_test(tmp_path, "model_name=deepnmt,scope_name=deepnmt,cell=atr,num_heads=1,num_encoder_layer=2,"
+                              "num_decoder_layer=3,hidden_size=32,embed_size=24")

@@ -1,5 +1,5 @@
 """rnnsearch_deepatt and deepnmt decoding with the lrn / olrn cells, end to end against the references restated in
-tests/lrn_ref.py (the restatements of tests/deepatt_ref.py and tests/deepnmt_ref.py with the cell dispatch widened).
+tests/deepatt_ref.py and tests/deepnmt_ref.py, whose cell dispatch runs all four cells (fixtures: tests/lrn_ref.py).
 
 Fixtures (vocabularies 120 / 104, B = 4 sources of 14, 5, 9 and 11 tokens):
     rnnsearch_deepatt, lrn and olrn: the sizes of tests/test_gpu_deepatt_model.py (H 128, E 64, NE = D = 2) -- a forward, a
@@ -7,7 +7,7 @@ Fixtures (vocabularies 120 / 104, B = 4 sources of 14, 5, 9 and 11 tokens):
     deepnmt olrn_ca: configuration (A) of tests/deepnmt_ref.py (caencoder, dl4mt_redict, NE 2, ND 3): the reversed paired scan of
         the encoder and the paired one-step launches of the one-to-one decoder layers run;
     deepnmt lrn_plain: configuration (B) (NE 1, ND 2, H = E = 64): the plain backward scan into a column slice, the [x | c] layer.
-lrn_ref's make_fixture measures on the CPU, and asserts there, what the reference alone shows on each (seeds and figures in
+make_fixture measures on the CPU, and asserts there, what the reference alone shows on each (seeds and figures in
 the docstring of tests/lrn_ref.py).
 
 fp32 mode: every hypothesis of every beam token-equal, scores within score_tol.  bf16 mode: output distribution sharpened x 6,
@@ -22,8 +22,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-from oracle import ref_torch as rt  # noqa: E402
 from tests import deepatt_ref as DA  # noqa: E402
+from tests import deepnmt_ref as DN  # noqa: E402
 from tests import decode_trace as DT  # noqa: E402
 from tests import lrn_ref as L  # noqa: E402
 from tests import variant_gpu as G  # noqa: E402
@@ -40,9 +40,9 @@ STEP_LAUNCHES = 6 + 4 * D           # embed, projection, lower cell, D x (feed_q
 @functools.lru_cache(maxsize=None)
 def _fixture(name):
     if name.startswith("deepatt_"):
-        model, hp, M = "rnnsearch_deepatt", L.deepatt_hp(name[len("deepatt_"):]), L.deepatt
+        model, hp, M = "rnnsearch_deepatt", L.deepatt_hp(name[len("deepatt_"):]), DA
     else:
-        model, hp, M = "deepnmt", L.deepnmt_hp(name[len("deepnmt_"):]), L.deepnmt
+        model, hp, M = "deepnmt", L.deepnmt_hp(name[len("deepnmt_"):]), DN
     src = V.ragged(L.LENGTHS, hp.src_vocab.size(), 5)
     f = M.make_fixture(hp, src, L.SEEDS[name])
     print("fixture %s: smallest candidate gap %.3e, largest fp32 - float64 score difference %.3e (x %.0f), %.3f of the fp32 "
@@ -62,39 +62,15 @@ def fn(request):
     return _fixture(request.param)
 
 
-def _fp32_exact(f, K):
-    ref = f["ref"](K, key=("plain", K))
-    seqs, scores, core = G.decode(G.beam_hp(f["hp"], K, "float32"), f["model"], f["Pn"], f["src"])
-    G.assert_tokens(seqs, ref["seq"])
-    fin = ref["score"] > -1e30
-    rtol, atol = f["tol"]
-    print("%s K=%d: largest score difference %.3e" % (f["name"], K, np.abs(scores - ref["score"])[fin].max()))
-    assert np.allclose(scores[fin], ref["score"][fin], rtol=rtol, atol=atol), np.abs(scores - ref["score"])[fin].max()
-    return core
-
-
-def _bf16_best(f, K):
-    from zero_amd.search import decode_hypothesis
-    Pn = V.sharpen(f["hp"], f["Pn"])
-    ref = f["ref"](K, Pn=Pn, key=("sharp", K))
-    hp = G.beam_hp(f["hp"], K, "bfloat16")
-    seqs, scores, core = G.decode(hp, f["model"], Pn, f["src"])
-    print("%s K=%d: %d launches per captured step, top score diff %.3e"
-          % (f["name"], K, core.__dict__.get("_decode_step_launches", 0), np.abs(scores[:, 0] - ref["score"][:, 0]).max()))
-    hyp, hyp_ref = decode_hypothesis(seqs, hp), rt.decode_hypothesis(ref["seq"], hp)
-    assert hyp == hyp_ref, (hyp, hyp_ref)
-    return core
-
-
 # ---------------------------------------------------------------------------------------------- rnnsearch_deepatt
 @pytest.mark.parametrize("K", [1, 4])
 def test_deepatt_fp32_mode_is_token_exact(fx, K):
-    _fp32_exact(fx, K)
+    G.fp32_exact(fx, fx["model"], K, fx["name"] + " ")
 
 
 @pytest.mark.parametrize("K", [1, 4])
 def test_deepatt_bf16_mode(fx, K):
-    core = _bf16_best(fx, K)
+    core = G.bf16_best(fx, fx["model"], K, fx["name"] + " ")
     assert core.__dict__.get("_decode_step_launches", 0) >= STEP_LAUNCHES       # the step ran from captured graphs
 
 
@@ -102,16 +78,7 @@ def test_deepatt_fp32_source_padding(fx, monkeypatch):
     """ZERO_HIP_DECODE_PAD_LEN = 1 (14 source positions) and = 8 (16): a padded position has mask 0, so every scan carries the
     state over it -- the reversed scans meet the padding FIRST -- and the attentions give it the weight 0.  Tokens equal, scores
     within the fp32 tolerance (not bitwise: the K-slicing of the fp32 GEMM depends on its row count)."""
-    out = []
-    for pad in ("1", "8"):
-        monkeypatch.setenv("ZERO_HIP_DECODE_PAD_LEN", pad)
-        seqs, scores, _ = G.decode(G.beam_hp(fx["hp"], 4, "float32"), fx["model"], fx["Pn"], fx["src"])
-        out.append((seqs, scores))
-    G.assert_tokens(out[0][0], out[1][0])
-    fin = out[0][1] > -1e30
-    rtol, atol = fx["tol"]
-    print("largest score difference between the paddings %.3e" % np.abs(out[0][1] - out[1][1])[fin].max())
-    assert np.array_equal(fin, out[1][1] > -1e30) and np.allclose(out[0][1][fin], out[1][1][fin], rtol=rtol, atol=atol)
+    G.assert_padding_within_tol(fx, fx["model"], monkeypatch)
 
 
 @pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
@@ -122,56 +89,19 @@ def test_deepatt_step_graphs_are_reused_across_batches(fx, dtype):
 
 
 def test_deepatt_four_lanes_equal_one_lane(fx):
-    from zero_amd.evalu import decode_many
-    hp = G.beam_hp(fx["hp"], 4, "bfloat16")
-    reset_cores(); get_core(hp, fx["model"], V.sharpen(fx["hp"], fx["Pn"]))
-    batches = [V.ragged(tuple(int(x) for x in np.random.default_rng(i).integers(5, 15, 3 + i % 2)), hp.src_vocab.size(), 10 + i)
-               for i in range(6)]
-    work = G.lane_worker(fx["model"], hp)
-    one = decode_many(batches, work, streams=1)
-    four = decode_many(batches, work, streams=4)
-    for i, (a, b) in enumerate(zip(one, four)):
-        assert a[2] == b[2] and np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), i
+    G.assert_four_lanes_equal_one(fx, fx["model"])
 
 
 @pytest.mark.parametrize("mode", ["eager", "host_book"])
 def test_deepatt_other_search_modes_equal_the_device_resident_one(fx, monkeypatch, mode):
-    hp = G.beam_hp(fx["hp"], 4, "float32")
-    base = G.decode(hp, fx["model"], fx["Pn"], fx["src"])
-    monkeypatch.setenv("ZERO_HIP_DECODE_GRAPH" if mode == "eager" else "ZERO_HIP_DECODE_DEVICE_BOOK", "0")
-    seqs, scores, _ = G.decode(hp, fx["model"], fx["Pn"], fx["src"])
-    G.assert_tokens(seqs, base[0])
-    fin = base[1] > -1e30
-    assert np.allclose(scores[fin], base[1][fin], rtol=fx["tol"][0], atol=fx["tol"][1])
+    G.assert_search_mode_equals_device(fx, fx["model"], monkeypatch, mode)
 
 
 def test_cli_mode_test(tmp_path):
     """`--mode test` in a fresh interpreter with model_name=rnnsearch_deepatt and cell=lrn (freshly initialised weights),
     hidden_size 32 / embed_size 24, in both decode modes: one translation per source line."""
-    import os
-    import subprocess
-    import sys
-    rng = np.random.default_rng(3)
-    words = ["w%d" % i for i in range(12)]
-    (tmp_path / "vocab.txt").write_text("\n".join(words) + "\n")
-    lines = [" ".join(rng.choice(words, size=int(rng.integers(2, 7)))) for _ in range(8)]
-    for name in ("test.src", "test.tgt"):
-        (tmp_path / name).write_text("\n".join(lines) + "\n")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYTHONPATH=root)
-    common = "model_name=rnnsearch_deepatt,scope_name=deepatt_lrn,cell=lrn,num_heads=1,num_encoder_layer=2,num_decoder_layer=2," \
-             "hidden_size=32,embed_size=24,eval_batch_size=3,beam_size=2," \
-             "decode_length=4,initializer=uniform_unit_scaling,initializer_gain=1.0,output_dir=%s," % (tmp_path / "out") + \
-             ",".join("%s=%s" % (k, tmp_path / v) for k, v in dict(
-                 src_vocab_file="vocab.txt", tgt_vocab_file="vocab.txt", src_test_file="test.src", tgt_test_file="test.tgt").items())
-    for dtype in ("bfloat16", "float32"):
-        out = tmp_path / ("t_%s.txt" % dtype)
-        r = subprocess.run([sys.executable, "-m", "zero_amd.run", "--mode", "test", "--parameters",
-                            common + ",decode_dtype=%s,test_output=%s" % (dtype, out)],
-                           env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        assert "bleu" in r.stdout
-        assert len(out.read_text().splitlines()) == 8
+    G.cli_mode_test(tmp_path, "model_name=rnnsearch_deepatt,scope_name=deepatt_lrn,cell=lrn,num_heads=1,num_encoder_layer=2,"
+                              "num_decoder_layer=2,hidden_size=32,embed_size=24")
 
 
 # ---------------------------------------------------------------------------------------------- the launch structure
@@ -227,11 +157,11 @@ def test_atr_issues_no_scan_launch(monkeypatch):
 
 # ---------------------------------------------------------------------------------------------- deepnmt
 def test_deepnmt_fp32_mode_is_token_exact(fn):
-    _fp32_exact(fn, 4)
+    G.fp32_exact(fn, fn["model"], 4, fn["name"] + " ")
 
 
 def test_deepnmt_bf16_mode(fn):
-    _bf16_best(fn, 4)
+    G.bf16_best(fn, fn["model"], 4, fn["name"] + " ")
 
 
 def test_deepnmt_one_to_one_layers_are_one_paired_launch(monkeypatch):

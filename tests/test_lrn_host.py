@@ -9,6 +9,8 @@ import pytest
 import torch
 
 from oracle import ref_torch as rt
+from tests import deepatt_ref as DA
+from tests import deepnmt_ref as DN
 from tests import lrn_ref as L
 from tests import variant_ref as V
 from tests.common import make_hp
@@ -57,11 +59,12 @@ def test_rnnsearch_still_refuses_the_new_cells():
 
 
 def test_the_gru_size_limit_does_not_apply():
-    """check_shape reads core.cell, H and E only: the 2048 limit of the additive attention holds for every cell, the GRU's LDS
-    limit is the GRU's, and the recipe's 1000 / 620 is taken by the fp32 mode and refused by the bf16 mode as for atr."""
-    from zero_amd.models import _deepatt, _deepnmt
-    core = lambda cell, H, E: type("C", (), {"cell": cell, "H": H, "E": E})()
-    for mod in (_deepatt, _deepnmt):
+    """check_shape reads the model's name, core.cell, H, E and M only: the 2048 limit of the additive attention holds for every
+    cell, the GRU's LDS limit is the GRU's, and the recipe's 1000 / 620 is taken by the fp32 mode and refused by the bf16 mode as
+    for atr."""
+    from zero_amd.models import _rnn as mod
+    for model in ("rnnsearch_deepatt", "deepnmt"):
+        core = lambda cell, H, E: type("C", (), {"model": model, "cell": cell, "H": H, "E": E, "M": H})()
         for cell in CELLS:
             mod.check_shape(core(cell, 1000, 624), False)
             mod.check_shape(core(cell, 1000, 620), True)
@@ -275,7 +278,7 @@ def test_null_state_and_no_mask():
 @pytest.mark.parametrize("NE,ND", [(2, 2), (0, 1)])
 def test_deepatt_full_decoder_equals_the_cached_steps(cell, NE, ND):
     hp = _tiny("rnnsearch_deepatt", cell, NE, ND)
-    M = L.deepatt
+    M = DA
     P = rt.to_torch(M.init_params(hp, 2), dtype=torch.float64)
     src = torch.as_tensor(V.ragged((6, 3, 5), hp.src_vocab.size(), 2))
     tgt = torch.as_tensor(np.random.default_rng(3).integers(3, hp.tgt_vocab.size(), (3, 5)))
@@ -293,7 +296,7 @@ def test_deepatt_full_decoder_equals_the_cached_steps(cell, NE, ND):
 @pytest.mark.parametrize("cell,ca,deep,redict", [("olrn", True, False, True), ("lrn", False, False, False), ("lrn", True, True, False)])
 def test_deepnmt_full_decoder_equals_the_cached_steps(cell, ca, deep, redict):
     hp = _tiny("deepnmt", cell, 2, 3, caencoder=ca, use_deep_att=deep, dl4mt_redict=redict)
-    M = L.deepnmt
+    M = DN
     P = rt.to_torch(M.init_params(hp, 2), dtype=torch.float64)
     src = torch.as_tensor(V.ragged((6, 3, 5), hp.src_vocab.size(), 2))
     tgt = torch.as_tensor(np.random.default_rng(3).integers(3, hp.tgt_vocab.size(), (3, 5)))
@@ -310,9 +313,9 @@ def test_deepnmt_full_decoder_equals_the_cached_steps(cell, ca, deep, redict):
 def test_restated_encoder_is_the_scan_reference():
     """The torch restatement of a one-to-one encoder layer and lrn_scan (the kernel's statement) are the same function."""
     hp = _tiny("rnnsearch_deepatt", "olrn", 1, 1)
-    P = rt.to_torch(L.deepatt.init_params(hp, 4), dtype=torch.float64)
+    P = rt.to_torch(DA.init_params(hp, 4), dtype=torch.float64)
     src = torch.as_tensor(V.ragged((5, 3), hp.src_vocab.size(), 1))
-    st = L.deepatt.encoder(src, hp, P)
+    st = DA.encoder(src, hp, P)
     x = P["src_embedding"][src] + P["bias"]
     mask = (src != 0).double().numpy().T
     tm = lambda a: a.numpy().transpose(1, 0, 2)
@@ -327,10 +330,10 @@ FIXTURES = ["deepatt_lrn", "deepatt_olrn", "deepnmt_olrn_ca", "deepnmt_lrn_plain
 
 
 def fixture_of(name):
-    """-> (hparams, the rebound reference module)."""
+    """-> (hparams, the model's reference module)."""
     if name.startswith("deepatt_"):
-        return L.deepatt_hp(name[len("deepatt_"):]), L.deepatt
-    return L.deepnmt_hp(name[len("deepnmt_"):]), L.deepnmt
+        return L.deepatt_hp(name[len("deepatt_"):]), DA
+    return L.deepnmt_hp(name[len("deepnmt_"):]), DN
 
 
 @pytest.mark.parametrize("name", FIXTURES)

@@ -5,6 +5,7 @@ constants that are their own, and take from here
 ``STORAGE``, ``ragged``, ``sharpen``      the storage types of the kernel forms, the padded id matrices and the sharpened model
 ``storage_model`` / ``search``            oracle.ref_torch's beam search over a restated (encoding_fn, decoding_fn) pair
 ``candidate_margin``                      the measurement that the REFERENCE ALONE is far from a tie on a fixture
+``init_params`` / ``make_fixture``        the recurrent models' random weights and what the REFERENCE ALONE shows on them
 ``assert_within`` / ``exceeds``           the element-wise check of a kernel (or stand-in) against its float64 statement
 ``embed_step`` / ``embed_shifted`` / ``cached_state`` / ``empty_caches``   the Transformer decoder's inputs and caches
 """
@@ -93,6 +94,44 @@ def candidate_margin(search_fn, hp, Pn, src, beams=(1, 4), factor=4.0, tol=None,
                 rel = max(rel, float((diff / (tol[0] + tol[1] * np.abs(s64[:, :2 * K])))[live].max()))
     assert gap > factor * err, (gap, err, seed)
     return {"gap": gap, "err": err} if tol is None else {"gap": gap, "err": err, "rel": rel}
+
+
+def init_params(hp, model, seed):
+    """Every variable of zero_amd.variables.variable_specs(hp, model) from its initial distribution (weights and embeddings
+    from the scope initialiser; "zeros" and "ones" draw nothing), with the biases and LayerNorm pairs perturbed so that every
+    term is exercised."""
+    from tests.common import perturb
+    from zero_amd.variables import variable_specs
+    rng = np.random.default_rng(seed)
+    Pn = {}
+    for name, shape, kind, _ in variable_specs(hp, model):
+        if kind in ("zeros", "ones"):
+            v = np.zeros(shape) if kind == "zeros" else np.ones(shape)
+        else:
+            v = rt._scope_init(rng, shape, hp.initializer, hp.initializer_gain)
+        Pn[name] = np.asarray(v, np.float32)
+    return perturb(Pn, rng)
+
+
+def make_fixture(model, decoding_fns, tol, hp, src, seed, factor=4.0):
+    """The tiny model of the GPU model tests with what the REFERENCE ALONE shows on it, measured on the CPU and asserted,
+    for beam 1 and 4:
+      * candidate_margin: the float64 and the fp32 run give identical hypotheses and candidate orders, and the smallest gap
+        between a kept candidate and its runner-up exceeds factor x err, the largest fp32 - float64 score difference;  rel:
+        that difference as a share of ATOL + RTOL |score_float64|, tol = (ATOL, RTOL) -- how much of the project's fp32 score
+        tolerance the fp32 reference itself uses up (rnnsearch_ref.score_tol);
+      * with the output embedding sharpened x 6, the bf16-storage restatement (rt.Cfg.store_bf16) keeps the best hypothesis
+        of every sentence of the fp32 run.
+    -> dict Pn, gap, err, rel (the worst over both beams)."""
+    Pn = init_params(hp, model, seed)
+    run = lambda *a, **k: search(decoding_fns, *a, **k)
+    m = candidate_margin(run, hp, Pn, src, factor=factor, tol=tol, seed=seed)
+    Ps = sharpen(hp, Pn)
+    for K in (1, 4):
+        a, _ = run(hp, Ps, src, K, torch.float32)
+        b, _ = run(hp, Ps, src, K, torch.float32, store_bf16=True)
+        assert rt.decode_hypothesis(a["seq"], hp) == rt.decode_hypothesis(b["seq"], hp), ("bf16 storage model", K, seed)
+    return dict(m, Pn=Pn)
 
 
 # ---------------------------------------------------------------------------------------------- the element-wise check

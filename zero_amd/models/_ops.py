@@ -5,8 +5,8 @@ attention or an embedding in the storage type of its mode.
 An ops object belongs to one core, one storage type and one buffer prefix.  ``Bf16Ops`` issues the bf16 launches (``zk_gemm``,
 ``zk_attn_fwd``, ``zk_rela_attn``, ``zk_dec_embed``) on the bf16 shadow weights, ``F32Ops`` the ``zk_f32_*`` launches
 (include/zero_hip.h) on the fp32 masters; ``ops_for`` picks between them.  The schedules of models/_decode.py (start-up),
-_decode_f32.py, _score_f32.py, _fixup.py, _l0drop.py, _rnnsearch.py, _deepatt.py and _deepnmt.py are written once against this
-interface.
+_decode_f32.py, _score_f32.py, _fixup.py, _l0drop.py and of the recurrent models (_rnn.py with _rnnsearch.py, _deepatt.py and
+_deepnmt.py) are written once against this interface.
 
 The prefix keeps the buffers of two passes of one engine apart (DESIGN.md has the table): ``dc.`` / ``dq.`` for the bf16 / fp32
 decode, ``fx.`` / ``dq.fx.`` for transformer_fixup, ``dc.rn.`` / ``dq.rn.`` for rnnsearch, rnnsearch_deepatt and deepnmt (each on its

@@ -56,7 +56,7 @@ def infer_fn(params):
     from zero_amd import shortlist
     shortlist.check(params, "deepnmt")
     check_params(params)
-    from zero_amd.models._deepnmt import make_infer_fns
+    from zero_amd.models._rnn import make_infer_fns
     return make_infer_fns(params, "deepnmt")
 
 

@@ -44,7 +44,7 @@ def infer_fn(params):
     from zero_amd import shortlist
     shortlist.check(params, "rnnsearch")
     check_params(params)
-    from zero_amd.models._rnnsearch import make_infer_fns
+    from zero_amd.models._rnn import make_infer_fns
     return make_infer_fns(params, "rnnsearch")
 
 

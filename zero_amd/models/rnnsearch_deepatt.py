@@ -57,7 +57,7 @@ def infer_fn(params):
     from zero_amd import shortlist
     shortlist.check(params, "rnnsearch_deepatt")
     check_params(params)
-    from zero_amd.models._deepatt import make_infer_fns
+    from zero_amd.models._rnn import make_infer_fns
     return make_infer_fns(params, "rnnsearch_deepatt")
 
 
