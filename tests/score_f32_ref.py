@@ -194,8 +194,12 @@ def attn_bound(name, x):
       output   one division by the running sum and one rounding: + 2 u |o_c|.
     A row without a live key (there is none in a correct run) would have the bound 0."""
     cs = ATTN_CASES[name]
-    B, nh, d, Lq, Lk = (cs[x_] for x_ in ("B", "nh", "d", "Lq", "Lk"))
-    r = attn_f64(name, x)
+    return attn_bound_from(attn_f64(name, x), cs["B"], cs["nh"], cs["Lq"], cs["d"])
+
+
+def attn_bound_from(r, B, nh, Lq, d):
+    """attn_bound on the pieces of a float64 statement (the dict attn_f64 returns); tests/f32_ref.py states zk_f32_attn in the
+    same terms (kv_group, a cached key count, a key bias) and is held to the same bound."""
     p, lg = r["p"], r["lg"]
     ds = (d + 2) * U * r["s_abs"] + U * np.abs(r["s"])
     ds[r["full"]] = 0.0
