@@ -19,69 +19,14 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from tests.util_gpu import eng  # noqa: E402
-from tests import parity as P  # noqa: E402
 from tests import deepatt_ref as D  # noqa: E402
 from tests import variant_ref as V  # noqa: E402
+from tests.rnn_cell_cases import gru_inputs as _gru_inputs, gru_run as _gru_run  # noqa: E402
 from zero_amd.func import Mat  # noqa: E402
 from zero_amd.hip import ZeroHipError  # noqa: E402
 
 BF, F32 = torch.bfloat16, torch.float32
 ST = {"bf16": BF, "fp32": F32}
-
-
-def G(rows, cols, ld=None, off=0, dtype=BF, prefill=None):
-    return P.guarded(rows, cols, ld, off, dtype, prefill, "cuda")
-
-
-def _t(a):
-    return torch.as_tensor(np.asarray(a, np.float64))
-
-
-def _gru_inputs(Rn, H, form, seed, n_prev, u_zero=False):
-    """float64 arrays whose values are exactly representable where the kernels read them: Ug, Uh, xg and xh in the storage
-    type, the state and the biases in fp32."""
-    g = np.random.default_rng(200 + seed)
-    st = lambda a: _t(a).float().to(ST[form]).double().numpy()
-    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
-    x = dict(h_prev=f32(g.normal(0, 1, (n_prev, H))), Ug=st(g.normal(0, H ** -0.5, (H, 2 * H))), bg=f32(g.normal(0, 0.3, 2 * H)),
-             Uh=st(g.normal(0, H ** -0.5, (H, H))), bh=f32(g.normal(0, 0.3, H)), xg=st(g.normal(0, 1, (Rn, 2 * H))),
-             xh=st(g.normal(0, 1, (Rn, H))), mask=(np.arange(Rn) % 3 != 1).astype(np.float64), idx=g.integers(0, n_prev, Rn))
-    x["idx"][:3] = (n_prev - 1, n_prev - 1, 0)         # repeated rows
-    if u_zero:
-        x["Ug"], x["Uh"] = np.zeros((H, 2 * H)), np.zeros((H, H))
-        x["h_prev"] = f32(x["h_prev"] * (1 + 2.0 ** -12))
-        assert not np.array_equal(D._bf(x["h_prev"]), x["h_prev"])
-    return x
-
-
-def _gru_run(x, form, with_state=True, with_idx=True, with_mask=True):
-    """-> dict z, rh, out, copy (float64 arrays) of one Engine.rnn_gru_step on guarded buffers."""
-    e = eng()
-    st = ST[form]
-    Rn, H = x["xh"].shape
-    n_prev = x["h_prev"].shape[0]
-    # (R = 5: row strides that are no multiple of 16 bytes -- the scalar loads of the state and of rh; else the 16-byte ones)
-    odd = Rn == 5
-    hp = G(n_prev, H, H + (13 if odd else 12), 4, F32, _t(x["h_prev"]))
-    Ug = G(H, 2 * H, 2 * H + 8, 0, st, _t(x["Ug"]))
-    Uh = G(H, H, H + 8, 0, st, _t(x["Uh"]))
-    bg = G(1, 2 * H, dtype=F32, prefill=_t(x["bg"]))
-    bh = G(1, H, dtype=F32, prefill=_t(x["bh"]))
-    xg = G(Rn, 2 * H, 3 * H + 8, 8, st, _t(x["xg"]))
-    xh = G(Rn, H, 2 * H + 8, 8, st, _t(x["xh"]))
-    m = G(Rn, 1, 3, 1, F32, _t(x["mask"]))
-    idx = torch.as_tensor(x["idx"].astype(np.int32)).cuda()
-    z, rh = G(Rn, H, H + 4, 4, F32), G(Rn, H, H + (11 if odd else 16), 8, st)
-    out, cp = G(Rn, H, 3 * H + 4, 4, F32), G(Rn, H, H + 16, 8, st)
-    e.rnn_gru_step(hp.mat if with_state else None, Ug.mat, bg.t[P.LEAD:P.LEAD + 2 * H], Uh.mat, bh.t[P.LEAD:P.LEAD + H], xg.mat,
-                   xh.mat, z.mat, rh.mat, out.mat, cp.mat, idx=idx if (with_idx and with_state) else None,
-                   mask=m.mat if with_mask else None)
-    torch.cuda.synchronize()
-    for buf, what in ((hp, "h_prev"), (Ug, "Ug"), (Uh, "Uh"), (bg, "bg"), (bh, "bh"), (xg, "xg"), (xh, "xh"), (m, "mask")):
-        buf.check_intact("gru_step " + what)
-    for buf, what in ((z, "z"), (rh, "rh"), (out, "state"), (cp, "copy")):
-        buf.check_guard("gru_step " + what)
-    return {k: b.value().double().numpy() for k, b in dict(z=z, rh=rh, out=out, copy=cp).items()}
 
 
 def _check(got, ref, form, label):

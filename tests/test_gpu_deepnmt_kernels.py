@@ -22,6 +22,7 @@ from tests.util_gpu import eng  # noqa: E402
 from tests import parity as P  # noqa: E402
 from tests import deepnmt_ref as D  # noqa: E402
 from tests import variant_ref as V  # noqa: E402
+from tests.rnn_cell_cases import ff_run as _run  # noqa: E402
 from zero_amd.func import Mat  # noqa: E402
 from zero_amd.hip import ZeroHipError  # noqa: E402
 
@@ -29,34 +30,8 @@ BF, F32 = torch.bfloat16, torch.float32
 ST = {"bf16": BF, "fp32": F32}
 
 
-def G(rows, cols, ld=None, off=0, dtype=BF, prefill=None):
-    return P.guarded(rows, cols, ld, off, dtype, prefill, "cuda")
-
-
 def _t(a):
     return torch.as_tensor(np.asarray(a, np.float64))
-
-
-def _run(x, form, in_place=False, with_copy=True):
-    """-> (out, copy or None) as float64 arrays of one Engine.rnn_ff_residual on guarded buffers."""
-    e = eng()
-    st = ST[form]
-    R, K = x["a"].shape
-    N = x["W"].shape[1]
-    odd = R % 2 == 1          # a row stride of a that is no multiple of 16 bytes: the scalar loads of the bf16 form
-    a = G(R, K, K + (13 if odd else 16), 5 if odd else 8, st, _t(x["a"]))
-    W = G(K, N, N + 8, 0, st, _t(x["W"]))
-    b = G(1, N, dtype=F32, prefill=_t(x["b"]))
-    xs = G(R, N, N + 4, 4, F32, _t(x["x"]))
-    out = xs if in_place else G(R, N, 2 * N + 4, 4, F32)
-    cp = G(R, N, N + K + 16, 8, st) if with_copy else None        # the x columns of a wider [. | x | c] operand
-    e.rnn_ff_residual(a.mat, W.mat, b.t[P.LEAD:P.LEAD + N], xs.mat, out.mat, cp.mat if with_copy else None)
-    torch.cuda.synchronize()
-    for buf, what in ((a, "a"), (W, "W"), (b, "b")) + (() if in_place else ((xs, "x"),)):
-        buf.check_intact("ff_residual " + what)
-    for buf, what in ((out, "out"),) + (((cp, "copy"),) if with_copy else ()):
-        buf.check_guard("ff_residual " + what)
-    return out.value().double().numpy(), cp.value().double().numpy() if with_copy else None
 
 
 def _shapes(form):

@@ -21,6 +21,7 @@ from tests.util_gpu import eng  # noqa: E402
 from tests import parity as P  # noqa: E402
 from tests import rnnsearch_ref as R  # noqa: E402
 from tests import variant_ref as V  # noqa: E402
+from tests.rnn_cell_cases import atr_inputs as _atr_inputs, atr_run as _atr_run  # noqa: E402
 from zero_amd.func import Mat  # noqa: E402
 from zero_amd.hip import ZeroHipError  # noqa: E402
 
@@ -37,46 +38,6 @@ def _t(a):
 
 
 # ---------------------------------------------------------------------------------------------- the ATR step
-def _atr_inputs(Rn, H, form, seed, n_prev, u_zero=False):
-    """float64 arrays whose values are exactly representable where the kernel reads them: U and p in the storage type, the
-    state and the bias in fp32."""
-    g = np.random.default_rng(100 + seed)
-    st = lambda a: _t(a).float().to(ST[form]).double().numpy()
-    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
-    x = dict(h_prev=f32(g.normal(0, 1, (n_prev, H))), U=st(g.normal(0, H ** -0.5, (H, H))), b=f32(g.normal(0, 0.3, H)),
-             p=st(g.normal(0, 1, (Rn, H))), mask=(np.arange(Rn) % 3 != 1).astype(np.float64),
-             idx=g.integers(0, n_prev, Rn))
-    x["idx"][:3] = (n_prev - 1, n_prev - 1, 0)         # repeated rows
-    if u_zero:
-        x["U"] = np.zeros((H, H))
-        x["h_prev"] = f32(x["h_prev"] * (1 + 2.0 ** -12))
-        assert not np.array_equal(R._bf(x["h_prev"]), x["h_prev"])
-    return x
-
-
-def _atr_run(x, form, with_state=True, with_idx=True, with_mask=True):
-    e = eng()
-    st = ST[form]
-    Rn, H = x["p"].shape
-    n_prev = x["h_prev"].shape[0]
-    # (R = 5: a row stride that is no multiple of 4 floats -- the scalar loads of the state; else the 16-byte ones)
-    hp = G(n_prev, H, H + (13 if Rn == 5 else 12), 4, F32, _t(x["h_prev"]))
-    U = G(H, H, H + 8, 0, st, _t(x["U"]))
-    b = G(1, H, dtype=F32, prefill=_t(x["b"]))
-    p = G(Rn, H, 2 * H + 8, 8, st, _t(x["p"]))
-    m = G(Rn, 1, 3, 1, F32, _t(x["mask"]))
-    idx = torch.as_tensor(x["idx"].astype(np.int32)).cuda()
-    out, cp = G(Rn, H, 3 * H + 4, 4, F32), G(Rn, H, H + 16, 8, st)
-    e.rnn_atr_step(hp.mat if with_state else None, U.mat, b.t[P.LEAD:P.LEAD + H], p.mat, out.mat, cp.mat,
-                   idx=idx if (with_idx and with_state) else None, mask=m.mat if with_mask else None)
-    torch.cuda.synchronize()
-    for buf, what in ((hp, "h_prev"), (U, "U"), (b, "b"), (p, "p"), (m, "mask")):
-        buf.check_intact("atr_step " + what)
-    out.check_guard("atr_step state")
-    cp.check_guard("atr_step copy")
-    return out.value().double().numpy(), cp.value().double().numpy()
-
-
 ATR_SHAPES = [("bf16", 5, 72), ("bf16", 33, 128), ("bf16", 70, 40), ("fp32", 5, 20), ("fp32", 33, 128)]
 
 

@@ -14,7 +14,10 @@
 // the loss would compound over the sequence.  In the bf16 form only the MFMA operand is a rounded copy of h_prev;
 // f h_prev and the carry use the fp32 value.  out_copy is the state in the storage type: the operand of the next GEMM.
 //
-// Grid of zk_rnn_atr_step: one workgroup (4 waves) per 16 output columns and 64 rows, wave w owns rows 16 w .. 16 w + 15.
+// The dense cell launches -- the ATR step, the two GRU launches, ff + residual -- are four epilogues (AtrCell, GruGatesCell,
+// GruOutCell, FfCell, each written once for both storage types) over ONE tile driver per form (rnn_bf16_tile, rnn_f32_tile);
+// the kernels are k_rnn_atr_step<T>, k_rnn_gru_gates<T>, k_rnn_gru_out<T> and k_rnn_ff_residual<T>, T = bf16_t or float.
+// bf16 driver: one workgroup (4 waves) per 16 output columns and 64 rows, wave w owns rows 16 w .. 16 w + 15.
 // Why: R is 32 .. 128 rows and H about 1000, so one step is ~0.25 GFLOP against 2 MB of U -- the launch is a latency
 // chain, not a throughput problem.  16-column tiles give H / 16 = 63 workgroups for H = 1000 (two for R = 128), each of
 // which streams a 32-row-stride slab of U ONCE (H x 16 bf16 = 32 KB) into a transposed LDS image [16][K + 8] so that the
@@ -23,8 +26,8 @@
 // its own 16 rows once.  Edge tiles in rows, columns and K are zero-filled.  v_mfma_f32_16x16x32_bf16 fragment maps
 // (zk_attn_dev.h frag / mfma16): A lane l = row l & 15, k = 8 (l >> 4) + j; B the same with the column; D column l & 15,
 // row 4 (l >> 4) + reg.
-// Grid of zk_f32_rnn_atr_step: one workgroup per 64 columns and 32 rows; lane = column (coalesced rows of U), wave w owns
-// rows 8 w .. 8 w + 7 whose h_prev chunk [32][64] sits in LDS (broadcast reads); k ascending, fused multiply-adds.
+// fp32 driver: one workgroup per 64 columns and 32 rows; lane = column (coalesced rows of U), wave w owns rows 8 w .. 8 w + 7
+// whose chunk [32][64] of the A operand sits in LDS (broadcast reads); k ascending, fused multiply-adds.
 //
 // Additive attention of one decode step (func.py:107-161; one head, rnns/rnn.py:131-136):
 //     logit_j = v . tanh(qa + pm_j) + (1 - mask_j) * -inf_const        a = softmax_j        c = sum_j a_j mem_j
@@ -45,148 +48,27 @@ typedef float rf32x4_t __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float rnn_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
-// ---------------------------------------------------------------- ATR step, bf16 form
-#define ATR_BN 16          // output columns per workgroup
-#define ATR_BM 64          // rows per workgroup (16 per wave)
+// an element of the storage type (bf16_t or float) as fp32
+__device__ __forceinline__ float rnn_load(const bf16_t* p, size_t i) { return bf2f(p[i]); }
+__device__ __forceinline__ float rnn_load(const float* p, size_t i) { return p[i]; }
+__device__ __forceinline__ void rnn_store(bf16_t* p, size_t i, float v) { p[i] = f2bf(v); }
+__device__ __forceinline__ void rnn_store(float* p, size_t i, float v) { p[i] = v; }
 
-__global__ void __launch_bounds__(256) k_rnn_atr_step(const float* __restrict__ h_prev, int ldh, int n_prev,
-                                                      const int* __restrict__ idx, const bf16_t* __restrict__ U, int ldu,
-                                                      const float* __restrict__ b, const bf16_t* __restrict__ p, int ldp,
-                                                      const float* __restrict__ mask, int ldm, float* __restrict__ out,
-                                                      int ldo, bf16_t* __restrict__ out_copy, int ldc, int R, int H,
-                                                      int vec_a) {
-  extern __shared__ __align__(16) unsigned char atr_lds[];
-  bf16_t* sU = reinterpret_cast<bf16_t*>(atr_lds);            // [ATR_BN][KS]: U[:, n0 .. n0 + 15] transposed
-  const int Kr = (H + 31) / 32 * 32, KS = Kr + 8;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
-  rf32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-  if (h_prev != nullptr) {
-    for (int k = threadIdx.x; k < Kr; k += 256) {
-      uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = lo;
-      if (k < H) {                                             // (H % 8 == 0: a group of 8 columns is inside or outside)
-        const bf16_t* up = U + (size_t)k * ldu + n0;
-        if (n0 < H) lo = *reinterpret_cast<const uint4*>(up);
-        if (n0 + 8 < H) hi = *reinterpret_cast<const uint4*>(up + 8);
-      }
-      const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        sU[(2 * c) * KS + k] = (bf16_t)(w[c] & 0xffffu);
-        sU[(2 * c + 1) * KS + k] = (bf16_t)(w[c] >> 16);
-      }
-    }
-    __syncthreads();
-    if (r0 < R) {                                              // wave-uniform: the MFMA runs with all 64 lanes
-      const int row = r0 + (lane & 15);
-      const bool valid = row < R;
-      int src = valid ? (idx != nullptr ? idx[row] : row) : 0;
-      src = min(max(src, 0), n_prev - 1);
-      const float* hp = h_prev + (size_t)src * ldh;
-      const bf16_t* bt = sU + (lane & 15) * KS + (lane >> 4) * 8;
-      for (int kk = 0; kk < Kr; kk += 32) {
-        const int k = kk + (lane >> 4) * 8;
-        float a[8];
-        if (vec_a) {
-          float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
-          if (valid && k < H) {
-            x0 = *reinterpret_cast<const float4*>(hp + k);
-            x1 = *reinterpret_cast<const float4*>(hp + k + 4);
-          }
-          a[0] = x0.x; a[1] = x0.y; a[2] = x0.z; a[3] = x0.w; a[4] = x1.x; a[5] = x1.y; a[6] = x1.z; a[7] = x1.w;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) a[e] = (valid && k + e < H) ? hp[k + e] : 0.f;
-        }
-        const uint4 af = pack8(a);
-        const uint4 bf = *reinterpret_cast<const uint4*>(bt + kk);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(rbf16x8_t, af), __builtin_bit_cast(rbf16x8_t, bf),
-                                                      acc, 0, 0, 0);
-      }
-    }
+// the state operand of a cell launch: fp32 rows, gathered by idx (NULL: row r is row r); h_prev NULL: the zero state
+struct RnnState {
+  const float* h_prev;
+  int ldh, n_prev;
+  const int* idx;
+  __device__ __forceinline__ int src(int row) const { return min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1); }
+  __device__ __forceinline__ float at(int row, int col) const {
+    return h_prev != nullptr ? h_prev[(size_t)src(row) * ldh + col] : 0.f;
   }
-  const int col = n0 + (lane & 15);
-  if (col >= H) return;
-  const float bias = b[col];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = r0 + (lane >> 4) * 4 + r;
-    if (row >= R) continue;
-    float hv = 0.f;
-    if (h_prev != nullptr) {
-      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
-      hv = h_prev[(size_t)src * ldh + col];
-    }
-    const float q = acc[r] + bias;
-    const float pv = bf2f(p[(size_t)row * ldp + col]);
-    float h = rnn_sigmoid(pv + q) * pv + rnn_sigmoid(pv - q) * hv;
-    if (mask != nullptr) {
-      const float m = mask[(size_t)row * ldm];
-      h = m * h + (1.f - m) * hv;
-    }
-    out[(size_t)row * ldo + col] = h;
-    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = f2bf(h);
+  // the row a lane feeds the product; a lane past R (not valid) points at row 0 and loads nothing
+  __device__ __forceinline__ const float* a_row(int row, bool valid) const {
+    const int s = min(max(valid ? (idx != nullptr ? idx[row] : row) : 0, 0), n_prev - 1);
+    return h_prev + (size_t)s * ldh;
   }
-}
-
-// ---------------------------------------------------------------- ATR step, fp32 form
-#define ATRF_BN 64
-#define ATRF_BM 32
-
-__global__ void __launch_bounds__(256) k_f32_rnn_atr_step(const float* __restrict__ h_prev, int ldh, int n_prev,
-                                                          const int* __restrict__ idx, const float* __restrict__ U, int ldu,
-                                                          const float* __restrict__ b, const float* __restrict__ p, int ldp,
-                                                          const float* __restrict__ mask, int ldm, float* __restrict__ out,
-                                                          int ldo, float* __restrict__ out_copy, int ldc, int R, int H) {
-  __shared__ float sh[ATRF_BM][64];                            // h_prev[rows of the block][k chunk]
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int col = blockIdx.x * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (h_prev != nullptr) {
-    const int lr = threadIdx.x >> 3, lk = (threadIdx.x & 7) * 8;       // this thread stages row lr, 8 values from lk
-    const int grow = r0 + lr;
-    int src = grow < R ? (idx != nullptr ? idx[grow] : grow) : 0;
-    src = min(max(src, 0), n_prev - 1);
-    const float* hp = h_prev + (size_t)src * ldh;
-    for (int k0 = 0; k0 < H; k0 += 64) {
-      __syncthreads();
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sh[lr][lk + e] = (grow < R && k0 + lk + e < H) ? hp[k0 + lk + e] : 0.f;
-      __syncthreads();
-      const int kn = min(64, H - k0);
-      if (col < H) {
-        for (int kk = 0; kk < kn; ++kk) {
-          const float u = U[(size_t)(k0 + kk) * ldu + col];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[j] = fmaf(sh[wave * 8 + j][kk], u, acc[j]);
-        }
-      }
-    }
-  }
-  if (col >= H) return;
-  const float bias = b[col];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int row = r0 + wave * 8 + j;
-    if (row >= R) continue;
-    float hv = 0.f;
-    if (h_prev != nullptr) {
-      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
-      hv = h_prev[(size_t)src * ldh + col];
-    }
-    const float q = acc[j] + bias;
-    const float pv = p[(size_t)row * ldp + col];
-    float h = rnn_sigmoid(pv + q) * pv + rnn_sigmoid(pv - q) * hv;
-    if (mask != nullptr) {
-      const float m = mask[(size_t)row * ldm];
-      h = m * h + (1.f - m) * hv;
-    }
-    out[(size_t)row * ldo + col] = h;
-    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = h;
-  }
-}
+};
 
 // true when some row [a + r lda, + w) (r < ra) shares an element with some row [b + s ldb, + w) (s < rb)
 static bool rnn_rows_overlap(const float* a, long lda, long ra, const float* b, long ldb, long rb, long w) {
@@ -210,29 +92,23 @@ static bool rnn_rows_overlap(const float* a, long lda, long ra, const float* b, 
   return false;
 }
 
-#define ATR_CHECK_COMMON(NAME)                                                                                              \
-  ZK_CHECK_ARG(U != nullptr && b != nullptr && p != nullptr && out != nullptr, NAME ": U, b, p and out are required");      \
-  ZK_CHECK_ARG(R >= 0 && H >= 1, NAME ": bad shape (R=%d H=%d)", R, H);                                                     \
-  ZK_CHECK_ARG(ldu >= H && ldp >= H && ldo >= H && (out_copy == nullptr || ldc >= H) && (h_prev == nullptr || ldh >= H),    \
-               NAME ": a leading dimension is smaller than H=%d (ldh=%d ldu=%d ldp=%d ldo=%d ldc=%d)", H, ldh, ldu, ldp,    \
-               ldo, ldc);                                                                                                   \
-  ZK_CHECK_ARG(h_prev == nullptr || (idx != nullptr ? n_prev >= 1 : n_prev >= R),                                           \
-               NAME ": h_prev has n_prev=%d rows (R=%d without an index, at least 1 with one)", n_prev, R);                 \
-  ZK_CHECK_ARG(mask == nullptr || ldm >= 1, NAME ": the mask stride must be at least 1 (ldm=%d)", ldm);                     \
-  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, h_prev, ldh, n_prev, H),                                                      \
-               NAME ": out overlaps h_prev (every column tile reads whole rows of h_prev while others write out)")
-
-// ---------------------------------------------------------------- GRU step (rnns/gru.py:32-57), two launches
-//     [z | r] = sigmoid(xg + h Ug + bg)        rh = r (.) h                               (zk_rnn_gru_gates)
-//     c = tanh(xh + rh Uh + bh)                o = z h + (1 - z) c      out = m o + (1 - m) h   (zk_rnn_gru_out)
-// The candidate product contracts r (.) h over ALL of K and r needs the gate product of every column, so the two products
-// cannot share a launch without an exchange between workgroups: the launch boundary is that exchange.  Tiling as the ATR
-// step.  A gates workgroup owns 16 columns j AND the 16 columns H + j of Ug (two accumulators per wave), so z_j and r_j of
-// an element meet in one lane and rh needs no second pass; its LDS image is [32][K + 8] bf16: 66 KB for H = 1000, and
-// GRU_MAX_H = 2048 (129 KB of the 160 KB of a CU) is the largest H of the bf16 forms.  rh is the MFMA operand of the second
-// launch: formed from the fp32 state and rounded ONCE to the storage type.  z stays fp32; z h and the carry read the fp32
-// state in the second launch, so a carried row is the gathered state bit for bit.  The fp32 forms tile as
-// zk_f32_rnn_atr_step (lane = column, k ascending) and take any H.
+// ---------------------------------------------------------------- the two tile drivers of the dense cells
+// A dense cell launch is out = epilogue(A W) for R rows: the ATR step, the two GRU launches and ff + residual differ in the
+// A operand (the gathered fp32 state, or rows of the storage type), in the number NT of 16- or 64-column blocks of W a
+// workgroup takes (2 for the GRU gates: z and r; else 1) and in the epilogue.  Each storage form has ONE driver; a cell is a
+// struct that names its A rows and W and states its arithmetic once, for both forms (`Cell<T>`, T the storage type):
+//     bool product()                 false: the zero state, no product (the accumulators stay 0)
+//     a_row(row, valid)              the A row of `row`; STATE_A: it is the fp32 state
+//     W, ldw, b                      block t of the product is A W[:, t N .. t N + N - 1] + b[t N .. t N + N - 1]
+//     operator()(t, row, col, q)     the epilogue of one element q of block t
+// bf16 form (rnn_bf16_tile): 16 columns x 64 rows per workgroup, the slabs in the LDS image [NT][16][K + 8] (rnn_stage_slab),
+// v_mfma_f32_16x16x32_bf16 (rnn_product); the largest image is 132 KB (ATR H = 4096, ff K = 4096; GRU gates H = GRU_MAX_H).
+// fp32 form (rnn_f32_tile): 64 columns x 32 rows, lane = column, eight rows per wave (rnn_f32_product); the grid has NT x
+// ceil(N / 64) column tiles, block t after block t - 1.
+#define ATR_BN 16          // bf16 form: output columns per workgroup
+#define ATR_BM 64          //            rows per workgroup (16 per wave)
+#define ATRF_BN 64         // fp32 form: output columns per workgroup
+#define ATRF_BM 32         //            rows per workgroup (8 per wave)
 #define GRU_MAX_H 2048
 
 // sT [16][KS] = U[0 .. K - 1][n0 .. n0 + 15] transposed; the columns n0 + c >= N and the rows k >= K are zero
@@ -297,90 +173,37 @@ __device__ __forceinline__ void rnn_product(rf32x4_t (&acc)[NT], const bf16_t* s
   }
 }
 
-__global__ void __launch_bounds__(256) k_rnn_gru_gates(const float* __restrict__ h_prev, int ldh, int n_prev,
-                                                       const int* __restrict__ idx, const bf16_t* __restrict__ Ug, int ldu,
-                                                       const float* __restrict__ bg, const bf16_t* __restrict__ xg, int ldx,
-                                                       float* __restrict__ z, int ldz, bf16_t* __restrict__ rh, int ldr, int R,
-                                                       int H, int vec_a) {
-  extern __shared__ __align__(16) unsigned char gru_lds[];
-  bf16_t* sU = reinterpret_cast<bf16_t*>(gru_lds);            // [2][ATR_BN][KS]: the z columns, then the r columns
-  const int Kr = (H + 31) / 32 * 32, KS = Kr + 8;
+template <int NT, typename Cell>
+__device__ __forceinline__ void rnn_bf16_tile(const Cell& cell, int R, int K, int N, int vec_a) {
+  extern __shared__ __align__(16) unsigned char rnn_lds[];
+  bf16_t* sW = reinterpret_cast<bf16_t*>(rnn_lds);            // [NT][ATR_BN][KS]: W[:, t N + n0 .. + 15] transposed
+  const int Kr = (K + 31) / 32 * 32, KS = Kr + 8;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
-  rf32x4_t acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  if (h_prev != nullptr) {
-    rnn_stage_slab(sU, KS, Ug, ldu, n0, H, H, Kr);
-    rnn_stage_slab(sU + (size_t)ATR_BN * KS, KS, Ug + H, ldu, n0, H, H, Kr);
+  rf32x4_t acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = rf32x4_t{0.f, 0.f, 0.f, 0.f};
+  if (cell.product()) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) rnn_stage_slab(sW + (size_t)t * ATR_BN * KS, KS, cell.W + t * N, cell.ldw, n0, K, N, Kr);
     __syncthreads();
     if (r0 < R) {                                              // wave-uniform: the MFMA runs with all 64 lanes
       const int row = r0 + (lane & 15);
       const bool valid = row < R;
-      int src = valid ? (idx != nullptr ? idx[row] : row) : 0;
-      src = min(max(src, 0), n_prev - 1);
-      rnn_product<2, true>(acc, sU, KS, Kr, H, h_prev + (size_t)src * ldh, valid, vec_a, lane);
+      rnn_product<NT, Cell::STATE_A>(acc, sW, KS, Kr, K, cell.a_row(row, valid), valid, vec_a, lane);
     }
   }
   const int col = n0 + (lane & 15);
-  if (col >= H) return;
-  const float bz = bg[col], br = bg[H + col];
+  if (col >= N) return;
+  float bias[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) bias[t] = cell.b[t * N + col];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = r0 + (lane >> 4) * 4 + r;
     if (row >= R) continue;
-    float hv = 0.f;
-    if (h_prev != nullptr) {
-      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
-      hv = h_prev[(size_t)src * ldh + col];
-    }
-    const bf16_t* xr = xg + (size_t)row * ldx;
-    z[(size_t)row * ldz + col] = rnn_sigmoid(bf2f(xr[col]) + (acc[0][r] + bz));
-    rh[(size_t)row * ldr + col] = f2bf(rnn_sigmoid(bf2f(xr[H + col]) + (acc[1][r] + br)) * hv);
-  }
-}
-
-__global__ void __launch_bounds__(256) k_rnn_gru_out(const bf16_t* __restrict__ rh, int ldr, const bf16_t* __restrict__ Uh,
-                                                     int ldu, const float* __restrict__ bh, const bf16_t* __restrict__ xh,
-                                                     int ldx, const float* __restrict__ z, int ldz,
-                                                     const float* __restrict__ h_prev, int ldh, int n_prev,
-                                                     const int* __restrict__ idx, const float* __restrict__ mask, int ldm,
-                                                     float* __restrict__ out, int ldo, bf16_t* __restrict__ out_copy, int ldc,
-                                                     int R, int H, int vec_a) {
-  extern __shared__ __align__(16) unsigned char gru_lds[];
-  bf16_t* sU = reinterpret_cast<bf16_t*>(gru_lds);            // [ATR_BN][KS]
-  const int Kr = (H + 31) / 32 * 32, KS = Kr + 8;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
-  rf32x4_t acc[1] = {{0.f, 0.f, 0.f, 0.f}};
-  if (h_prev != nullptr) {                                     // (the zero state: rh = 0, no product)
-    rnn_stage_slab(sU, KS, Uh, ldu, n0, H, H, Kr);
-    __syncthreads();
-    if (r0 < R) {
-      const int row = r0 + (lane & 15);
-      const bool valid = row < R;
-      rnn_product<1, false>(acc, sU, KS, Kr, H, rh + (size_t)(valid ? row : 0) * ldr, valid, vec_a, lane);
-    }
-  }
-  const int col = n0 + (lane & 15);
-  if (col >= H) return;
-  const float bias = bh[col];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = r0 + (lane >> 4) * 4 + r;
-    if (row >= R) continue;
-    float hv = 0.f;
-    if (h_prev != nullptr) {
-      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
-      hv = h_prev[(size_t)src * ldh + col];
-    }
-    const float c = tanhf(bf2f(xh[(size_t)row * ldx + col]) + (acc[0][r] + bias));
-    const float zv = z[(size_t)row * ldz + col];
-    float h = zv * hv + (1.f - zv) * c;
-    if (mask != nullptr) {
-      const float m = mask[(size_t)row * ldm];
-      h = m * h + (1.f - m) * hv;
-    }
-    out[(size_t)row * ldo + col] = h;
-    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = f2bf(h);
+    for (int t = NT - 1; t >= 0; --t) cell(t, row, col, acc[t][r] + bias[t]);       // (the GRU gates: the piece that gathers first)
   }
 }
 
@@ -419,120 +242,202 @@ __device__ __forceinline__ void rnn_f32_product(float (&acc)[8], float (*sh)[64]
   }
 }
 
-// (the fp32 gates launch needs no pairing of z_j with r_j: rh = r h takes r alone.  So its grid is 2 x H / 64 column tiles -- the
-// first half forms z, the second rh -- and twice as many CUs pull Ug as a paired tile would give)
-__global__ void __launch_bounds__(256) k_f32_rnn_gru_gates(const float* __restrict__ h_prev, int ldh, int n_prev,
-                                                           const int* __restrict__ idx, const float* __restrict__ Ug, int ldu,
-                                                           const float* __restrict__ bg, const float* __restrict__ xg, int ldx,
-                                                           float* __restrict__ z, int ldz, float* __restrict__ rh, int ldr,
-                                                           int R, int H) {
-  __shared__ __align__(16) float sh[ATRF_BM][64];
+template <int NT, typename Cell>
+__device__ __forceinline__ void rnn_f32_tile(const Cell& cell, int R, int K, int N) {
+  static_assert(NT == 1 || NT == 2, "one block of W, or the two of the GRU gates");
+  __shared__ __align__(16) float sh[ATRF_BM][64];              // A[rows of the block][k chunk]
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int nct = gridDim.x >> 1;
-  const bool second = (int)blockIdx.x >= nct;                  // block-uniform: this tile forms r (and rh), not z
-  const int col = ((int)blockIdx.x - (second ? nct : 0)) * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
-  const int gcol = (second ? H : 0) + col;                     // the column of Ug, bg and xg
+  const int nct = gridDim.x / NT;
+  const int t = NT == 2 && (int)blockIdx.x >= nct ? 1 : 0;     // block-uniform: the block of W this tile belongs to
+  const int col = ((int)blockIdx.x - t * nct) * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
   float acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (h_prev != nullptr) {
-    const int grow = r0 + (threadIdx.x >> 3);
-    int src = grow < R ? (idx != nullptr ? idx[grow] : grow) : 0;
-    src = min(max(src, 0), n_prev - 1);
-    rnn_f32_product(acc, sh, grow < R ? h_prev + (size_t)src * ldh : nullptr, Ug + (second ? H : 0), ldu, H, H, col, wave);
+  if (cell.product()) {
+    const int grow = r0 + (threadIdx.x >> 3);                  // the row this thread stages
+    rnn_f32_product(acc, sh, grow < R ? cell.a_row(grow, true) : nullptr, cell.W + t * N, cell.ldw, K, N, col, wave);
   }
-  if (col >= H) return;
-  const float bias = bg[gcol];
+  if (col >= N) return;
+  const float bias = cell.b[t * N + col];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int row = r0 + wave * 8 + j;
     if (row >= R) continue;
-    const float g = rnn_sigmoid(xg[(size_t)row * ldx + gcol] + (acc[j] + bias));
-    if (!second) {
-      z[(size_t)row * ldz + col] = g;
-      continue;
-    }
-    float hv = 0.f;
-    if (h_prev != nullptr) {
-      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
-      hv = h_prev[(size_t)src * ldh + col];
-    }
-    rh[(size_t)row * ldr + col] = g * hv;
+    cell(t, row, col, acc[j] + bias);
   }
 }
 
-__global__ void __launch_bounds__(256) k_f32_rnn_gru_out(const float* __restrict__ rh, int ldr, const float* __restrict__ Uh,
-                                                         int ldu, const float* __restrict__ bh, const float* __restrict__ xh,
-                                                         int ldx, const float* __restrict__ z, int ldz,
-                                                         const float* __restrict__ h_prev, int ldh, int n_prev,
-                                                         const int* __restrict__ idx, const float* __restrict__ mask, int ldm,
-                                                         float* __restrict__ out, int ldo, float* __restrict__ out_copy, int ldc,
-                                                         int R, int H) {
-  __shared__ __align__(16) float sh[ATRF_BM][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int col = blockIdx.x * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (h_prev != nullptr) {
-    const int grow = r0 + (threadIdx.x >> 3);
-    rnn_f32_product(acc, sh, grow < R ? rh + (size_t)grow * ldr : nullptr, Uh, ldu, H, H, col, wave);
-  }
-  if (col >= H) return;
-  const float bias = bh[col];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int row = r0 + wave * 8 + j;
-    if (row >= R) continue;
-    float hv = 0.f;
-    if (h_prev != nullptr) {
-      const int src = min(max(idx != nullptr ? idx[row] : row, 0), n_prev - 1);
-      hv = h_prev[(size_t)src * ldh + col];
-    }
-    const float c = tanhf(xh[(size_t)row * ldx + col] + (acc[j] + bias));
-    const float zv = z[(size_t)row * ldz + col];
-    float h = zv * hv + (1.f - zv) * c;
+template <int NT, typename Cell>
+__device__ __forceinline__ void rnn_tile(const Cell& cell, int R, int K, int N, int vec_a) {
+  if constexpr (std::is_same<typename Cell::st_t, float>::value) rnn_f32_tile<NT>(cell, R, K, N);
+  else rnn_bf16_tile<NT>(cell, R, K, N, vec_a);
+}
+
+// ---------------------------------------------------------------- the four cells
+// The kernels keep plain `__restrict__` parameters (the compiler's alias information hangs on them, not on struct members)
+// and only fill their cell in.  out / out_copy with the mask carry of rnns/rnn.py:41-49, shared by the cells that end a step:
+template <typename T>
+struct RnnOut {
+  const float* mask;
+  int ldm;
+  float* out;
+  int ldo;
+  T* out_copy;
+  int ldc;
+  __device__ __forceinline__ void put(int row, int col, float h, float hv) const {
     if (mask != nullptr) {
       const float m = mask[(size_t)row * ldm];
       h = m * h + (1.f - m) * hv;
     }
     out[(size_t)row * ldo + col] = h;
-    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = h;
+    if (out_copy != nullptr) rnn_store(out_copy, (size_t)row * ldc + col, h);
   }
+};
+
+// ATR (head of the file): q = h U + b, h' = sigmoid(p + q) p + sigmoid(p - q) h
+template <typename T>
+struct AtrCell {
+  typedef T st_t;
+  static constexpr bool STATE_A = true;
+  RnnState s;
+  const T* W;
+  int ldw;
+  const float* b;
+  const T* p;
+  int ldp;
+  RnnOut<T> o;
+  __device__ __forceinline__ bool product() const { return s.h_prev != nullptr; }
+  __device__ __forceinline__ const float* a_row(int row, bool valid) const { return s.a_row(row, valid); }
+  __device__ __forceinline__ void operator()(int, int row, int col, float q) const {
+    const float hv = s.at(row, col);
+    const float pv = rnn_load(p, (size_t)row * ldp + col);
+    o.put(row, col, rnn_sigmoid(pv + q) * pv + rnn_sigmoid(pv - q) * hv, hv);
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_rnn_atr_step(const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                      const int* __restrict__ idx, const T* __restrict__ U, int ldu,
+                                                      const float* __restrict__ b, const T* __restrict__ p, int ldp,
+                                                      const float* __restrict__ mask, int ldm, float* __restrict__ out, int ldo,
+                                                      T* __restrict__ out_copy, int ldc, int R, int H, int vec_a) {
+  rnn_tile<1>(AtrCell<T>{{h_prev, ldh, n_prev, idx}, U, ldu, b, p, ldp, {mask, ldm, out, ldo, out_copy, ldc}}, R, H, H, vec_a);
 }
 
-#define GRU_CHECK_STATE(NAME)                                                                                               \
-  ZK_CHECK_ARG(R >= 0 && H >= 1, NAME ": bad shape (R=%d H=%d)", R, H);                                                     \
-  ZK_CHECK_ARG(h_prev == nullptr || ldh >= H, NAME ": ldh=%d is smaller than H=%d", ldh, H);                                \
-  ZK_CHECK_ARG(h_prev == nullptr || (idx != nullptr ? n_prev >= 1 : n_prev >= R),                                           \
-               NAME ": h_prev has n_prev=%d rows (R=%d without an index, at least 1 with one)", n_prev, R)
+// GRU step (rnns/gru.py:32-57), two launches
+//     [z | r] = sigmoid(xg + h Ug + bg)        rh = r (.) h                               (zk_rnn_gru_gates)
+//     c = tanh(xh + rh Uh + bh)                o = z h + (1 - z) c      out = m o + (1 - m) h   (zk_rnn_gru_out)
+// The candidate product contracts r (.) h over ALL of K and r needs the gate product of every column, so the two products
+// cannot share a launch without an exchange between workgroups: the launch boundary is that exchange.  The gates take the
+// two blocks of Ug (NT = 2): block 0 forms z, block 1 r and rh.  In the bf16 form a workgroup owns 16 columns j AND the 16
+// columns H + j (two accumulators per wave; LDS image [32][K + 8] bf16: 66 KB for H = 1000, and GRU_MAX_H = 2048, 129 KB of
+// the 160 KB of a CU, is the largest H of the bf16 forms); in the fp32 form the grid is 2 x H / 64 column tiles -- the first
+// half forms z, the second rh -- so twice as many CUs pull Ug as a paired tile would give.  rh is the MFMA operand of the
+// second launch: formed from the fp32 state and rounded ONCE to the storage type.  z stays fp32; z h and the carry read the
+// fp32 state in the second launch, so a carried row is the gathered state bit for bit.  The fp32 forms take any H.
+template <typename T>
+struct GruGatesCell {
+  typedef T st_t;
+  static constexpr bool STATE_A = true;
+  RnnState s;
+  const T* W;
+  int ldw;
+  const float* b;
+  const T* xg;
+  int ldx;
+  float* z;
+  int ldz;
+  T* rh;
+  int ldr, H;
+  __device__ __forceinline__ bool product() const { return s.h_prev != nullptr; }
+  __device__ __forceinline__ const float* a_row(int row, bool valid) const { return s.a_row(row, valid); }
+  __device__ __forceinline__ void operator()(int t, int row, int col, float q) const {
+    const float hv = t == 0 ? 0.f : s.at(row, col);             // (first: the gather is two dependent loads)
+    const float g = rnn_sigmoid(rnn_load(xg, (size_t)row * ldx + t * H + col) + q);
+    if (t == 0) z[(size_t)row * ldz + col] = g;
+    else rnn_store(rh, (size_t)row * ldr + col, g * hv);
+  }
+};
 
-#define GRU_CHECK_GATES(NAME)                                                                                               \
-  ZK_CHECK_ARG(Ug != nullptr && bg != nullptr && xg != nullptr && z != nullptr && rh != nullptr,                            \
-               NAME ": Ug, bg, xg, z and rh are required");                                                                 \
-  GRU_CHECK_STATE(NAME);                                                                                                    \
-  ZK_CHECK_ARG(ldu >= 2 * H && ldx >= 2 * H && ldz >= H && ldr >= H,                                                        \
-               NAME ": a leading dimension is too small for H=%d (ldu=%d and ldx=%d hold 2 H columns, ldz=%d ldr=%d)", H,   \
-               ldu, ldx, ldz, ldr);                                                                                         \
-  ZK_CHECK_ARG(!rnn_rows_overlap(z, ldz, R, h_prev, ldh, n_prev, H),                                                        \
-               NAME ": z overlaps h_prev (every column tile reads whole rows of h_prev while others write z)")
+template <typename T>
+__global__ void __launch_bounds__(256) k_rnn_gru_gates(const float* __restrict__ h_prev, int ldh, int n_prev,
+                                                       const int* __restrict__ idx, const T* __restrict__ Ug, int ldu,
+                                                       const float* __restrict__ bg, const T* __restrict__ xg, int ldx,
+                                                       float* __restrict__ z, int ldz, T* __restrict__ rh, int ldr, int R, int H,
+                                                       int vec_a) {
+  rnn_tile<2>(GruGatesCell<T>{{h_prev, ldh, n_prev, idx}, Ug, ldu, bg, xg, ldx, z, ldz, rh, ldr, H}, R, H, H, vec_a);
+}
 
-#define GRU_CHECK_OUT(NAME)                                                                                                 \
-  ZK_CHECK_ARG(rh != nullptr && Uh != nullptr && bh != nullptr && xh != nullptr && z != nullptr && out != nullptr,          \
-               NAME ": rh, Uh, bh, xh, z and out are required");                                                            \
-  GRU_CHECK_STATE(NAME);                                                                                                    \
-  ZK_CHECK_ARG(ldr >= H && ldu >= H && ldx >= H && ldz >= H && ldo >= H && (out_copy == nullptr || ldc >= H),               \
-               NAME ": a leading dimension is smaller than H=%d (ldr=%d ldu=%d ldx=%d ldz=%d ldo=%d ldc=%d)", H, ldr, ldu,  \
-               ldx, ldz, ldo, ldc);                                                                                         \
-  ZK_CHECK_ARG(mask == nullptr || ldm >= 1, NAME ": the mask stride must be at least 1 (ldm=%d)", ldm);                     \
-  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, h_prev, ldh, n_prev, H),                                                      \
-               NAME ": out overlaps h_prev (a row of h_prev may be gathered by several rows while others write out)");      \
-  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, z, ldz, R, H), NAME ": out overlaps z")
+template <typename T>
+struct GruOutCell {
+  typedef T st_t;
+  static constexpr bool STATE_A = false;
+  RnnState s;
+  const T* rh;
+  int ldr;
+  const T* W;
+  int ldw;
+  const float* b;
+  const T* xh;
+  int ldx;
+  const float* z;
+  int ldz;
+  RnnOut<T> o;
+  __device__ __forceinline__ bool product() const { return s.h_prev != nullptr; }         // (the zero state: rh = 0)
+  __device__ __forceinline__ const T* a_row(int row, bool valid) const { return rh + (size_t)(valid ? row : 0) * ldr; }
+  __device__ __forceinline__ void operator()(int, int row, int col, float q) const {
+    const float hv = s.at(row, col);
+    const float c = tanhf(rnn_load(xh, (size_t)row * ldx + col) + q);
+    const float zv = z[(size_t)row * ldz + col];
+    o.put(row, col, zv * hv + (1.f - zv) * c, hv);
+  }
+};
 
-#define GRU_CHECK_BF16(NAME, U, F32NAME)                                                                                    \
-  ZK_CHECK_ARG(H % 8 == 0 && H <= GRU_MAX_H && ldu % 8 == 0 && (((uintptr_t)U) & 15) == 0,                                  \
-               NAME ": the bf16 form needs H a multiple of 8 and at most %d (its LDS image of the recurrent matrix) and "   \
-               "16-byte aligned rows of the matrix (H=%d ldu=%d); " F32NAME " takes any H", GRU_MAX_H, H, ldu)
+template <typename T>
+__global__ void __launch_bounds__(256) k_rnn_gru_out(const T* __restrict__ rh, int ldr, const T* __restrict__ Uh, int ldu,
+                                                     const float* __restrict__ bh, const T* __restrict__ xh, int ldx,
+                                                     const float* __restrict__ z, int ldz, const float* __restrict__ h_prev,
+                                                     int ldh, int n_prev, const int* __restrict__ idx,
+                                                     const float* __restrict__ mask, int ldm, float* __restrict__ out, int ldo,
+                                                     T* __restrict__ out_copy, int ldc, int R, int H, int vec_a) {
+  rnn_tile<1>(GruOutCell<T>{{h_prev, ldh, n_prev, idx}, rh, ldr, Uh, ldu, bh, xh, ldx, z, ldz,
+                            {mask, ldm, out, ldo, out_copy, ldc}}, R, H, H, vec_a);
+}
+
+// ff + residual of a deepnmt layer
+// models/deepnmt.py:73-79 (encoder) and 166-172 (decoder): y = linear(outputs, embed_size, scope="ff"); x = x + y, with
+// layer_norm off -- so NOTHING re-normalises x from the embedding to the last layer.  One launch:
+//     out[r, :] = x[r, :] + (a[r, :] W + b)          out_copy = the same in the storage type (the next product's operand)
+// The stream x / out is fp32 in BOTH forms for the reason the recurrent state is: a bf16 stream would drop every layer's
+// update below half an ulp of x, and the loss would add up over the layers (DESIGN.md 6n; 6j has the same argument for
+// transformer_fixup).  In the bf16 form only the MFMA operands a and W are bf16.  out may BE x (same address, same stride):
+// an element is read and written by the one lane that owns it, and no lane reads another's.  No workgroup waits for another.
+template <typename T>
+struct FfCell {
+  typedef T st_t;
+  static constexpr bool STATE_A = false;
+  const T* a;
+  int lda;
+  const T* W;
+  int ldw;
+  const float* b;
+  const float* x;
+  int ldx;
+  RnnOut<T> o;
+  __device__ __forceinline__ bool product() const { return true; }
+  __device__ __forceinline__ const T* a_row(int row, bool valid) const { return a + (size_t)(valid ? row : 0) * lda; }
+  __device__ __forceinline__ void operator()(int, int row, int col, float q) const {
+    o.put(row, col, x[(size_t)row * ldx + col] + q, 0.f);
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_rnn_ff_residual(const T* __restrict__ a, int lda, const T* __restrict__ W, int ldw,
+                                                         const float* __restrict__ b, const float* x, int ldx, float* out,
+                                                         int ldo, T* __restrict__ out_copy, int ldc, int R, int K, int N,
+                                                         int vec_a) {
+  rnn_tile<1>(FfCell<T>{a, lda, W, ldw, b, x, ldx, {nullptr, 0, out, ldo, out_copy, ldc}}, R, K, N, vec_a);
+}
 
 template <typename Kern>
 static int rnn_lds_attr(const char* name, Kern kern, size_t lds) {
@@ -540,73 +445,6 @@ static int rnn_lds_attr(const char* name, Kern kern, size_t lds) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return zk_set_error((int)e, "%s: hipFuncSetAttribute: %s", name, hipGetErrorString(e));
   return 0;
-}
-
-// ---------------------------------------------------------------- ff + residual of a deepnmt layer
-// models/deepnmt.py:73-79 (encoder) and 166-172 (decoder): y = linear(outputs, embed_size, scope="ff"); x = x + y, with
-// layer_norm off -- so NOTHING re-normalises x from the embedding to the last layer.  One launch:
-//     out[r, :] = x[r, :] + (a[r, :] W + b)          out_copy = the same in the storage type (the next product's operand)
-// The stream x / out is fp32 in BOTH forms for the reason the recurrent state is: a bf16 stream would drop every layer's
-// update below half an ulp of x, and the loss would add up over the layers (DESIGN.md 6n; 6j has the same argument for
-// transformer_fixup).  In the bf16 form only the MFMA operands a and W are bf16.  out may BE x (same address, same stride):
-// an element is read and written by the one lane that owns it, and no lane reads another's.
-// bf16 form: the tile scheme of k_rnn_atr_step -- 16 output columns x 64 rows per workgroup, the slab W[:, n0 .. n0 + 15]
-// streamed once into the transposed LDS image [16][K + 8] (131 KB for K = 4096, the largest K), the A fragments 16-byte
-// global loads of a (bf16 already), v_mfma_f32_16x16x32_bf16; edge tiles in rows, columns and K are zero-filled.
-// fp32 form: the scheme of k_f32_rnn_atr_step -- 64 columns x 32 rows, lane = column, k ascending.
-// No workgroup waits for another in either form.
-__global__ void __launch_bounds__(256) k_rnn_ff_residual(const bf16_t* __restrict__ a, int lda, const bf16_t* __restrict__ W,
-                                                         int ldw, const float* __restrict__ b, const float* x, int ldx,
-                                                         float* out, int ldo, bf16_t* __restrict__ out_copy, int ldc, int R,
-                                                         int K, int N, int vec_a) {
-  extern __shared__ __align__(16) unsigned char ff_lds[];
-  bf16_t* sW = reinterpret_cast<bf16_t*>(ff_lds);            // [ATR_BN][KS]
-  const int Kr = (K + 31) / 32 * 32, KS = Kr + 8;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n0 = blockIdx.x * ATR_BN, r0 = blockIdx.y * ATR_BM + wave * 16;
-  rf32x4_t acc[1] = {{0.f, 0.f, 0.f, 0.f}};
-  rnn_stage_slab(sW, KS, W, ldw, n0, K, N, Kr);
-  __syncthreads();
-  if (r0 < R) {                                                // wave-uniform: the MFMA runs with all 64 lanes
-    const int row = r0 + (lane & 15);
-    const bool valid = row < R;
-    rnn_product<1, false>(acc, sW, KS, Kr, K, a + (size_t)(valid ? row : 0) * lda, valid, vec_a, lane);
-  }
-  const int col = n0 + (lane & 15);
-  if (col >= N) return;
-  const float bias = b[col];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = r0 + (lane >> 4) * 4 + r;
-    if (row >= R) continue;
-    const float o = x[(size_t)row * ldx + col] + (acc[0][r] + bias);
-    out[(size_t)row * ldo + col] = o;
-    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = f2bf(o);
-  }
-}
-
-__global__ void __launch_bounds__(256) k_f32_rnn_ff_residual(const float* __restrict__ a, int lda, const float* __restrict__ W,
-                                                             int ldw, const float* __restrict__ b, const float* x, int ldx,
-                                                             float* out, int ldo, float* __restrict__ out_copy, int ldc, int R,
-                                                             int K, int N) {
-  __shared__ __align__(16) float sh[ATRF_BM][64];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int col = blockIdx.x * ATRF_BN + lane, r0 = blockIdx.y * ATRF_BM;
-  float acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  const int grow = r0 + (threadIdx.x >> 3);
-  rnn_f32_product(acc, sh, grow < R ? a + (size_t)grow * lda : nullptr, W, ldw, K, N, col, wave);
-  if (col >= N) return;
-  const float bias = b[col];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int row = r0 + wave * 8 + j;
-    if (row >= R) continue;
-    const float o = x[(size_t)row * ldx + col] + (acc[j] + bias);
-    out[(size_t)row * ldo + col] = o;
-    if (out_copy != nullptr) out_copy[(size_t)row * ldc + col] = o;
-  }
 }
 
 // true when the byte ranges that ENCLOSE the rows of p ([rp, wp] elements of ep bytes, stride ldp) and of q meet.  Conservative:
@@ -619,24 +457,162 @@ static bool rnn_spans_meet(const void* p, long ldp, long rp, long wp, long ep, c
   return p0 < q1 && q0 < p1;
 }
 
-// ESZ: bytes of an element of the storage type (a, W, out_copy)
-#define FF_CHECK_COMMON(NAME, ESZ)                                                                                          \
-  ZK_CHECK_ARG(a != nullptr && W != nullptr && b != nullptr && x != nullptr && out != nullptr,                              \
-               NAME ": a, W, b, x and out are required");                                                                   \
-  ZK_CHECK_ARG(R >= 0 && K >= 1 && N >= 1, NAME ": bad shape (R=%d K=%d N=%d)", R, K, N);                                   \
-  ZK_CHECK_ARG(lda >= K && ldw >= N && ldx >= N && ldo >= N && (out_copy == nullptr || ldc >= N),                           \
-               NAME ": a leading dimension is too small for K=%d N=%d (lda=%d ldw=%d ldx=%d ldo=%d ldc=%d)", K, N, lda,     \
-               ldw, ldx, ldo, ldc);                                                                                         \
-  ZK_CHECK_ARG((out == x && ldo == ldx) || !rnn_rows_overlap(out, ldo, R, x, ldx, R, N),                                    \
-               NAME ": out overlaps x without being x (in place needs the same address and the same stride: then every "   \
-               "element is read and written by the one lane that owns it)");                                                \
-  ZK_CHECK_ARG(!rnn_spans_meet(a, lda, R, K, ESZ, out, ldo, R, N, 4) &&                                                     \
-               !rnn_spans_meet(a, lda, R, K, ESZ, out_copy, ldc, R, N, ESZ),                                                \
-               NAME ": the span of out or out_copy meets the span of a (every column tile reads whole rows of a while "    \
-               "others write; the check is by enclosing byte ranges: keep a in a buffer of its own)");                      \
-  ZK_CHECK_ARG(!rnn_spans_meet(out_copy, ldc, R, N, ESZ, out, ldo, R, N, 4) &&                                              \
-               !rnn_spans_meet(out_copy, ldc, R, N, ESZ, x, ldx, R, N, 4),                                                  \
-               NAME ": the span of out_copy meets the span of x or out (by enclosing byte ranges)")
+// ---------------------------------------------------------------- host side of the dense cells
+// One launch function per cell, `F32` the form; the storage-type operands arrive as void pointers.
+template <bool F32>
+using rnn_st_t = typename std::conditional<F32, float, bf16_t>::type;
+
+static int rnn_check_n_prev(const char* name, const RnnState& s, int R) {
+  ZK_CHECK_ARG(s.h_prev == nullptr || (s.idx != nullptr ? s.n_prev >= 1 : s.n_prev >= R),
+               "%s: h_prev has n_prev=%d rows (R=%d without an index, at least 1 with one)", name, s.n_prev, R);
+  return 0;
+}
+
+// grid, LDS and launch of a cell kernel: NT blocks of N columns of W, K rows (the geometry at the two tile drivers)
+template <bool F32, int NT, typename Kern, typename... Args>
+static int rnn_cell_launch(const char* name, Kern kern, int R, int K, int N, hipStream_t stream, Args... args) {
+  const size_t lds = F32 ? 0 : (size_t)NT * ATR_BN * ((K + 31) / 32 * 32 + 8) * sizeof(bf16_t);
+  if (rnn_lds_attr(name, kern, lds) != 0) return -1;
+  const dim3 grid = F32 ? dim3((unsigned)(NT * ((N + ATRF_BN - 1) / ATRF_BN)), (unsigned)((R + ATRF_BM - 1) / ATRF_BM))
+                        : dim3((unsigned)((N + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM));
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, args...);
+  ZK_LAUNCH_CHECK();
+  return 0;
+}
+
+// the 16-byte loads of the A operand: fp32 state rows (4 floats) or bf16 rows (8 elements); the fp32 form has none
+static int rnn_vec_a(const void* a, int lda, int per16) { return a != nullptr && lda % per16 == 0 && (((uintptr_t)a) & 15) == 0; }
+
+template <bool F32>
+static int rnn_atr_launch(const char* name, RnnState s, const void* U, int ldu, const float* b, const void* p, int ldp,
+                          const float* mask, int ldm, float* out, int ldo, void* out_copy, int ldc, int R, int H,
+                          hipStream_t stream) {
+  typedef rnn_st_t<F32> T;
+  ZK_CHECK_ARG(U != nullptr && b != nullptr && p != nullptr && out != nullptr, "%s: U, b, p and out are required", name);
+  ZK_CHECK_ARG(R >= 0 && H >= 1, "%s: bad shape (R=%d H=%d)", name, R, H);
+  ZK_CHECK_ARG(ldu >= H && ldp >= H && ldo >= H && (out_copy == nullptr || ldc >= H) && (s.h_prev == nullptr || s.ldh >= H),
+               "%s: a leading dimension is smaller than H=%d (ldh=%d ldu=%d ldp=%d ldo=%d ldc=%d)", name, H, s.ldh, ldu, ldp,
+               ldo, ldc);
+  if (rnn_check_n_prev(name, s, R) != 0) return -1;
+  ZK_CHECK_ARG(mask == nullptr || ldm >= 1, "%s: the mask stride must be at least 1 (ldm=%d)", name, ldm);
+  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, s.h_prev, s.ldh, s.n_prev, H),
+               "%s: out overlaps h_prev (every column tile reads whole rows of h_prev while others write out)", name);
+  if (F32)
+    ZK_CHECK_ARG(!rnn_rows_overlap(reinterpret_cast<const float*>(out_copy), ldc, R, s.h_prev, s.ldh, s.n_prev, H),
+                 "%s: out_copy overlaps h_prev", name);
+  else
+    ZK_CHECK_ARG(H % 8 == 0 && H <= 4096 && ldu % 8 == 0 && (((uintptr_t)U) & 15) == 0,
+                 "%s: the bf16 form needs H a multiple of 8 and at most 4096 and 16-byte aligned rows of U (H=%d ldu=%d); "
+                 "zk_f32_rnn_atr_step takes any H", name, H, ldu);
+  if (R == 0) return 0;
+  return rnn_cell_launch<F32, 1>(name, k_rnn_atr_step<T>, R, H, H, stream, s.h_prev, s.ldh, s.n_prev, s.idx,
+                                 reinterpret_cast<const T*>(U), ldu, b, reinterpret_cast<const T*>(p), ldp, mask, ldm, out, ldo,
+                                 reinterpret_cast<T*>(out_copy), ldc, R, H, F32 ? 0 : rnn_vec_a(s.h_prev, s.ldh, 4));
+}
+
+// what the two GRU launches refuse alike; the bf16 forms name their fp32 twin (zk_f32_ + the name past its zk_)
+static int gru_check_state(const char* name, const RnnState& s, int R, int H) {
+  ZK_CHECK_ARG(R >= 0 && H >= 1, "%s: bad shape (R=%d H=%d)", name, R, H);
+  ZK_CHECK_ARG(s.h_prev == nullptr || s.ldh >= H, "%s: ldh=%d is smaller than H=%d", name, s.ldh, H);
+  return rnn_check_n_prev(name, s, R);
+}
+
+static int gru_check_bf16(const char* name, const void* U, int ldu, int H) {
+  ZK_CHECK_ARG(H % 8 == 0 && H <= GRU_MAX_H && ldu % 8 == 0 && (((uintptr_t)U) & 15) == 0,
+               "%s: the bf16 form needs H a multiple of 8 and at most %d (its LDS image of the recurrent matrix) and "
+               "16-byte aligned rows of the matrix (H=%d ldu=%d); zk_f32_%s takes any H", name, GRU_MAX_H, H, ldu, name + 3);
+  return 0;
+}
+
+template <bool F32>
+static int rnn_gru_gates_launch(const char* name, RnnState s, const void* Ug, int ldu, const float* bg, const void* xg, int ldx,
+                                float* z, int ldz, void* rh, int ldr, int R, int H, hipStream_t stream) {
+  typedef rnn_st_t<F32> T;
+  ZK_CHECK_ARG(Ug != nullptr && bg != nullptr && xg != nullptr && z != nullptr && rh != nullptr,
+               "%s: Ug, bg, xg, z and rh are required", name);
+  if (gru_check_state(name, s, R, H) != 0) return -1;
+  ZK_CHECK_ARG(ldu >= 2 * H && ldx >= 2 * H && ldz >= H && ldr >= H,
+               "%s: a leading dimension is too small for H=%d (ldu=%d and ldx=%d hold 2 H columns, ldz=%d ldr=%d)", name, H,
+               ldu, ldx, ldz, ldr);
+  ZK_CHECK_ARG(!rnn_rows_overlap(z, ldz, R, s.h_prev, s.ldh, s.n_prev, H),
+               "%s: z overlaps h_prev (every column tile reads whole rows of h_prev while others write z)", name);
+  if (F32)
+    ZK_CHECK_ARG(!rnn_rows_overlap(reinterpret_cast<const float*>(rh), ldr, R, s.h_prev, s.ldh, s.n_prev, H),
+                 "%s: rh overlaps h_prev", name);
+  else if (gru_check_bf16(name, Ug, ldu, H) != 0)
+    return -1;
+  if (R == 0) return 0;
+  return rnn_cell_launch<F32, 2>(name, k_rnn_gru_gates<T>, R, H, H, stream, s.h_prev, s.ldh, s.n_prev, s.idx,
+                                 reinterpret_cast<const T*>(Ug), ldu, bg, reinterpret_cast<const T*>(xg), ldx, z, ldz,
+                                 reinterpret_cast<T*>(rh), ldr, R, H, F32 ? 0 : rnn_vec_a(s.h_prev, s.ldh, 4));
+}
+
+template <bool F32>
+static int rnn_gru_out_launch(const char* name, const void* rh, int ldr, const void* Uh, int ldu, const float* bh, const void* xh,
+                              int ldx, const float* z, int ldz, RnnState s, const float* mask, int ldm, float* out, int ldo,
+                              void* out_copy, int ldc, int R, int H, hipStream_t stream) {
+  typedef rnn_st_t<F32> T;
+  ZK_CHECK_ARG(rh != nullptr && Uh != nullptr && bh != nullptr && xh != nullptr && z != nullptr && out != nullptr,
+               "%s: rh, Uh, bh, xh, z and out are required", name);
+  if (gru_check_state(name, s, R, H) != 0) return -1;
+  ZK_CHECK_ARG(ldr >= H && ldu >= H && ldx >= H && ldz >= H && ldo >= H && (out_copy == nullptr || ldc >= H),
+               "%s: a leading dimension is smaller than H=%d (ldr=%d ldu=%d ldx=%d ldz=%d ldo=%d ldc=%d)", name, H, ldr, ldu,
+               ldx, ldz, ldo, ldc);
+  ZK_CHECK_ARG(mask == nullptr || ldm >= 1, "%s: the mask stride must be at least 1 (ldm=%d)", name, ldm);
+  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, s.h_prev, s.ldh, s.n_prev, H),
+               "%s: out overlaps h_prev (a row of h_prev may be gathered by several rows while others write out)", name);
+  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, z, ldz, R, H), "%s: out overlaps z", name);
+  if (F32) {
+    const float* cp = reinterpret_cast<const float*>(out_copy);
+    const float* rf = reinterpret_cast<const float*>(rh);
+    ZK_CHECK_ARG(!rnn_rows_overlap(cp, ldc, R, s.h_prev, s.ldh, s.n_prev, H), "%s: out_copy overlaps h_prev", name);
+    ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, rf, ldr, R, H) && !rnn_rows_overlap(cp, ldc, R, rf, ldr, R, H),
+                 "%s: out or out_copy overlaps rh (every column tile reads whole rows of rh)", name);
+  } else if (gru_check_bf16(name, Uh, ldu, H) != 0) {
+    return -1;
+  }
+  if (R == 0) return 0;
+  return rnn_cell_launch<F32, 1>(name, k_rnn_gru_out<T>, R, H, H, stream, reinterpret_cast<const T*>(rh), ldr,
+                                 reinterpret_cast<const T*>(Uh), ldu, bh, reinterpret_cast<const T*>(xh), ldx, z, ldz, s.h_prev,
+                                 s.ldh, s.n_prev, s.idx, mask, ldm, out, ldo, reinterpret_cast<T*>(out_copy), ldc, R, H,
+                                 F32 ? 0 : rnn_vec_a(rh, ldr, 8));
+}
+
+template <bool F32>
+static int rnn_ff_residual_launch(const char* name, const void* a, int lda, const void* W, int ldw, const float* b, const float* x,
+                                  int ldx, float* out, int ldo, void* out_copy, int ldc, int R, int K, int N,
+                                  hipStream_t stream) {
+  typedef rnn_st_t<F32> T;
+  const long esz = sizeof(T);                                  // bytes of an element of the storage type (a, W, out_copy)
+  ZK_CHECK_ARG(a != nullptr && W != nullptr && b != nullptr && x != nullptr && out != nullptr,
+               "%s: a, W, b, x and out are required", name);
+  ZK_CHECK_ARG(R >= 0 && K >= 1 && N >= 1, "%s: bad shape (R=%d K=%d N=%d)", name, R, K, N);
+  ZK_CHECK_ARG(lda >= K && ldw >= N && ldx >= N && ldo >= N && (out_copy == nullptr || ldc >= N),
+               "%s: a leading dimension is too small for K=%d N=%d (lda=%d ldw=%d ldx=%d ldo=%d ldc=%d)", name, K, N, lda,
+               ldw, ldx, ldo, ldc);
+  ZK_CHECK_ARG((out == x && ldo == ldx) || !rnn_rows_overlap(out, ldo, R, x, ldx, R, N),
+               "%s: out overlaps x without being x (in place needs the same address and the same stride: then every "
+               "element is read and written by the one lane that owns it)", name);
+  ZK_CHECK_ARG(!rnn_spans_meet(a, lda, R, K, esz, out, ldo, R, N, 4) &&
+               !rnn_spans_meet(a, lda, R, K, esz, out_copy, ldc, R, N, esz),
+               "%s: the span of out or out_copy meets the span of a (every column tile reads whole rows of a while "
+               "others write; the check is by enclosing byte ranges: keep a in a buffer of its own)", name);
+  ZK_CHECK_ARG(!rnn_spans_meet(out_copy, ldc, R, N, esz, out, ldo, R, N, 4) &&
+               !rnn_spans_meet(out_copy, ldc, R, N, esz, x, ldx, R, N, 4),
+               "%s: the span of out_copy meets the span of x or out (by enclosing byte ranges)", name);
+  if (!F32) {
+    ZK_CHECK_ARG(K % 8 == 0 && N % 8 == 0 && K <= 4096,
+                 "%s: the bf16 form needs K and N multiples of 8 and K at most 4096 (its LDS image of 16 columns "
+                 "of W: 131 KB there) -- got K=%d N=%d; zk_f32_rnn_ff_residual takes any K and N", name, K, N);
+    ZK_CHECK_ARG(ldw % 8 == 0 && (((uintptr_t)W) & 15) == 0,
+                 "%s: the bf16 form reads W 16 bytes at a time: its rows must be 16-byte aligned (ldw=%d, W %% 16 "
+                 "= %d)", name, ldw, (int)(((uintptr_t)W) & 15));
+  }
+  if (R == 0) return 0;
+  return rnn_cell_launch<F32, 1>(name, k_rnn_ff_residual<T>, R, K, N, stream, reinterpret_cast<const T*>(a), lda,
+                                 reinterpret_cast<const T*>(W), ldw, b, x, ldx, out, ldo, reinterpret_cast<T*>(out_copy), ldc, R, K,
+                                 N, F32 ? 0 : rnn_vec_a(a, lda, 8));
+}
 
 // ---------------------------------------------------------------- additive attention
 #define ADD_RB 4          // beam rows per workgroup (1 when a sentence has a single row)
@@ -1020,12 +996,6 @@ __global__ void __launch_bounds__(64) k_rnn_lrn_scan(const float* __restrict__ h
   }
 }
 
-// the bytes [base, end) that enclose an operand of T positions x R rows x w elements of esz bytes
-static void lrn_span(const void* p, long ps, long rs, long T, long R, long w, long esz, uintptr_t* b0, uintptr_t* b1) {
-  *b0 = (uintptr_t)p;
-  *b1 = *b0 + (uintptr_t)(((T - 1) * ps + (R - 1) * rs + w) * esz);
-}
-
 template <bool F32>
 static int lrn_scan_launch(const char* name, const char* other, const float* h_prev, int ldh, int n_prev, const int* idx,
                            const void* lo, long lo_ps, long lo_rs, const void* hi, long hi_ps, long hi_rs, const float* mask,
@@ -1058,18 +1028,12 @@ static int lrn_scan_launch(const char* name, const char* other, const float* h_p
   if (rnn_rows_overlap(out, ldo, R, h_prev, ldh, n_prev, H))
     return zk_set_error(-1, "%s: out overlaps h_prev (a row of h_prev may be gathered by several rows while others write out)", name);
   if (seq != nullptr) {
-    uintptr_t s0, s1, a0, a1;
-    lrn_span(seq, sq_ps, sq_rs, T, R, H, esz, &s0, &s1);
-    lrn_span(lo, lo_ps, lo_rs, T, R, W, esz, &a0, &a1);
-    bool meet = s0 < a1 && a0 < s1;
-    if (hi != nullptr) {
-      lrn_span(hi, hi_ps, hi_rs, T, R, W, esz, &a0, &a1);
-      meet = meet || (s0 < a1 && a0 < s1);
-    }
-    if (meet) return zk_set_error(-1, "%s: seq overlaps lo / hi (by enclosing byte ranges: later positions are read while earlier "
-                                  "ones are written)", name);
-    if (rnn_spans_meet(seq, sq_rs, R, (T - 1) * sq_ps + H, esz, h_prev, ldh, n_prev, H, 4) ||
-        rnn_spans_meet(seq, sq_rs, R, (T - 1) * sq_ps + H, esz, out, ldo, R, H, 4))
+    const long sw = (T - 1) * sq_ps + H;                        // a "row" of the span: the T positions of one sentence row
+    if (rnn_spans_meet(seq, sq_rs, R, sw, esz, lo, lo_rs, R, (T - 1) * lo_ps + W, esz) ||
+        rnn_spans_meet(seq, sq_rs, R, sw, esz, hi, hi_rs, R, (T - 1) * hi_ps + W, esz))
+      return zk_set_error(-1, "%s: seq overlaps lo / hi (by enclosing byte ranges: later positions are read while earlier "
+                          "ones are written)", name);
+    if (rnn_spans_meet(seq, sq_rs, R, sw, esz, h_prev, ldh, n_prev, H, 4) || rnn_spans_meet(seq, sq_rs, R, sw, esz, out, ldo, R, H, 4))
       return zk_set_error(-1, "%s: seq overlaps h_prev or out (by enclosing byte ranges)", name);
   }
   if (R == 0) return 0;
@@ -1096,123 +1060,52 @@ extern "C" {
 int zk_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const void* U, int ldu, const float* b,
                     const void* p, int ldp, const float* mask, int ldm, float* out, int ldo, void* out_copy, int ldc, int R,
                     int H, hipStream_t stream) {
-  ATR_CHECK_COMMON("zk_rnn_atr_step");
-  ZK_CHECK_ARG(H % 8 == 0 && H <= 4096 && ldu % 8 == 0 && (((uintptr_t)U) & 15) == 0,
-               "zk_rnn_atr_step: the bf16 form needs H a multiple of 8 and at most 4096 and 16-byte aligned rows of U (H=%d "
-               "ldu=%d); zk_f32_rnn_atr_step takes any H", H, ldu);
-  if (R == 0) return 0;
-  const int Kr = (H + 31) / 32 * 32;
-  const size_t lds = (size_t)ATR_BN * (Kr + 8) * sizeof(bf16_t);
-  const int vec_a = h_prev != nullptr && ldh % 4 == 0 && (((uintptr_t)h_prev) & 15) == 0;
-  hipLaunchKernelGGL(k_rnn_atr_step, dim3((unsigned)((H + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)), dim3(256),
-                     lds, stream, h_prev, ldh, n_prev, idx, reinterpret_cast<const bf16_t*>(U), ldu, b,
-                     reinterpret_cast<const bf16_t*>(p), ldp, mask, ldm, out, ldo, reinterpret_cast<bf16_t*>(out_copy), ldc, R, H,
-                     vec_a);
-  ZK_LAUNCH_CHECK();
-  return 0;
+  return rnn_atr_launch<false>("zk_rnn_atr_step", {h_prev, ldh, n_prev, idx}, U, ldu, b, p, ldp, mask, ldm, out, ldo, out_copy,
+                               ldc, R, H, stream);
 }
 
 int zk_f32_rnn_atr_step(const float* h_prev, int ldh, int n_prev, const int* idx, const float* U, int ldu, const float* b,
                         const float* p, int ldp, const float* mask, int ldm, float* out, int ldo, float* out_copy, int ldc,
                         int R, int H, hipStream_t stream) {
-  ATR_CHECK_COMMON("zk_f32_rnn_atr_step");
-  ZK_CHECK_ARG(!rnn_rows_overlap(out_copy, ldc, R, h_prev, ldh, n_prev, H), "zk_f32_rnn_atr_step: out_copy overlaps h_prev");
-  if (R == 0) return 0;
-  hipLaunchKernelGGL(k_f32_rnn_atr_step, dim3((unsigned)((H + ATRF_BN - 1) / ATRF_BN), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
-                     dim3(256), 0, stream, h_prev, ldh, n_prev, idx, U, ldu, b, p, ldp, mask, ldm, out, ldo, out_copy, ldc, R, H);
-  ZK_LAUNCH_CHECK();
-  return 0;
+  return rnn_atr_launch<true>("zk_f32_rnn_atr_step", {h_prev, ldh, n_prev, idx}, U, ldu, b, p, ldp, mask, ldm, out, ldo,
+                              out_copy, ldc, R, H, stream);
 }
 
 int zk_rnn_gru_gates(const float* h_prev, int ldh, int n_prev, const int* idx, const void* Ug, int ldu, const float* bg,
                      const void* xg, int ldx, float* z, int ldz, void* rh, int ldr, int R, int H, hipStream_t stream) {
-  GRU_CHECK_GATES("zk_rnn_gru_gates");
-  GRU_CHECK_BF16("zk_rnn_gru_gates", Ug, "zk_f32_rnn_gru_gates");
-  if (R == 0) return 0;
-  const int Kr = (H + 31) / 32 * 32;
-  const size_t lds = (size_t)2 * ATR_BN * (Kr + 8) * sizeof(bf16_t);
-  if (rnn_lds_attr("zk_rnn_gru_gates", k_rnn_gru_gates, lds) != 0) return -1;
-  const int vec_a = h_prev != nullptr && ldh % 4 == 0 && (((uintptr_t)h_prev) & 15) == 0;
-  hipLaunchKernelGGL(k_rnn_gru_gates, dim3((unsigned)((H + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)),
-                     dim3(256), lds, stream, h_prev, ldh, n_prev, idx, reinterpret_cast<const bf16_t*>(Ug), ldu, bg,
-                     reinterpret_cast<const bf16_t*>(xg), ldx, z, ldz, reinterpret_cast<bf16_t*>(rh), ldr, R, H, vec_a);
-  ZK_LAUNCH_CHECK();
-  return 0;
+  return rnn_gru_gates_launch<false>("zk_rnn_gru_gates", {h_prev, ldh, n_prev, idx}, Ug, ldu, bg, xg, ldx, z, ldz, rh, ldr, R, H,
+                                     stream);
 }
 
 int zk_f32_rnn_gru_gates(const float* h_prev, int ldh, int n_prev, const int* idx, const float* Ug, int ldu, const float* bg,
                          const float* xg, int ldx, float* z, int ldz, float* rh, int ldr, int R, int H, hipStream_t stream) {
-  GRU_CHECK_GATES("zk_f32_rnn_gru_gates");
-  ZK_CHECK_ARG(!rnn_rows_overlap(rh, ldr, R, h_prev, ldh, n_prev, H), "zk_f32_rnn_gru_gates: rh overlaps h_prev");
-  if (R == 0) return 0;
-  hipLaunchKernelGGL(k_f32_rnn_gru_gates, dim3((unsigned)(2 * ((H + ATRF_BN - 1) / ATRF_BN)), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
-                     dim3(256), 0, stream, h_prev, ldh, n_prev, idx, Ug, ldu, bg, xg, ldx, z, ldz, rh, ldr, R, H);
-  ZK_LAUNCH_CHECK();
-  return 0;
+  return rnn_gru_gates_launch<true>("zk_f32_rnn_gru_gates", {h_prev, ldh, n_prev, idx}, Ug, ldu, bg, xg, ldx, z, ldz, rh, ldr, R,
+                                    H, stream);
 }
 
 int zk_rnn_gru_out(const void* rh, int ldr, const void* Uh, int ldu, const float* bh, const void* xh, int ldx, const float* z,
                    int ldz, const float* h_prev, int ldh, int n_prev, const int* idx, const float* mask, int ldm, float* out,
                    int ldo, void* out_copy, int ldc, int R, int H, hipStream_t stream) {
-  GRU_CHECK_OUT("zk_rnn_gru_out");
-  GRU_CHECK_BF16("zk_rnn_gru_out", Uh, "zk_f32_rnn_gru_out");
-  if (R == 0) return 0;
-  const int Kr = (H + 31) / 32 * 32;
-  const size_t lds = (size_t)ATR_BN * (Kr + 8) * sizeof(bf16_t);
-  if (rnn_lds_attr("zk_rnn_gru_out", k_rnn_gru_out, lds) != 0) return -1;
-  const int vec_a = ldr % 8 == 0 && (((uintptr_t)rh) & 15) == 0;
-  hipLaunchKernelGGL(k_rnn_gru_out, dim3((unsigned)((H + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)), dim3(256),
-                     lds, stream, reinterpret_cast<const bf16_t*>(rh), ldr, reinterpret_cast<const bf16_t*>(Uh), ldu, bh,
-                     reinterpret_cast<const bf16_t*>(xh), ldx, z, ldz, h_prev, ldh, n_prev, idx, mask, ldm, out, ldo,
-                     reinterpret_cast<bf16_t*>(out_copy), ldc, R, H, vec_a);
-  ZK_LAUNCH_CHECK();
-  return 0;
+  return rnn_gru_out_launch<false>("zk_rnn_gru_out", rh, ldr, Uh, ldu, bh, xh, ldx, z, ldz, {h_prev, ldh, n_prev, idx}, mask, ldm,
+                                   out, ldo, out_copy, ldc, R, H, stream);
 }
 
 int zk_f32_rnn_gru_out(const float* rh, int ldr, const float* Uh, int ldu, const float* bh, const float* xh, int ldx,
                        const float* z, int ldz, const float* h_prev, int ldh, int n_prev, const int* idx, const float* mask,
                        int ldm, float* out, int ldo, float* out_copy, int ldc, int R, int H, hipStream_t stream) {
-  GRU_CHECK_OUT("zk_f32_rnn_gru_out");
-  ZK_CHECK_ARG(!rnn_rows_overlap(out_copy, ldc, R, h_prev, ldh, n_prev, H), "zk_f32_rnn_gru_out: out_copy overlaps h_prev");
-  ZK_CHECK_ARG(!rnn_rows_overlap(out, ldo, R, rh, ldr, R, H) && !rnn_rows_overlap(out_copy, ldc, R, rh, ldr, R, H),
-               "zk_f32_rnn_gru_out: out or out_copy overlaps rh (every column tile reads whole rows of rh)");
-  if (R == 0) return 0;
-  hipLaunchKernelGGL(k_f32_rnn_gru_out, dim3((unsigned)((H + ATRF_BN - 1) / ATRF_BN), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
-                     dim3(256), 0, stream, rh, ldr, Uh, ldu, bh, xh, ldx, z, ldz, h_prev, ldh, n_prev, idx, mask, ldm, out, ldo,
-                     out_copy, ldc, R, H);
-  ZK_LAUNCH_CHECK();
-  return 0;
+  return rnn_gru_out_launch<true>("zk_f32_rnn_gru_out", rh, ldr, Uh, ldu, bh, xh, ldx, z, ldz, {h_prev, ldh, n_prev, idx}, mask,
+                                  ldm, out, ldo, out_copy, ldc, R, H, stream);
 }
 
 int zk_rnn_ff_residual(const void* a, int lda, const void* W, int ldw, const float* b, const float* x, int ldx, float* out,
                        int ldo, void* out_copy, int ldc, int R, int K, int N, hipStream_t stream) {
-  FF_CHECK_COMMON("zk_rnn_ff_residual", 2);
-  ZK_CHECK_ARG(K % 8 == 0 && N % 8 == 0 && K <= 4096,
-               "zk_rnn_ff_residual: the bf16 form needs K and N multiples of 8 and K at most 4096 (its LDS image of 16 columns "
-               "of W: 131 KB there) -- got K=%d N=%d; zk_f32_rnn_ff_residual takes any K and N", K, N);
-  ZK_CHECK_ARG(ldw % 8 == 0 && (((uintptr_t)W) & 15) == 0,
-               "zk_rnn_ff_residual: the bf16 form reads W 16 bytes at a time: its rows must be 16-byte aligned (ldw=%d, W %% 16 "
-               "= %d)", ldw, (int)(((uintptr_t)W) & 15));
-  if (R == 0) return 0;
-  const int Kr = (K + 31) / 32 * 32;
-  const size_t lds = (size_t)ATR_BN * (Kr + 8) * sizeof(bf16_t);
-  if (rnn_lds_attr("zk_rnn_ff_residual", k_rnn_ff_residual, lds) != 0) return -1;
-  const int vec_a = lda % 8 == 0 && (((uintptr_t)a) & 15) == 0;
-  hipLaunchKernelGGL(k_rnn_ff_residual, dim3((unsigned)((N + ATR_BN - 1) / ATR_BN), (unsigned)((R + ATR_BM - 1) / ATR_BM)),
-                     dim3(256), lds, stream, reinterpret_cast<const bf16_t*>(a), lda, reinterpret_cast<const bf16_t*>(W), ldw, b, x,
-                     ldx, out, ldo, reinterpret_cast<bf16_t*>(out_copy), ldc, R, K, N, vec_a);
-  ZK_LAUNCH_CHECK();
-  return 0;
+  return rnn_ff_residual_launch<false>("zk_rnn_ff_residual", a, lda, W, ldw, b, x, ldx, out, ldo, out_copy, ldc, R, K, N, stream);
 }
 
 int zk_f32_rnn_ff_residual(const float* a, int lda, const float* W, int ldw, const float* b, const float* x, int ldx, float* out,
                            int ldo, float* out_copy, int ldc, int R, int K, int N, hipStream_t stream) {
-  FF_CHECK_COMMON("zk_f32_rnn_ff_residual", 4);
-  if (R == 0) return 0;
-  hipLaunchKernelGGL(k_f32_rnn_ff_residual, dim3((unsigned)((N + ATRF_BN - 1) / ATRF_BN), (unsigned)((R + ATRF_BM - 1) / ATRF_BM)),
-                     dim3(256), 0, stream, a, lda, W, ldw, b, x, ldx, out, ldo, out_copy, ldc, R, K, N);
-  ZK_LAUNCH_CHECK();
-  return 0;
+  return rnn_ff_residual_launch<true>("zk_f32_rnn_ff_residual", a, lda, W, ldw, b, x, ldx, out, ldo, out_copy, ldc, R, K, N,
+                                      stream);
 }
 
 int zk_add_attn(const void* qa, int ldq, const void* pm, int ldpm, long bspm, const void* mem, int ldmem, long bsmem,

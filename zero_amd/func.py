@@ -67,6 +67,16 @@ class Mat(object):
         return torch.as_strided(flat, (self.rows, self.cols), (self.ld, 1), self.off)
 
 
+def _mp(t):
+    """(pointer, leading dimension) of an optional Mat operand"""
+    return (t.ptr, t.ld) if t is not None else (None, 0)
+
+
+def _state(h_prev, idx):
+    """(h_prev, ldh, n_prev, idx) of the recurrent launches: an fp32 Mat or None (the zero state), gathered by idx or not"""
+    return (*_mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx))
+
+
 def _removed_kernel(name):
     def removed(*args, **kwargs):
         raise hip.ZeroHipError("%s was removed (a measured negative result; see git history)" % name)
@@ -631,8 +641,7 @@ class Engine(object):
         st = y if y is not None else xs_out
         m = next(t for t in (xs_out, x_out, y, x) if t is not None)
         name = "zk_f32_fixup_residual" if st is not None and st.t.dtype == torch.float32 else "zk_fixup_residual"
-        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
-        self.lib.call(name, *mp(x), *mp(y), hip.ptr(scale), hip.ptr(offset), hip.ptr(scale2), *mp(x_out), *mp(xs_out),
+        self.lib.call(name, *_mp(x), *_mp(y), hip.ptr(scale), hip.ptr(offset), hip.ptr(scale2), *_mp(x_out), *_mp(xs_out),
                       m.rows, m.cols, self.stream)
 
     def fixup_relu_shift(self, h, offset, out):
@@ -648,17 +657,15 @@ class Engine(object):
         [R] or None; U: Mat [H, H] and p: Mat [R, H] of the storage type; b: fp32 [H]; mask: fp32 Mat [R, 1] (ld = the
         stride between rows) or None; out: fp32 Mat [R, H]; out_copy: storage-type Mat [R, H] or None."""
         name = "zk_f32_rnn_atr_step" if p.t.dtype == torch.float32 else "zk_rnn_atr_step"
-        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
-        self.lib.call(name, *mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx), U.ptr, U.ld,
-                      b.data_ptr(), p.ptr, p.ld, *mp(mask), out.ptr, out.ld, *mp(out_copy), out.rows, out.cols, self.stream)
+        self.lib.call(name, *_state(h_prev, idx), U.ptr, U.ld, b.data_ptr(), p.ptr, p.ld, *_mp(mask), out.ptr, out.ld,
+                      *_mp(out_copy), out.rows, out.cols, self.stream)
 
     def rnn_ff_residual(self, a, W, b, x, out, out_copy=None):
         """models/deepnmt.py:73-79, 166-172 in one launch (zk_rnn_ff_residual; the fp32 form by a's dtype): out = x + (a W + b)
         on the fp32 residual stream.  a: Mat [R, K] and W: Mat [K, N] of the storage type; b: fp32 [N]; x, out: fp32 Mats
         [R, N] (out may be x itself); out_copy: storage-type Mat [R, N] -- e.g. a column slice of the next operand -- or None."""
         name = "zk_f32_rnn_ff_residual" if a.t.dtype == torch.float32 else "zk_rnn_ff_residual"
-        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
-        self.lib.call(name, a.ptr, a.ld, W.ptr, W.ld, b.data_ptr(), x.ptr, x.ld, out.ptr, out.ld, *mp(out_copy), out.rows,
+        self.lib.call(name, a.ptr, a.ld, W.ptr, W.ld, b.data_ptr(), x.ptr, x.ld, out.ptr, out.ld, *_mp(out_copy), out.rows,
                       W.rows, out.cols, self.stream)
 
     def rnn_gru_step(self, h_prev, Ug, bg, Uh, bh, xg, xh, z, rh, out, out_copy=None, idx=None, mask=None):
@@ -668,12 +675,11 @@ class Engine(object):
         Uh: Mat [H, H], xg: Mat [R, 2 H], xh: Mat [R, H] of the storage type; bg fp32 [2 H], bh fp32 [H]; z (fp32 Mat [R, H])
         and rh (storage-type Mat [R, H]) are the caller's scratch between the two launches."""
         f32 = xh.t.dtype == torch.float32
-        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
-        state = (*mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx))
+        state = _state(h_prev, idx)
         self.lib.call("zk_f32_rnn_gru_gates" if f32 else "zk_rnn_gru_gates", *state, Ug.ptr, Ug.ld, bg.data_ptr(), xg.ptr, xg.ld,
                       z.ptr, z.ld, rh.ptr, rh.ld, out.rows, out.cols, self.stream)
         self.lib.call("zk_f32_rnn_gru_out" if f32 else "zk_rnn_gru_out", rh.ptr, rh.ld, Uh.ptr, Uh.ld, bh.data_ptr(), xh.ptr,
-                      xh.ld, z.ptr, z.ld, *state, *mp(mask), out.ptr, out.ld, *mp(out_copy), out.rows, out.cols, self.stream)
+                      xh.ld, z.ptr, z.ld, *state, *_mp(mask), out.ptr, out.ld, *_mp(out_copy), out.rows, out.cols, self.stream)
 
     def rnn_lrn_scan(self, h_prev, lo, hi, out, seq=None, idx=None, mask=None, T=1, reverse=False, gated=False):
         """rnns/lrn.py:32-53 / rnns/olrn.py:32-58 (gated) with the carry of rnns/rnn.py:41-49, T time steps of one cell (hi
@@ -692,8 +698,7 @@ class Engine(object):
             if isinstance(m, tuple):
                 return (m[0].ptr, int(m[1]), int(m[2]))
             return (m.ptr, m.ld if ps is None else ps, T * m.ld if ps is None else m.ld)
-        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
-        self.lib.call(name, *mp(h_prev), h_prev.rows if h_prev is not None else 0, hip.ptr(idx), *sq(lo), *sq(hi), *sq(mask, 1),
+        self.lib.call(name, *_state(h_prev, idx), *sq(lo), *sq(hi), *sq(mask, 1),
                       out.ptr, out.ld, *sq(seq), out.rows, out.cols, T, 1 if reverse else 0, 1 if gated else 0, self.stream)
 
     def add_attn(self, qa, pm, mem, v, kmask, ctx, ctx_copy, kv_group, Ls):
@@ -717,8 +722,7 @@ class Engine(object):
         """tanh(x + bias) of an fp32 Mat x; input row r -> output rows r rep .. r rep + rep - 1 of out_f32 (fp32 Mat) and /
         or out_copy (Mat of the storage type: fp32 when f32)."""
         name = "zk_f32_rnn_bias_tanh" if f32 else "zk_rnn_bias_tanh"
-        mp = lambda t: (t.ptr, t.ld) if t is not None else (None, 0)
-        self.lib.call(name, x.ptr, x.ld, hip.ptr(bias), *mp(out_f32), *mp(out_copy), x.rows, x.cols, int(rep), self.stream)
+        self.lib.call(name, x.ptr, x.ld, hip.ptr(bias), *_mp(out_f32), *_mp(out_copy), x.rows, x.cols, int(rep), self.stream)
 
     def attn_bwd(self, q, k, v, out, dout, lse, dq, dk, dv, B, nh, Lq, Lk, d, kmask=None, causal=False,
                  rpr_k=None, rpr_v=None, drpr_k=None, drpr_v=None, max_rel=0, drop_p=0.0, sid=0, impl=None,
