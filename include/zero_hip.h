@@ -682,6 +682,21 @@ int zk_shortlist_build(const int* src, int rows, int ld_src, int Ls, const int* 
                        int best, int first, int V, int round, int* ids, int cap, int* count, void* workspace,
                        size_t ws_bytes, zk_stream_t stream);
 
+/* ---- no_repeat_ngram_size (see zk_ngram.hip; the rule is stated in tests/ngram_ref.py): the n-gram ban of a decode step,
+ * between the optional Gumbel noise and the fused search tail (search.py:143-176).
+ *   logits   fp32 [rows, ld], V candidates per row; hist int32 [rows, ldh]: row r has generated y_1 .. y_t, y_i at
+ *            hist[r * ldh + i] (index 0 is the search's start symbol and belongs to no n-gram)
+ *   t        = *time_dev when time_dev != NULL (device memory, read by the kernel: one captured node serves every step),
+ *            else `time`
+ *   Token v is banned when t >= n - 1 and some i with 1 <= i, i + n - 1 <= t has y_i .. y_{i+n-2} == y_{t-n+2} .. y_t and
+ *   v == y_{i+n-1}; n = 1 bans every token generated so far.  logits[r * ld + v] = value for every banned v of row r;
+ *   nothing else is written.  A history token outside [0, V) bans nothing.  Under time_dev a word outside [n - 1, ldh)
+ *   makes the launch a no-op.
+ * Argument errors (nothing launched, every buffer untouched): n outside 1 .. 16; ld < V; rows < 0; with time by value,
+ * time < 0 or ldh <= time.  rows == 0, or time by value below n - 1: returns 0 without a launch. */
+int zk_ngram_ban(float* logits, int ld, int rows, int V, const int* hist, int ldh, int time, const int* time_dev, int n,
+                 float value, zk_stream_t stream);
+
 /* ---- transformer_l0drop at inference (models/transformer_l0drop.py:16-135, 244-273; modules/l0norm.py:75-96, 166-177)
  * A learned hard-concrete gate drops encoder outputs; cross-attention runs over the kept ones plus ONE slot (index 0, a
  * zero key / value) that carries the number of dropped positions as its softmax weight.

@@ -69,6 +69,10 @@ _DEFAULTS = [
     # with the lowest missing ids up to a multiple of shortlist_round (a multiple of 8; the size is part of the step
     # graphs' shape)
     ("shortlist_file", ""), ("shortlist_first", 100), ("shortlist_best", 100), ("shortlist_round", 1024),
+    # build-specific: n-gram blocking inside the decode step (zk_ngram_ban; models/_decode.py search_tail).  n > 0: a
+    # hypothesis never completes an n-gram it already holds -- the step's logits of such tokens are overwritten with the
+    # forbid value BEFORE the log-softmax, so the rest is renormalised; 0 = off, at most 16
+    ("no_repeat_ngram_size", 0),
 ]
 
 

@@ -81,6 +81,8 @@ STEP_GRAPH_CACHE = 24        # shapes per core; least recently used goes first
 
 def _graph_pointers(state, book):
     own = getattr(state, "graph_pointers", None)      # a state that is not a Transformer layer stack names its own
+    if state.get("ngram_hist") is not None:           # the history the n-gram ban reads (the book's seq, or ngram_history)
+        book = (tuple(book) if book is not None else ()) + tuple(state["ngram_hist"])
     if own is not None:
         return tuple(own()) + (tuple(book) if book is not None else ())
     core = state["_core"]
@@ -109,8 +111,9 @@ def _destroy_graphs(core, graphs):
     graphs.clear()
 
 
-def adopt_graphs(state, book, temperature, forbid_value, noise):
-    """First step of a batch: take over the cached parity graphs of its shape, if they are still valid."""
+def adopt_graphs(state, book, temperature, forbid_value, noise, ngram=0):
+    """First step of a batch: take over the cached parity graphs of its shape, if they are still valid.  ngram: the
+    n-gram size of the step's ban node (0: the step has none)."""
     core = state["_core"]
     e = core.eng
     # (zk_dec_group(-1) = the rows-per-workgroup geometry in force: graphs captured with several batches in flight --
@@ -119,6 +122,8 @@ def adopt_graphs(state, book, temperature, forbid_value, noise):
            float(forbid_value), bool(noise), int(e.lib.raw("zk_dec_group")(-1)), bool(state.get("f32")))
     if state.get("shortlist") is not None:      # the size of the output vocabulary is part of a step's shape
         key += (("shortlist", state["shortlist"].Vs),)
+    if ngram > 0:                               # a step with the ban node, and its n, is a launch sequence of its own
+        key += (("ngram", int(ngram)),)
     state["_gkey"] = key
     if os.environ.get("ZERO_HIP_DECODE_GRAPH_CACHE", "1") == "0":
         return
@@ -261,11 +266,60 @@ def vocab_size(state):
     return state["_core"].V if sl is None else sl.Vs
 
 
-def search_tail(state, core, logits, noise, temperature, forbid_value):
+NGRAM_MAX = 16      # zk_ngram_ban compares at most 15 suffix tokens
+
+
+def ngram_size(hp):
+    """hp.no_repeat_ngram_size as an int: 0 = off; ValueError outside 0 .. NGRAM_MAX."""
+    n = getattr(hp, "no_repeat_ngram_size", 0)
+    n = 0 if n is None else int(n)
+    if not 0 <= n <= NGRAM_MAX:
+        raise ValueError("no_repeat_ngram_size=%d: the n-gram ban takes n in 1 .. %d (0 = off)" % (n, NGRAM_MAX))
+    return n
+
+
+def check_ngram(hp, V_eff, Tmax, K):
+    """A banned token must never be among the 2K survivors of a step: a row bans at most one token per generated
+    position, Tmax of them, so V_eff - Tmax candidates are always left.  V_eff: the shortlist size where there is one."""
+    if ngram_size(hp) > 0 and int(V_eff) - int(Tmax) < 2 * int(K):
+        raise ValueError("no_repeat_ngram_size=%d: up to %d tokens of a row can be banned (the cache length), which leaves "
+                         "fewer than 2 * beam_size = %d of the %d candidates per row for the top-2K of a step"
+                         % (ngram_size(hp), Tmax, 2 * K, V_eff))
+
+
+def ngram_history(state, rows, cols):
+    """The n-gram ban's history of a search that keeps its books on the host: an int32 [rows, cols] device buffer under the
+    decode mode's prefix plus a pinned host mirror (search.py refreshes the mirror from its sequences and uploads it next to
+    the step's other inputs).  state["ngram_hist"] = (device address, row stride) is what search_tail launches with and what
+    _graph_pointers compares.  -> (device tensor, pinned host tensor)"""
+    core = state["_core"]
+    st = getattr(state, "storage", BF16_CACHES)
+    own = getattr(state, "graph_pointers", None)
+    name = st.prefix + ("rn." if own is not None else "") + "ngram.hist"
+    dev = core.eng.buf(name, (rows, cols), torch.int32)
+    pins = core.__dict__.setdefault("_decode_pins", {})
+    n = rows * cols
+    host = pins.get("ngram")
+    if host is None or host.numel() < n:
+        host = pins["ngram"] = torch.zeros(n + n // 4, dtype=torch.int32).pin_memory()
+    host = host[:n].view(rows, cols)
+    host.zero_()
+    state["ngram_hist"] = (dev.data_ptr(), cols)
+    return dev, host
+
+
+def ngram_ban(e, logits, rows, V, hist, n, forbid_value, time=0, time_dev=None):
+    """zk_ngram_ban on the step's logits Mat; hist = (device address of the int32 history, its row stride).  forbid_value is
+    the search tail's, dtype.inf() = +1e8 (the tail subtracts it): the ban writes -forbid_value."""
+    e.lib.call("zk_ngram_ban", logits.ptr, logits.ld, rows, V, hist[0], hist[1], int(time),
+               time_dev.data_ptr() if time_dev is not None else None, n, -float(forbid_value), e.stream)
+
+
+def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0):
     """search.py:143-176 (+ 198-228 with the device-resident bookkeeping) on the step's fp32 ``logits`` Mat [B*K, ld]:
-    optional Gumbel noise, then temperature, log-softmax, EOS ban, length penalty and top-2K in the fused tail.  Launches
-    on the current stream with the scratch of ``core``'s engine; shared by the single-model step and the ensemble step
-    (models/_ensemble.py)."""
+    optional Gumbel noise, the n-gram ban (ngram > 0: no_repeat_ngram_size), then temperature, log-softmax, EOS ban, length
+    penalty and top-2K in the fused tail.  Launches on the current stream with the scratch of ``core``'s engine; shared by
+    the single-model step and the ensemble step (models/_ensemble.py)."""
     e = core.eng
     book = state.get("book")
     sb = state["stepbuf"]
@@ -274,6 +328,11 @@ def search_tail(state, core, logits, noise, temperature, forbid_value):
         e.lib.call("zk_add_gumbel", logits.ptr, state["BK"], V, logits.ld, float(zdtype.epsilon()),
                    e.seed.data_ptr(), 7001, e.stream)
         e.lib.call("zk_seed_advance", e.seed.data_ptr(), 1, e.stream)
+    if ngram > 0:
+        # the rows' histories are the search's sequences, in the row order of the logits: the device-resident book's seq
+        # (the previous step's advance wrote the alive rows in the order flat_idx reorders the caches to), or the buffer
+        # the host refreshes (ngram_history); the step's time word is read on the device
+        ngram_ban(e, logits, state["BK"], V, state["ngram_hist"], ngram, forbid_value, time_dev=sb[0:1])
     fused_tail = False
     if book is not None:
         # merge of the chunked top-2K and the alive / finished bookkeeping in one launch
@@ -484,6 +543,8 @@ def build_state(core, hp, model_name, source, K, max_steps):
     st = o.storage
     batch, max_steps = shape_batch(core, hp, source, max_steps)
     B, Ls = batch["B"], batch["Ls"]
+    if not _shortlist.wanted(hp):      # (a shortlist's size is known once it is built: checked below)
+        check_ngram(hp, core.V, max_steps, K)
     # the batch's output vocabulary is built from the source ids while the encoder runs (zero_amd/shortlist.py)
     sl = _shortlist.launch(core, hp, batch["src"], B, Ls, Ls, o.pre) if _shortlist.wanted(hp) else None
     enc, smask = encode(core, hp, batch, o)
@@ -506,6 +567,7 @@ def build_state(core, hp, model_name, source, K, max_steps):
         state["kbias"] = kbias
     if sl is not None:
         state["shortlist"] = _shortlist.finish(core, hp, sl, o)
+        check_ngram(hp, state["shortlist"].Vs, max_steps, K)
     for l in range(nl):
         p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
         kv = o.mat("%d.kv" % l, B * Ls, 2 * H)
@@ -635,15 +697,16 @@ def static_step(state, hp, logits_of, fast_capture, temperature, forbid_value, d
     e = core.eng
     book = state.get("book")          # device-resident search bookkeeping (search._beam_search_device)
     noise = hp.enable_noise_beam_search
+    ngram = ngram_size(hp)
     if "_gkey" not in state:
-        adopt_graphs(state, book, temperature, forbid_value, noise)
+        adopt_graphs(state, book, temperature, forbid_value, noise, ngram)
 
     def body():
         time_dev = state["stepbuf"][0:1]
         if book is not None:
             e.lib.call("zk_beam_dev_prepare", *book, e.stream)
         state.reorder(state["idx"], time_dev=time_dev, defer_aan=defer_aan)
-        search_tail(state, core, logits_of(state, time_dev), noise, temperature, forbid_value)
+        search_tail(state, core, logits_of(state, time_dev), noise, temperature, forbid_value, ngram)
     run_step(state, core, body, fast_capture)
 
 
@@ -651,6 +714,7 @@ def make_infer_fns(params, model_name):
     hp = params
     _shortlist.check(hp, model_name)
     check_search_mode(model_name, hp)
+    ngram_size(hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)

@@ -348,6 +348,7 @@ def build_state(core, hp, source, K, max_steps):
                   "pms": pms, "mask": mask_keep, "time_filled": 0, "decoder": {}, "f32": f32, "_pp": 0})
     if sl is not None:
         state["shortlist"] = _shortlist.finish(core, hp, sl, o)
+    _dec.check_ngram(hp, _dec.vocab_size(state), max_steps, K)
     state.bind_caches()
     return _dec.finish_state(state)
 
@@ -355,6 +356,7 @@ def build_state(core, hp, source, K, max_steps):
 def make_infer_fns(params, model_name):
     hp = params
     from zero_amd.models._factory import get_core
+    _dec.ngram_size(hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)

@@ -120,6 +120,8 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
     d_idx = e.buf("bs.idx", (B * K,), torch.int32)
     mtl_i = max_target_length.astype(np.int32)
     time = 0
+    from zero_amd.models import _decode as _dec
+    ngram = _dec.ngram_size(params)           # no_repeat_ngram_size: zk_ngram_ban ahead of every step's top-2K
     # AAN decoding: the whole step (cache reorder + model + top-2K) has static launch arguments and is
     # replayed as a hipGraph; per-step scalars travel through a small device buffer
     static_step = cache_mode and state.get("static_ok", False) and hasattr(decoding_fn, "step_static") \
@@ -136,6 +138,17 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
         pack[2 * BK:3 * BK] = np.arange(BK, dtype=np.int32)     # step 0: identity reorder
         out_host = state["out_host"]
         out_np = out_host.numpy()
+    if ngram > 0:
+        # the ban's history [B*K, Tcap]: this loop's sequences, uploaded before every step (a captured step reads it and
+        # the time word on the device, an eager one is told the time)
+        Tcap = (int(state["Tmax"]) if cache_mode else int(max_target_length.max()) + 2) + 2
+        if cache_mode:
+            hist_dev, hist_host = _dec.ngram_history(state, B * K, Tcap)
+        else:
+            _dec.check_ngram(params, V, Tcap - 2, K)
+            hist_dev = e.buf("bs.ngram", (B * K, Tcap), torch.int32)
+            hist_host = torch.zeros((B * K, Tcap), dtype=torch.int32)
+        hist_np = hist_host.numpy()
     while True:
         # ---- search.py:85-113
         max_lp = np.power((f32(5.) + max_target_length) / f32(6.), f32(alpha)).astype(f32)
@@ -148,6 +161,11 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
             break
         # ---- model step (search.py:118-142)
         penalty = f32(np.power(f32((f32(5.) + f32(time + 1)) / f32(6.)), f32(alpha)))
+        if ngram > 0:
+            if time + 1 > hist_np.shape[1]:
+                raise RuntimeError("decode step %d exceeds the n-gram history of %d positions" % (time, hist_np.shape[1]))
+            hist_np[:, :time + 1] = seq.reshape(B * K, time + 1)
+            hist_dev.copy_(hist_host, non_blocking=True)
         if static_step:
             if time >= state["Tmax"]:
                 raise RuntimeError("decode step %d exceeds the allocated cache length %d" % (time, state["Tmax"]))
@@ -171,6 +189,8 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
                 e.lib.call("zk_add_gumbel", logits.ptr, B * K, V, logits.ld, float(zdtype.epsilon()),
                            e.seed.data_ptr(), 7001, e.stream)
                 e.lib.call("zk_seed_advance", e.seed.data_ptr(), 1, e.stream)
+            if ngram > 0:
+                _dec.ngram_ban(e, logits, B * K, V, (hist_dev.data_ptr(), hist_np.shape[1]), ngram, zdtype.inf(), time=time)
             d_prev.copy_(torch.from_numpy(log_probs.reshape(-1)))
             e.beam_topk(logits, d_prev, d_ts, d_ti, B, K, V, 2 * K, params.beam_search_temperature, penalty,
                         eos_id if time < 1 else -1, zdtype.inf())
@@ -237,7 +257,15 @@ def _beam_search_static(state, decoding_fn, params, B, K, V, eos_id, pad_id, alp
     lib = core.eng.lib
     BK = B * K
     Tcap = int(state["Tmax"]) + 2
-    seq = np.full((B, K, Tcap), pad_id, dtype=np.int32)
+    from zero_amd.models import _decode as _dec
+    ngram = _dec.ngram_size(params)
+    if ngram > 0:
+        # the alive sequences live in the pinned mirror of the n-gram ban's history: one more async copy beside the pack
+        hist_dev, hist_host = _dec.ngram_history(state, BK, Tcap)
+        seq = hist_host.numpy().reshape(B, K, Tcap)
+        seq[:] = pad_id
+    else:
+        seq = np.full((B, K, Tcap), pad_id, dtype=np.int32)
     fin_seq = np.zeros((B, K, Tcap), dtype=np.int32)
     log_probs = np.tile(np.array([[0.] + [F32_MIN] * (K - 1)], dtype=f32), (B, 1))
     scores = np.zeros((B, K), dtype=f32)
@@ -270,6 +298,8 @@ def _beam_search_static(state, decoding_fn, params, B, K, V, eos_id, pad_id, alp
         pack[3 * BK], pack[3 * BK + 1], pack[3 * BK + 2] = \
             time, int(penalty.view(np.int32)), (eos_id if time < 1 else -1)
         state["pack_dev"].copy_(state["pack_host"], non_blocking=True)
+        if ngram > 0:
+            hist_dev.copy_(hist_host, non_blocking=True)
         decoding_fn.step_static(state, params.beam_search_temperature, zdtype.inf())
         out_host.copy_(state["out_dev"])           # one D2H for scores and indices (synchronises)
         if trace is not None:
@@ -346,9 +376,13 @@ def _beam_search_device(state, decoding_fn, params, B, K, V, eos_id, pad_id, alp
     # two decode steps, and with several batches in flight the lanes' host threads stop serialising on it.
     run_c = True
     from zero_amd.models import _decode as _dec
+    ngram = _dec.ngram_size(params)
+    if ngram > 0:
+        # the n-gram ban reads the book's alive sequences: when a step's tail runs, seq[b, k] is row b * K + k of the logits
+        state["ngram_hist"] = (d(8), Tcap)
     if run_c and "_gkey" not in state:
         _dec.adopt_graphs(state, state["book"], params.beam_search_temperature, zdtype.inf(),
-                          params.enable_noise_beam_search)
+                          params.enable_noise_beam_search, ngram)
     stopped = False
     while True:
         if run_c and _dec._startup_settled(state):
