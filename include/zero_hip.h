@@ -697,6 +697,21 @@ int zk_shortlist_build(const int* src, int rows, int ld_src, int Ls, const int* 
 int zk_ngram_ban(float* logits, int ld, int rows, int V, const int* hist, int ldh, int time, const int* time_dev, int n,
                  float value, zk_stream_t stream);
 
+/* ---- sampling_topk / sampling_topp (see zk_sample.hip; the rule is stated in tests/sampling_ref.py): the truncation of a
+ * decode step's logits, after the n-gram ban and before the Gumbel noise and the fused search tail.
+ *   logits   fp32 [rows, ld], V finite candidates per row.  With s = softmax(row), c(v) = #{u : x_u > x_v} and
+ *            M(v) = sum of s_u over x_u > x_v, token v is KEPT iff
+ *              c(v) < min_keep  or  ((topk == 0 or c(v) < topk) and (topp == 0 or M(v) < topp));
+ *            every other entry of the row is overwritten with `value`.  Tokens tied in value share their fate: the kept set
+ *            is {v : x_v >= tau} for one threshold per row, and the result is deterministic (integer sums only).
+ *   Only dropped entries are written; the columns V .. ld-1 never.  One launch, no workspace.  topk == 0 && topp == 0, or
+ *   rows == 0: returns 0 without a launch.  topp == 1 keeps every token.  Rows of at most 32768 candidates are staged in LDS
+ *   and fetched from memory once; longer rows are re-read per pass.
+ * Argument errors (nothing launched, every buffer untouched): ld < V; V < 1; rows < 0; topk < 0; topp outside [0, 1];
+ * min_keep < 1; logits NULL with rows > 0. */
+int zk_sample_truncate(float* logits, int ld, int rows, int V, int topk, float topp, int min_keep, float value,
+                       zk_stream_t stream);
+
 /* ---- transformer_l0drop at inference (models/transformer_l0drop.py:16-135, 244-273; modules/l0norm.py:75-96, 166-177)
  * A learned hard-concrete gate drops encoder outputs; cross-attention runs over the kept ones plus ONE slot (index 0, a
  * zero key / value) that carries the number of dropped positions as its softmax weight.

@@ -73,6 +73,12 @@ _DEFAULTS = [
     # hypothesis never completes an n-gram it already holds -- the step's logits of such tokens are overwritten with the
     # forbid value BEFORE the log-softmax, so the rest is renormalised; 0 = off, at most 16
     ("no_repeat_ngram_size", 0),
+    # build-specific: truncated decoding (zk_sample_truncate; models/_decode.py search_tail; the rule is stated in
+    # tests/sampling_ref.py).  sampling_topk = k > 0: only the k most probable tokens of a beam row survive the step;
+    # sampling_topp = p in (0, 1]: only the smallest set of most probable tokens whose softmax mass reaches p (1.0 keeps
+    # everything).  The other logits are overwritten with the forbid value after the n-gram ban and BEFORE the Gumbel noise
+    # and the log-softmax, so the rest is renormalised; 0 / 0.0 = off
+    ("sampling_topk", 0), ("sampling_topp", 0.0),
 ]
 
 

@@ -26,6 +26,7 @@ through the training-path decoder each step.
 import collections
 import ctypes
 import os
+import struct
 import threading
 
 import numpy as np
@@ -111,19 +112,28 @@ def _destroy_graphs(core, graphs):
     graphs.clear()
 
 
-def adopt_graphs(state, book, temperature, forbid_value, noise, ngram=0):
-    """First step of a batch: take over the cached parity graphs of its shape, if they are still valid.  ngram: the
-    n-gram size of the step's ban node (0: the step has none)."""
-    core = state["_core"]
-    e = core.eng
-    # (zk_dec_group(-1) = the rows-per-workgroup geometry in force: graphs captured with several batches in flight --
-    # 16 rows per workgroup -- must not be adopted by a single-stream decode, nor the reverse)
+def graph_key(state, book, temperature, forbid_value, noise, dec_group, ngram=0, sample=None):
+    """What tells the step graphs of one batch from those of another: the shape, the search's constants and the option set
+    (ngram: the n-gram size of the step's ban node, 0 = none; sample: sampling_opts' pair when the step truncates)."""
     key = (state["B"], state["K"], state["Ls"], state["Tmax"], book is not None, float(temperature),
-           float(forbid_value), bool(noise), int(e.lib.raw("zk_dec_group")(-1)), bool(state.get("f32")))
+           float(forbid_value), bool(noise), int(dec_group), bool(state.get("f32")))
     if state.get("shortlist") is not None:      # the size of the output vocabulary is part of a step's shape
         key += (("shortlist", state["shortlist"].Vs),)
     if ngram > 0:                               # a step with the ban node, and its n, is a launch sequence of its own
         key += (("ngram", int(ngram)),)
+    if sampling_on(sample):                     # so is one with the truncation node, per (k, p): both are launch arguments
+        key += (("sample", int(sample[0]), struct.unpack("<I", struct.pack("<f", float(sample[1])))[0]),)
+    return key
+
+
+def adopt_graphs(state, book, temperature, forbid_value, noise, ngram=0, sample=None):
+    """First step of a batch: take over the cached parity graphs of its shape, if they are still valid.  ngram: the
+    n-gram size of the step's ban node (0: the step has none); sample: sampling_opts(hp) (None / (0, 0.0): no truncation)."""
+    core = state["_core"]
+    e = core.eng
+    # (zk_dec_group(-1) = the rows-per-workgroup geometry in force: graphs captured with several batches in flight --
+    # 16 rows per workgroup -- must not be adopted by a single-stream decode, nor the reverse)
+    key = graph_key(state, book, temperature, forbid_value, noise, e.lib.raw("zk_dec_group")(-1), ngram, sample)
     state["_gkey"] = key
     if os.environ.get("ZERO_HIP_DECODE_GRAPH_CACHE", "1") == "0":
         return
@@ -315,15 +325,73 @@ def ngram_ban(e, logits, rows, V, hist, n, forbid_value, time=0, time_dev=None):
                time_dev.data_ptr() if time_dev is not None else None, n, -float(forbid_value), e.stream)
 
 
-def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0):
+def sampling_opts(hp):
+    """(hp.sampling_topk, hp.sampling_topp) as (int, float): 0 / 0.0 = off; ValueError for a negative k and for p outside
+    [0, 1].  p = 1.0 is an active setting that keeps everything."""
+    k = getattr(hp, "sampling_topk", 0)
+    p = getattr(hp, "sampling_topp", 0.0)
+    k = 0 if k is None else int(k)
+    p = 0.0 if p is None else float(p)
+    if k < 0:
+        raise ValueError("sampling_topk=%d: top-k truncation takes k >= 1 (0 = off)" % k)
+    if not 0.0 <= p <= 1.0:      # (a NaN fails both comparisons)
+        raise ValueError("sampling_topp=%r: nucleus truncation takes p in (0, 1] (0 = off)" % p)
+    return k, p
+
+
+def sampling_on(sample):
+    return sample is not None and (sample[0] > 0 or sample[1] > 0.0)
+
+
+def sampling_min_keep(K):
+    """The entries of a row the truncation always leaves: the top-2K of a step must never have to take an overwritten
+    entry, and at step 0 the tail bans EOS on top."""
+    return 2 * int(K) + 1
+
+
+def check_sampling(hp, V_eff, Tmax, K):
+    """The truncation keeps at least min_keep = 2 * beam_size + 1 entries per row, so a row must have that many -- after the
+    n-gram ban, which takes up to Tmax of them (check_ngram), where both are on.  V_eff: the shortlist size where there is
+    one."""
+    sample = sampling_opts(hp)
+    if not sampling_on(sample):
+        return
+    mk = sampling_min_keep(K)
+    what = "sampling_topk=%d, sampling_topp=%g" % sample
+    if int(V_eff) < mk:
+        raise ValueError("%s: the truncation keeps at least 2 * beam_size + 1 = %d candidates per row for the top-2K of a "
+                         "step, a row has only %d" % (what, mk, V_eff))
+    if ngram_size(hp) > 0 and int(V_eff) - int(Tmax) < mk:
+        raise ValueError("%s with no_repeat_ngram_size=%d: up to %d tokens of a row can be banned (the cache length), which "
+                         "leaves fewer than 2 * beam_size + 1 = %d of the %d candidates per row for the truncation to keep"
+                         % (what, ngram_size(hp), Tmax, mk, V_eff))
+
+
+def sample_truncate(e, logits, rows, V, topk, topp, min_keep, forbid_value):
+    """zk_sample_truncate on the step's logits Mat.  forbid_value is the search tail's, dtype.inf() = +1e8 (the tail subtracts
+    it): the truncation writes -forbid_value, as the n-gram ban does.  With both settings off there is no call."""
+    if int(topk) == 0 and float(topp) == 0.0:
+        return
+    e.lib.call("zk_sample_truncate", logits.ptr, logits.ld, rows, V, int(topk), float(topp), int(min_keep),
+               -float(forbid_value), e.stream)
+
+
+def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0, sample=None):
     """search.py:143-176 (+ 198-228 with the device-resident bookkeeping) on the step's fp32 ``logits`` Mat [B*K, ld]:
     optional Gumbel noise, the n-gram ban (ngram > 0: no_repeat_ngram_size), then temperature, log-softmax, EOS ban, length
-    penalty and top-2K in the fused tail.  Launches on the current stream with the scratch of ``core``'s engine; shared by
-    the single-model step and the ensemble step (models/_ensemble.py)."""
+    penalty and top-2K in the fused tail.  With sample = sampling_opts' pair active (sampling_topk / sampling_topp) the order
+    is n-gram ban, truncation, noise, tail: the noise then draws from the truncated distribution, and banned tokens -- at the
+    forbid value, with mass 0 and the lowest rank -- stay out of the counts and the mass.  Launches on the current stream with
+    the scratch of ``core``'s engine; shared by the single-model step and the ensemble step (models/_ensemble.py)."""
     e = core.eng
     book = state.get("book")
     sb = state["stepbuf"]
     V = vocab_size(state)
+    if sampling_on(sample):
+        if ngram > 0:
+            ngram_ban(e, logits, state["BK"], V, state["ngram_hist"], ngram, forbid_value, time_dev=sb[0:1])
+            ngram = 0
+        sample_truncate(e, logits, state["BK"], V, sample[0], sample[1], sampling_min_keep(state["K"]), forbid_value)
     if noise:      # search.py:143-145; a fresh stream position every step
         e.lib.call("zk_add_gumbel", logits.ptr, state["BK"], V, logits.ld, float(zdtype.epsilon()),
                    e.seed.data_ptr(), 7001, e.stream)
@@ -545,6 +613,7 @@ def build_state(core, hp, model_name, source, K, max_steps):
     B, Ls = batch["B"], batch["Ls"]
     if not _shortlist.wanted(hp):      # (a shortlist's size is known once it is built: checked below)
         check_ngram(hp, core.V, max_steps, K)
+        check_sampling(hp, core.V, max_steps, K)
     # the batch's output vocabulary is built from the source ids while the encoder runs (zero_amd/shortlist.py)
     sl = _shortlist.launch(core, hp, batch["src"], B, Ls, Ls, o.pre) if _shortlist.wanted(hp) else None
     enc, smask = encode(core, hp, batch, o)
@@ -568,6 +637,7 @@ def build_state(core, hp, model_name, source, K, max_steps):
     if sl is not None:
         state["shortlist"] = _shortlist.finish(core, hp, sl, o)
         check_ngram(hp, state["shortlist"].Vs, max_steps, K)
+        check_sampling(hp, state["shortlist"].Vs, max_steps, K)
     for l in range(nl):
         p = "decoder/layer_%d/%s/dot_attention/" % (l, core.cross)
         kv = o.mat("%d.kv" % l, B * Ls, 2 * H)
@@ -688,25 +758,27 @@ def run_step(state, core, body, fast_capture):
         startup_end(state)
 
 
-def static_step(state, hp, logits_of, fast_capture, temperature, forbid_value, defer_aan=False):
+def static_step(state, hp, logits_of, fast_capture, temperature, forbid_value, defer_aan=False, sample=None):
     """One whole decode step with every per-step value read from device memory: the bookkeeping head, the beam reorder of
     the caches (indices chosen by the previous step), the step itself -- logits_of(state, time_dev) -> fp32 logits Mat --
     and the fused log-softmax + length penalty + top-2K, through run_step.  A batch whose state carries no "_gkey" yet
-    first asks the cross-batch cache for the graphs of its shape."""
+    first asks the cross-batch cache for the graphs of its shape.  sample: the truncation's (topk, topp); None = hp's."""
     core = state["_core"]
     e = core.eng
     book = state.get("book")          # device-resident search bookkeeping (search._beam_search_device)
     noise = hp.enable_noise_beam_search
     ngram = ngram_size(hp)
+    if sample is None:
+        sample = sampling_opts(hp)
     if "_gkey" not in state:
-        adopt_graphs(state, book, temperature, forbid_value, noise, ngram)
+        adopt_graphs(state, book, temperature, forbid_value, noise, ngram, sample)
 
     def body():
         time_dev = state["stepbuf"][0:1]
         if book is not None:
             e.lib.call("zk_beam_dev_prepare", *book, e.stream)
         state.reorder(state["idx"], time_dev=time_dev, defer_aan=defer_aan)
-        search_tail(state, core, logits_of(state, time_dev), noise, temperature, forbid_value, ngram)
+        search_tail(state, core, logits_of(state, time_dev), noise, temperature, forbid_value, ngram, sample)
     run_step(state, core, body, fast_capture)
 
 
@@ -715,6 +787,7 @@ def make_infer_fns(params, model_name):
     _shortlist.check(hp, model_name)
     check_search_mode(model_name, hp)
     ngram_size(hp)
+    sampling_opts(hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)

@@ -349,6 +349,7 @@ def build_state(core, hp, source, K, max_steps):
     if sl is not None:
         state["shortlist"] = _shortlist.finish(core, hp, sl, o)
     _dec.check_ngram(hp, _dec.vocab_size(state), max_steps, K)
+    _dec.check_sampling(hp, _dec.vocab_size(state), max_steps, K)
     state.bind_caches()
     return _dec.finish_state(state)
 
@@ -357,6 +358,7 @@ def make_infer_fns(params, model_name):
     hp = params
     from zero_amd.models._factory import get_core
     _dec.ngram_size(hp)
+    _dec.sampling_opts(hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)

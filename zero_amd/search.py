@@ -122,6 +122,9 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
     time = 0
     from zero_amd.models import _decode as _dec
     ngram = _dec.ngram_size(params)           # no_repeat_ngram_size: zk_ngram_ban ahead of every step's top-2K
+    sample = _dec.sampling_opts(params)       # sampling_topk / sampling_topp: zk_sample_truncate ahead of the noise
+    if not cache_mode:                        # (a cached batch was checked by its encoding_fn)
+        _dec.check_sampling(params, V, int(max_target_length.max()) + 2, K)
     # AAN decoding: the whole step (cache reorder + model + top-2K) has static launch arguments and is
     # replayed as a hipGraph; per-step scalars travel through a small device buffer
     static_step = cache_mode and state.get("static_ok", False) and hasattr(decoding_fn, "step_static") \
@@ -185,11 +188,19 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
             logits, state = decoding_fn(decode_target, state, time)
         # ---- fused log-softmax + penalty + top-2K (search.py:143-176)
         if not static_step:
+            ban_left = ngram
+            if _dec.sampling_on(sample):
+                # truncated decoding: n-gram ban, truncation, THEN the noise (models/_decode.py search_tail)
+                if ngram > 0:
+                    _dec.ngram_ban(e, logits, B * K, V, (hist_dev.data_ptr(), hist_np.shape[1]), ngram, zdtype.inf(),
+                                   time=time)
+                    ban_left = 0
+                _dec.sample_truncate(e, logits, B * K, V, sample[0], sample[1], _dec.sampling_min_keep(K), zdtype.inf())
             if params.enable_noise_beam_search:      # search.py:143-145
                 e.lib.call("zk_add_gumbel", logits.ptr, B * K, V, logits.ld, float(zdtype.epsilon()),
                            e.seed.data_ptr(), 7001, e.stream)
                 e.lib.call("zk_seed_advance", e.seed.data_ptr(), 1, e.stream)
-            if ngram > 0:
+            if ban_left > 0:
                 _dec.ngram_ban(e, logits, B * K, V, (hist_dev.data_ptr(), hist_np.shape[1]), ngram, zdtype.inf(), time=time)
             d_prev.copy_(torch.from_numpy(log_probs.reshape(-1)))
             e.beam_topk(logits, d_prev, d_ts, d_ti, B, K, V, 2 * K, params.beam_search_temperature, penalty,
@@ -382,7 +393,7 @@ def _beam_search_device(state, decoding_fn, params, B, K, V, eos_id, pad_id, alp
         state["ngram_hist"] = (d(8), Tcap)
     if run_c and "_gkey" not in state:
         _dec.adopt_graphs(state, state["book"], params.beam_search_temperature, zdtype.inf(),
-                          params.enable_noise_beam_search, ngram)
+                          params.enable_noise_beam_search, ngram, _dec.sampling_opts(params))
     stopped = False
     while True:
         if run_c and _dec._startup_settled(state):
