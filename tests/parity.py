@@ -186,12 +186,13 @@ def pairwise(factors, valid=lambda row: True):
     rows = [dict(zip(names, lv)) for lv in itertools.product(*(factors[n] for n in names))]
     rows = [r for r in rows if valid(r)]
     pairs = lambda r: {(n1, repr(r[n1]), n2, repr(r[n2])) for n1, n2 in itertools.combinations(names, 2)}
-    todo = set().union(*(pairs(r) for r in rows))
+    of = [pairs(r) for r in rows]                   # (once per row: the same rows in the same order as recomputing them)
+    todo = set().union(*of)
     out = []
     while todo:
-        best = max(rows, key=lambda r: len(pairs(r) & todo))
-        out.append(best)
-        todo -= pairs(best)
+        best = max(range(len(rows)), key=lambda i: len(of[i] & todo))
+        out.append(rows[best])
+        todo -= of[best]
     return out
 
 
@@ -412,7 +413,7 @@ def assert_exact(got, ref64, what):
                              "got %r ref %r" % (what, n, got.numel(), r, c, float(got[r, c]), float(ref64[r, c])))
 
 
-def ln_fwd_bound(x, y, scale, gamma, beta, eps, s_stored=None):
+def ln_fwd_bound(x, y, scale, gamma, beta, eps, s_stored=None, e=None):
     """zk_add_ln_fwd (zk_ln_dev.h add_ln_fwd_row): s = x + y * scale (bf16 when saved), out = gamma (s - mean) rstd +
     beta.  x, y: the bf16 operands [rows, H] (y may be None), scale: what zk_dropout_mask gives for the seed and site
     (None = no dropout), s_stored: the sum the KERNEL saved (None = the inference form).  A STAGED reference: returns
@@ -435,7 +436,10 @@ def ln_fwd_bound(x, y, scale, gamma, beta, eps, s_stored=None):
     that is (H + 6) / 2 + RSQRT_ULP + 4 <= H + 5 units for H >= 8, on mean|v| H + 1 half-units, on |beta| one:
         bound_out = 2^-8 |ref| + (H + C_LN) PER_TERM (|gamma| rstd (|v - mu| + mean|v|) + |beta|)
                     + |gamma| rstd (mean(e) + e + |v - mu| (dm2 + ...) / (2 (var + eps)))
-    (the last line is second order with a saved sum).  C_LN = 8 covers each of these counts and is not tuned."""
+    (the last line is second order with a saved sum).  C_LN = 8 covers each of these counts and is not tuned.
+    e (inference form only; [rows, H]): the caller's own bound on |v - (x + y scale)| in place of 2 PER_TERM (|x| + |y scale|),
+    for a y that is itself a reference with an error (the product inside zk_gemm_add_ln, tests/chain_ref.py).  None: as
+    above, bit for bit."""
     x = _d(x)
     H = x.shape[1]
     zero = torch.zeros_like(x)
@@ -450,7 +454,7 @@ def ln_fwd_bound(x, y, scale, gamma, beta, eps, s_stored=None):
         res["s"] = (s_ref, s_bound)
         v, e = _d(s_stored), zero
     else:
-        v, e = s_ref, 2 * PER_TERM * mag
+        v, e = s_ref, (2 * PER_TERM * mag if e is None else _d(e).reshape(x.shape))
     g, b = _d(gamma)[None], _d(beta)[None]
     mu, ma = v.mean(1), v.abs().mean(1)
     lin = (H + C_LN) * PER_TERM
