@@ -712,6 +712,23 @@ int zk_ngram_ban(float* logits, int ld, int rows, int V, const int* hist, int ld
 int zk_sample_truncate(float* logits, int ld, int rows, int V, int topk, float topp, int min_keep, float value,
                        zk_stream_t stream);
 
+/* ---- diverse_beam_groups / diverse_beam_strength (see zk_diverse.hip; the rule is stated in tests/diverse_ref.py): the
+ * group selection of a decode step under diverse beam search.  The K rows of a sentence are G groups of K/G consecutive rows.
+ *   cand_scores / cand_index   fp32 / int32 [B*K, k2]: every row's k2 best (score, token), best first -- zk_beam_topk with
+ *            B*K "sentences" of beam 1, so the score is (prev + logp) / length_penalty and the index the token.
+ *   topk_scores / topk_index   fp32 / int32 [B*G, 2K/G]: per group, in the order g = 0 .. G-1, the 2K/G best of its K/G * k2
+ *            candidates under score - lambda * cnt(v) / length_penalty, where cnt(v) is how often the groups before it counted
+ *            token v in this step; ties go to the lower index = beam_in_group * V + v.  A group counts the tokens, EOS
+ *            (eos_id) excepted, of its K/G best picks.
+ *   length_penalty by value, or read from penalty_dev (a device float, stepbuf + 1) at run time when that is not NULL.
+ * One launch, one wave per sentence, no workspace, no atomics.  B == 0: returns 0 without a launch.
+ * Argument errors (-1, nothing launched, every buffer untouched): B < 0; K, G or V < 1; K % G != 0; k2 outside 2 .. 16;
+ * K/G * k2 > 128; (G-1) * K/G > 64; K/G * V >= INT_MAX; lambda negative or not finite; length_penalty not positive and finite
+ * with penalty_dev NULL; a NULL buffer with B > 0. */
+int zk_diverse_select(const float* cand_scores, const int* cand_index, float* topk_scores, int* topk_index, int B, int K,
+                      int G, int k2, int V, float lambda, float length_penalty, const float* penalty_dev, int eos_id,
+                      zk_stream_t stream);
+
 /* ---- transformer_l0drop at inference (models/transformer_l0drop.py:16-135, 244-273; modules/l0norm.py:75-96, 166-177)
  * A learned hard-concrete gate drops encoder outputs; cross-attention runs over the kept ones plus ONE slot (index 0, a
  * zero key / value) that carries the number of dropped positions as its softmax weight.

@@ -79,6 +79,13 @@ _DEFAULTS = [
     # everything).  The other logits are overwritten with the forbid value after the n-gram ban and BEFORE the Gumbel noise
     # and the log-softmax, so the rest is renormalised; 0 / 0.0 = off
     ("sampling_topk", 0), ("sampling_topp", 0.0),
+    # build-specific: diverse beam search (zk_diverse_select; models/_decode.py search_tail; the rule is stated in
+    # tests/diverse_ref.py).  diverse_beam_groups = G > 1: the beam_size rows of a sentence are G groups of beam_size / G,
+    # each a beam search of its own; within a step group g sees every candidate's score -- the normalised
+    # (prev + logp) / length_penalty -- lowered by diverse_beam_strength (lambda >= 0) * cnt(v) / length_penalty, cnt(v) being
+    # how often the groups before it chose token v in this step.  beam_size % G == 0 and beam_size + beam_size / G <= 16;
+    # 1 = off (the strength is then ignored)
+    ("diverse_beam_groups", 1), ("diverse_beam_strength", 0.5),
 ]
 
 

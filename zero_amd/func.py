@@ -864,6 +864,13 @@ class Engine(object):
                       logits.ld, k2, float(temperature), float(penalty), int(forbid_id), float(forbid_value),
                       hip.ptr(scal_dev), ws.data_ptr(), ws.numel(), self.stream)
 
+    def diverse_select(self, cand_s, cand_i, out_s, out_i, B, K, G, k2, V, strength, penalty, eos_id, penalty_dev=None):
+        """The group selection of a diverse-beam step (zk_diverse_select, include/zero_hip.h): the per-row candidate lists
+        fp32 / int32 [B*K, k2] -> out_s / out_i [B*G, 2K/G].  penalty_dev: a device float that holds the length penalty."""
+        self.lib.call("zk_diverse_select", cand_s.data_ptr(), cand_i.data_ptr(), out_s.data_ptr(), out_i.data_ptr(), int(B),
+                      int(K), int(G), int(k2), int(V), float(strength), float(penalty), hip.ptr(penalty_dev), int(eos_id),
+                      self.stream)
+
     def shortlist_build(self, src, rows, ld_src, Ls, lex_off, lex_ids, best, first, V, round_to, ids, count, workspace=None):
         """The per-batch output vocabulary (zk_shortlist_build, include/zero_hip.h): src int32 [rows, ld_src] source ids,
         lex_off / lex_ids the lexical table as CSR -> ids int32 [cap] (the set ascending, -1 behind) and count int32 [2] =

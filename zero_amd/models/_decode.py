@@ -112,9 +112,14 @@ def _destroy_graphs(core, graphs):
     graphs.clear()
 
 
-def graph_key(state, book, temperature, forbid_value, noise, dec_group, ngram=0, sample=None):
+def _f32_bits(x):
+    return struct.unpack("<I", struct.pack("<f", float(x)))[0]
+
+
+def graph_key(state, book, temperature, forbid_value, noise, dec_group, ngram=0, sample=None, diverse=None):
     """What tells the step graphs of one batch from those of another: the shape, the search's constants and the option set
-    (ngram: the n-gram size of the step's ban node, 0 = none; sample: sampling_opts' pair when the step truncates)."""
+    (ngram: the n-gram size of the step's ban node, 0 = none; sample: sampling_opts' pair when the step truncates; diverse:
+    diverse_opts' pair when the step selects per beam group)."""
     key = (state["B"], state["K"], state["Ls"], state["Tmax"], book is not None, float(temperature),
            float(forbid_value), bool(noise), int(dec_group), bool(state.get("f32")))
     if state.get("shortlist") is not None:      # the size of the output vocabulary is part of a step's shape
@@ -122,18 +127,21 @@ def graph_key(state, book, temperature, forbid_value, noise, dec_group, ngram=0,
     if ngram > 0:                               # a step with the ban node, and its n, is a launch sequence of its own
         key += (("ngram", int(ngram)),)
     if sampling_on(sample):                     # so is one with the truncation node, per (k, p): both are launch arguments
-        key += (("sample", int(sample[0]), struct.unpack("<I", struct.pack("<f", float(sample[1])))[0]),)
+        key += (("sample", int(sample[0]), _f32_bits(sample[1])),)
+    if diverse_on(diverse):                     # and one with the group selection, per (G, lambda): launch arguments too
+        key += (("diverse", int(diverse[0]), _f32_bits(diverse[1])),)
     return key
 
 
-def adopt_graphs(state, book, temperature, forbid_value, noise, ngram=0, sample=None):
+def adopt_graphs(state, book, temperature, forbid_value, noise, ngram=0, sample=None, diverse=None):
     """First step of a batch: take over the cached parity graphs of its shape, if they are still valid.  ngram: the
-    n-gram size of the step's ban node (0: the step has none); sample: sampling_opts(hp) (None / (0, 0.0): no truncation)."""
+    n-gram size of the step's ban node (0: the step has none); sample: sampling_opts(hp) (None / (0, 0.0): no truncation);
+    diverse: diverse_opts(hp) (None / G = 1: the fused tail)."""
     core = state["_core"]
     e = core.eng
     # (zk_dec_group(-1) = the rows-per-workgroup geometry in force: graphs captured with several batches in flight --
     # 16 rows per workgroup -- must not be adopted by a single-stream decode, nor the reverse)
-    key = graph_key(state, book, temperature, forbid_value, noise, e.lib.raw("zk_dec_group")(-1), ngram, sample)
+    key = graph_key(state, book, temperature, forbid_value, noise, e.lib.raw("zk_dec_group")(-1), ngram, sample, diverse)
     state["_gkey"] = key
     if os.environ.get("ZERO_HIP_DECODE_GRAPH_CACHE", "1") == "0":
         return
@@ -376,12 +384,46 @@ def sample_truncate(e, logits, rows, V, topk, topp, min_keep, forbid_value):
                -float(forbid_value), e.stream)
 
 
-def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0, sample=None):
+DIVERSE_DEPTH_MAX = 16      # the deepest candidate list zk_beam_topk returns per row (TOPK_MAX of zk_decode.hip)
+
+
+def diverse_opts(hp, K=None):
+    """(hp.diverse_beam_groups, hp.diverse_beam_strength) as (int G, float lambda) for beam size K (default hp.beam_size);
+    G = 1 = off, and the strength is then ignored: (1, 0.0).  ValueError, in this order, for G < 1, a beam size that is no
+    multiple of G, a negative or non-finite strength, and beam_size + beam_size / G > DIVERSE_DEPTH_MAX (the depth of the
+    per-row candidate lists from which a group's selection is exact, see search_tail)."""
+    G = getattr(hp, "diverse_beam_groups", 1)
+    lam = getattr(hp, "diverse_beam_strength", 0.5)
+    G = 1 if G is None else int(G)
+    lam = 0.5 if lam is None else float(lam)
+    K = int(hp.beam_size if K is None else K)
+    if G < 1:
+        raise ValueError("diverse_beam_groups=%d: diverse beam search takes G >= 2 groups (1 = off)" % G)
+    if G == 1:
+        return 1, 0.0
+    if K % G != 0:
+        raise ValueError("diverse_beam_groups=%d: beam_size=%d is no multiple of the number of groups" % (G, K))
+    if not 0.0 <= lam < float("inf"):      # (a NaN fails both comparisons)
+        raise ValueError("diverse_beam_strength=%r: the Hamming penalty takes a finite strength >= 0" % lam)
+    if K + K // G > DIVERSE_DEPTH_MAX:
+        raise ValueError("diverse_beam_groups=%d with beam_size=%d: the step needs beam_size + beam_size / G = %d + %d = %d "
+                         "candidates per beam row, the per-row top-k returns at most %d"
+                         % (G, K, K, K // G, K + K // G, DIVERSE_DEPTH_MAX))
+    return G, lam
+
+
+def diverse_on(diverse):
+    return diverse is not None and diverse[0] > 1
+
+
+def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0, sample=None, diverse=None):
     """search.py:143-176 (+ 198-228 with the device-resident bookkeeping) on the step's fp32 ``logits`` Mat [B*K, ld]:
     optional Gumbel noise, the n-gram ban (ngram > 0: no_repeat_ngram_size), then temperature, log-softmax, EOS ban, length
     penalty and top-2K in the fused tail.  With sample = sampling_opts' pair active (sampling_topk / sampling_topp) the order
     is n-gram ban, truncation, noise, tail: the noise then draws from the truncated distribution, and banned tokens -- at the
-    forbid value, with mass 0 and the lowest rank -- stay out of the counts and the mass.  Launches on the current stream with
+    forbid value, with mass 0 and the lowest rank -- stay out of the counts and the mass.  With diverse = (G, lambda, eos_id),
+    G > 1 (diverse_opts + the EOS id: diverse_beam_groups / diverse_beam_strength), the fused tail is replaced by the per-row
+    top-k, zk_diverse_select and the bookkeeping on B*G pseudo-sentences (below).  Launches on the current stream with
     the scratch of ``core``'s engine; shared by the single-model step and the ensemble step (models/_ensemble.py)."""
     e = core.eng
     book = state.get("book")
@@ -401,6 +443,24 @@ def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0, 
         # (the previous step's advance wrote the alive rows in the order flat_idx reorders the caches to), or the buffer
         # the host refreshes (ngram_history); the step's time word is read on the device
         ngram_ban(e, logits, state["BK"], V, state["ngram_hist"], ngram, forbid_value, time_dev=sb[0:1])
+    if diverse_on(diverse):
+        # Diverse beam search: three launches instead of the fused tail.  (1) zk_beam_topk with B*K "sentences" of beam 1:
+        # every row's k2 = K + K/G best (score, token).  That depth is exact: a kept candidate with an unpenalised token has
+        # fewer than 2K/G unpenalised and at most (G-1) K/G penalised entries of its row above it, and a penalised one below
+        # the row's top k2 has at least 2K/G + 1 unpenalised ones above it.  (2) zk_diverse_select: per group, in order, the
+        # 2K/G best under the Hamming penalty.  (3) the unchanged bookkeeping on (B*G, K/G): the book was built with these
+        # sizes (search.py), and the flat row indices of the pseudo-sentences are the model's.
+        G, lam, eos_id = diverse
+        K, BK = state["K"], state["BK"]
+        k2 = K + K // G
+        assert k2 <= 2 * K        # check_ngram / check_sampling leave 2K (2K + 1) candidates per row: enough for the lists
+        cs = e.buf("bs.dv.s", (BK, k2), F32)
+        ci = e.buf("bs.dv.i", (BK, k2), torch.int32)
+        e.beam_topk(logits, state["prev"], cs, ci, BK, 1, V, k2, temperature, 1.0, -1, forbid_value, scal_dev=sb[1:3])
+        e.diverse_select(cs, ci, state["ts"], state["ti"], state["B"], K, G, k2, V, lam, 1.0, eos_id, penalty_dev=sb[1:2])
+        if book is not None:
+            e.lib.call("zk_beam_dev_advance", *book, e.stream)
+        return
     fused_tail = False
     if book is not None:
         # merge of the chunked top-2K and the alive / finished bookkeeping in one launch
@@ -770,15 +830,18 @@ def static_step(state, hp, logits_of, fast_capture, temperature, forbid_value, d
     ngram = ngram_size(hp)
     if sample is None:
         sample = sampling_opts(hp)
+    diverse = diverse_opts(hp, state["K"])
     if "_gkey" not in state:
-        adopt_graphs(state, book, temperature, forbid_value, noise, ngram, sample)
+        adopt_graphs(state, book, temperature, forbid_value, noise, ngram, sample, diverse)
+    if diverse_on(diverse):
+        diverse = diverse + (hp.tgt_vocab.eos(),)
 
     def body():
         time_dev = state["stepbuf"][0:1]
         if book is not None:
             e.lib.call("zk_beam_dev_prepare", *book, e.stream)
         state.reorder(state["idx"], time_dev=time_dev, defer_aan=defer_aan)
-        search_tail(state, core, logits_of(state, time_dev), noise, temperature, forbid_value, ngram, sample)
+        search_tail(state, core, logits_of(state, time_dev), noise, temperature, forbid_value, ngram, sample, diverse)
     run_step(state, core, body, fast_capture)
 
 
@@ -788,6 +851,7 @@ def make_infer_fns(params, model_name):
     check_search_mode(model_name, hp)
     ngram_size(hp)
     sampling_opts(hp)
+    diverse_opts(hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)

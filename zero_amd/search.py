@@ -32,6 +32,17 @@ def _top_k(x, k):
     return np.take_along_axis(x, idx, axis=-1), idx
 
 
+def merge_groups(seqs, scores, G):
+    """Diverse beam search, the end of a search: the hypotheses [B*G, K/G, T] and scores [B*G, K/G] of the G groups of every
+    sentence as one n-best list [B, K, T] / [B, K], sorted by score, descending and stable in group order."""
+    if G <= 1:
+        return seqs, scores
+    B, n = scores.shape[0] // G, G * scores.shape[1]
+    s = scores.reshape(B, n)
+    order = np.argsort(-s.astype(np.float64), axis=1, kind="stable")
+    return np.take_along_axis(seqs.reshape(B, n, -1), order[:, :, None], axis=1), np.take_along_axis(s, order, axis=1)
+
+
 def beam_search(features, encoding_fn, decoding_fn, params):
     """search.py:19-275.  Runs on the engine's work stream (decode-step graphs cannot be captured on
     the legacy default stream)."""
@@ -74,6 +85,8 @@ def _beam_search(features, encoding_fn, decoding_fn, params):
 def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
     f32 = np.float32
     K = params.beam_size
+    from zero_amd.models import _decode as _dec
+    G, strength = _dec.diverse_opts(params, K)      # diverse_beam_groups / diverse_beam_strength; refused before a core exists
     alpha = params.decode_alpha
     eos_id = params.tgt_vocab.eos()
     pad_id = params.tgt_vocab.pad()
@@ -87,7 +100,6 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
     if cache_mode:
         # start-up (allocations, pinned staging, the two graph captures) is serialised between concurrent batches
         # (models/_decode.py STARTUP_LOCK); step_static releases it once both step graphs exist, _beam_search at the end
-        from zero_amd.models import _decode as _dec
         _dec.startup_begin()
         try:
             state = encoding_fn(source, beam_size=K,
@@ -105,6 +117,14 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
         state = np.repeat(src_np, K, axis=0)      # expand_tile_dims of the raw source
     e = core.eng
     dev = e.device
+    Kall = K
+    if G > 1:
+        # Diverse beam search: every group is a beam search of its own, so from here on the bookkeeping sees B * G
+        # pseudo-sentences s = b * G + g of K / G beams each.  Their flat row indices are the model's (row b K + g K/G + j is
+        # beam j of group g): cache reorders, n-gram histories and the packed step inputs need no remapping.  Only the
+        # step's selection knows the groups (models/_decode.py search_tail), and the end merges them (merge_groups).
+        B, K = B * G, K // G
+        max_target_length = np.repeat(max_target_length, G)
 
     log_probs = np.tile(np.array([[0.] + [F32_MIN] * (K - 1)], dtype=f32), (B, 1))
     scores = np.zeros_like(log_probs)
@@ -120,11 +140,10 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
     d_idx = e.buf("bs.idx", (B * K,), torch.int32)
     mtl_i = max_target_length.astype(np.int32)
     time = 0
-    from zero_amd.models import _decode as _dec
     ngram = _dec.ngram_size(params)           # no_repeat_ngram_size: zk_ngram_ban ahead of every step's top-2K
     sample = _dec.sampling_opts(params)       # sampling_topk / sampling_topp: zk_sample_truncate ahead of the noise
     if not cache_mode:                        # (a cached batch was checked by its encoding_fn)
-        _dec.check_sampling(params, V, int(max_target_length.max()) + 2, K)
+        _dec.check_sampling(params, V, int(max_target_length.max()) + 2, Kall)
     # AAN decoding: the whole step (cache reorder + model + top-2K) has static launch arguments and is
     # replayed as a hipGraph; per-step scalars travel through a small device buffer
     static_step = cache_mode and state.get("static_ok", False) and hasattr(decoding_fn, "step_static") \
@@ -133,8 +152,11 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
         Tcap = int(state["Tmax"]) + 2
         if os.environ.get("ZERO_HIP_DECODE_DEVICE_BOOK", "1") != "0" and 2 * K * Tcap * 4 <= 64 * 1024 \
                 and getattr(params, "search_trace", None) is None:
-            return _beam_search_device(state, decoding_fn, params, B, K, V, eos_id, pad_id, alpha, max_target_length)
-        return _beam_search_static(state, decoding_fn, params, B, K, V, eos_id, pad_id, alpha, max_target_length)
+            out = _beam_search_device(state, decoding_fn, params, B, K, V, eos_id, pad_id, alpha, max_target_length)
+        else:
+            out = _beam_search_static(state, decoding_fn, params, B, K, V, eos_id, pad_id, alpha, max_target_length)
+        out["seq"], out["score"] = merge_groups(out["seq"], out["score"], G)
+        return out
     if static_step:
         BK = B * K
         pack = state["pack_host"].numpy()             # pinned; shares memory with the tensor
@@ -148,7 +170,7 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
         if cache_mode:
             hist_dev, hist_host = _dec.ngram_history(state, B * K, Tcap)
         else:
-            _dec.check_ngram(params, V, Tcap - 2, K)
+            _dec.check_ngram(params, V, Tcap - 2, Kall)
             hist_dev = e.buf("bs.ngram", (B * K, Tcap), torch.int32)
             hist_host = torch.zeros((B * K, Tcap), dtype=torch.int32)
         hist_np = hist_host.numpy()
@@ -195,7 +217,9 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
                     _dec.ngram_ban(e, logits, B * K, V, (hist_dev.data_ptr(), hist_np.shape[1]), ngram, zdtype.inf(),
                                    time=time)
                     ban_left = 0
-                _dec.sample_truncate(e, logits, B * K, V, sample[0], sample[1], _dec.sampling_min_keep(K), zdtype.inf())
+                # (min_keep from the sentence's whole beam, as the captured step's: with groups K here is K / G, and the
+                # per-row lists of depth K + K/G need that many real candidates)
+                _dec.sample_truncate(e, logits, B * K, V, sample[0], sample[1], _dec.sampling_min_keep(Kall), zdtype.inf())
             if params.enable_noise_beam_search:      # search.py:143-145
                 e.lib.call("zk_add_gumbel", logits.ptr, B * K, V, logits.ld, float(zdtype.epsilon()),
                            e.seed.data_ptr(), 7001, e.stream)
@@ -203,12 +227,21 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
             if ban_left > 0:
                 _dec.ngram_ban(e, logits, B * K, V, (hist_dev.data_ptr(), hist_np.shape[1]), ngram, zdtype.inf(), time=time)
             d_prev.copy_(torch.from_numpy(log_probs.reshape(-1)))
-            e.beam_topk(logits, d_prev, d_ts, d_ti, B, K, V, 2 * K, params.beam_search_temperature, penalty,
-                        eos_id if time < 1 else -1, zdtype.inf())
+            if G > 1:
+                # per-row candidates, the group selection (models/_decode.py search_tail), then the bookkeeping below
+                k2 = Kall + K
+                d_cs = e.buf("bs.dv.s", (B * K, k2), torch.float32)
+                d_ci = e.buf("bs.dv.i", (B * K, k2), torch.int32)
+                e.beam_topk(logits, d_prev, d_cs, d_ci, B * K, 1, V, k2, params.beam_search_temperature, penalty,
+                            eos_id if time < 1 else -1, zdtype.inf())
+                e.diverse_select(d_cs, d_ci, d_ts, d_ti, B // G, Kall, G, k2, V, strength, penalty, eos_id)
+            else:
+                e.beam_topk(logits, d_prev, d_ts, d_ti, B, K, V, 2 * K, params.beam_search_temperature, penalty,
+                            eos_id if time < 1 else -1, zdtype.inf())
         if static_step:
             out_host.copy_(state["out_dev"])           # one D2H for scores and indices (synchronises)
-            topk_scores = out_np[0].view(f32).copy()
-            topk_idx = out_np[1].astype(np.int64)
+            topk_scores = out_np[0].view(f32).reshape(B, 2 * K).copy()
+            topk_idx = out_np[1].reshape(B, 2 * K).astype(np.int64)
         else:
             topk_scores = d_ts.cpu().numpy().astype(f32)
             topk_idx = d_ti.cpu().numpy().astype(np.int64)
@@ -247,6 +280,7 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
     any_fin = fin_flags.any(axis=1)
     final_seqs = np.where(any_fin[:, None, None], fin_seq, seq)
     final_scores = np.where(any_fin[:, None], fin_scores, scores)
+    final_seqs, final_scores = merge_groups(final_seqs, final_scores, G)
     return {"seq": final_seqs[:, :, 1:], "score": final_scores, "steps": time}
 
 
@@ -393,7 +427,8 @@ def _beam_search_device(state, decoding_fn, params, B, K, V, eos_id, pad_id, alp
         state["ngram_hist"] = (d(8), Tcap)
     if run_c and "_gkey" not in state:
         _dec.adopt_graphs(state, state["book"], params.beam_search_temperature, zdtype.inf(),
-                          params.enable_noise_beam_search, ngram, _dec.sampling_opts(params))
+                          params.enable_noise_beam_search, ngram, _dec.sampling_opts(params),
+                          _dec.diverse_opts(params, state["K"]))
     stopped = False
     while True:
         if run_c and _dec._startup_settled(state):
