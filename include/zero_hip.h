@@ -697,6 +697,21 @@ int zk_shortlist_build(const int* src, int rows, int ld_src, int Ls, const int* 
 int zk_ngram_ban(float* logits, int ld, int rows, int V, const int* hist, int ldh, int time, const int* time_dev, int n,
                  float value, zk_stream_t stream);
 
+/* ---- tgt_prefix_file (see zk_prefix.hip; the rule is stated in tests/prefix_ref.py): the forced target prefix of a decode
+ * step, the last launch ahead of the search tail (search.py:143-176), after the n-gram ban, the truncation and the noise.
+ *   logits   fp32 [rows, ld], V candidates per row; prefix int32 [rows / rows_per_sentence, ldp], right-padded with 0: the
+ *            token sentence b must emit at step t is prefix[b * ldp + t]
+ *   t        = *time_dev when time_dev != NULL (device memory, read by the kernel: one captured node serves every step),
+ *            else `time`
+ *   Row r (sentence r / rows_per_sentence) is forced when 0 <= t < ldp and its token p is in [1, V):
+ *   logits[r * ld + v] = value for every v < V but p and eos_id, 2 * value for v == eos_id (eos_id < 0: no such entry);
+ *   logits[r * ld + p] and the columns V .. ld - 1 are not written, and the row is never read.  A row that is not forced is
+ *   not written at all.  ld need not be a multiple of 4 and a row base need not be 16-byte aligned.
+ * Argument errors (nothing launched, every buffer untouched): ld < V; rows < 0; rows % rows_per_sentence != 0; ldp < 1;
+ * with time by value, time < 0.  rows == 0, or time by value >= ldp: returns 0 without a launch. */
+int zk_prefix_force(float* logits, int ld, int rows, int V, const int* prefix, int ldp, int rows_per_sentence, int time,
+                    const int* time_dev, int eos_id, float value, zk_stream_t stream);
+
 /* ---- sampling_topk / sampling_topp (see zk_sample.hip; the rule is stated in tests/sampling_ref.py): the truncation of a
  * decode step's logits, after the n-gram ban and before the Gumbel noise and the fused search tail.
  *   logits   fp32 [rows, ld], V finite candidates per row.  With s = softmax(row), c(v) = #{u : x_u > x_v} and

@@ -86,6 +86,12 @@ _DEFAULTS = [
     # how often the groups before it chose token v in this step.  beam_size % G == 0 and beam_size + beam_size / G <= 16;
     # 1 = off (the strength is then ignored)
     ("diverse_beam_groups", 1), ("diverse_beam_strength", 0.5),
+    # build-specific: forced target prefixes (zk_prefix_force; models/_decode.py search_tail; the rule is stated in
+    # tests/prefix_ref.py).  A file parallel to src_test_file, one line of target tokens per source line (an empty line: no
+    # prefix): every hypothesis of that sentence starts with them.  While a prefix lasts, every other logit of the step is
+    # overwritten with the forbid value BEFORE the log-softmax, so a forced token scores exactly 0 and a hypothesis' score
+    # is log P(continuation | prefix); "" = off.  Not together with shortlist_file
+    ("tgt_prefix_file", ""),
 ]
 
 

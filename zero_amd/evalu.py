@@ -160,10 +160,38 @@ def decode_many(items, work, streams=None, each_lane=False):
     return [results[k] for k in range(counter[0])]
 
 
-def decoding(graph, dataset, params, infer=None, streams=None):
+def load_prefixes(src_file, prefix_file, tgt_vocab, max_len=100):
+    """tgt_prefix_file: one line of target tokens per line of ``src_file`` (an empty line: no prefix) -> a list of id lists
+    that ``data['index']`` of the test set's batches indexes.  Dataset.load_data skips blank source lines and numbers what is
+    left; both files are read together here and the same lines skipped.  Tokens go through ``tgt_vocab.to_id`` (an unknown
+    word is forced as UNK), without the end-of-sentence id.  ValueError for files of different line counts."""
+    with open(src_file, 'r') as sr, open(prefix_file, 'r') as pr:
+        src_lines, prefix_lines = sr.readlines(), pr.readlines()
+    if len(src_lines) != len(prefix_lines):
+        raise ValueError("tgt_prefix_file %s has %d lines, src_test_file %s has %d: one prefix line (possibly empty) per "
+                         "source line is expected" % (prefix_file, len(prefix_lines), src_file, len(src_lines)))
+    out = []
+    for s, p in zip(src_lines, prefix_lines):
+        if s.strip() == "":
+            continue
+        out.append(tgt_vocab.to_id(p.strip().split()[:max_len], append_eos=False))
+    return out
+
+
+def prefix_matrix(prefixes, index):
+    """The rows ``index`` of load_prefixes' list as features["prefix"]: int32 [len(index), P], right-padded with 0."""
+    rows = [prefixes[i] for i in index]
+    out = np.zeros((len(rows), max(1, max(len(r) for r in rows))), dtype=np.int32)
+    for b, r in enumerate(rows):
+        out[b, :len(r)] = r
+    return out
+
+
+def decoding(graph, dataset, params, infer=None, streams=None, prefixes=None):
     """Translate ``dataset``; ``infer(features, graph, params) -> (seqs [B,K,L], scores [B,K])``
     defaults to zero_amd.main.tower_infer_graph.  Batches are decoded ``streams`` (default ``decode_streams()``) at a
-    time (decode_many)."""
+    time (decode_many).  prefixes: load_prefixes' list (tgt_prefix_file); every batch then carries features["prefix"] and
+    every hypothesis starts with its sentence's prefix."""
     if infer is None:
         from zero_amd.main import tower_infer_graph as infer
     translations, scores, indices = [], [], []
@@ -171,7 +199,10 @@ def decoding(graph, dataset, params, infer=None, streams=None):
 
     def work(data):
         start = time.time()
-        seqs, sc = infer({"source": data['src']}, graph, params)
+        features = {"source": data['src']}
+        if prefixes is not None:
+            features["prefix"] = prefix_matrix(prefixes, data['index'])
+        seqs, sc = infer(features, graph, params)
         return data, np.asarray(seqs), np.asarray(sc), time.time() - start
 
     # (dev-mode search re-encodes on the training path of lane 0's engine: one batch at a time)

@@ -777,6 +777,17 @@ def _eval_trainer(params):
     return trainer
 
 
+def _load_prefixes(params):
+    """tgt_prefix_file of --mode test / ensemble: the forced target prefixes in the numbering of the test set's batches
+    (evalu.load_prefixes), or None when the option is off."""
+    from zero_amd import evalu
+    from zero_amd.models._decode import check_prefix_opts, prefix_file
+    if not prefix_file(params):
+        return None
+    check_prefix_opts(params)
+    return evalu.load_prefixes(params.src_test_file, params.tgt_prefix_file, params.tgt_vocab, params.eval_max_len)
+
+
 def evaluate(params):
     """main.py:469-535: translate the test set, BLEU against ``tgt_test_file``, dump to
     ``test_output``."""
@@ -784,9 +795,10 @@ def evaluate(params):
     from zero_amd.data import Dataset
     dataset = Dataset(params.src_test_file, params.src_test_file, params.src_vocab, params.src_vocab,
                       params.eval_max_len, batch_or_token='batch', data_leak_ratio=params.data_leak_ratio)
+    prefixes = _load_prefixes(params)      # tgt_prefix_file; a bad file is refused before the checkpoint is read
     trainer = _eval_trainer(params)
     t0 = time.time()
-    tranes, scores, indices = evalu.decoding(trainer.graph, dataset, params)
+    tranes, scores, indices = evalu.decoding(trainer.graph, dataset, params, prefixes=prefixes)
     bleu = evalu.eval_metric(tranes, params.tgt_test_file, indices=indices)
     log.info("Scores %s, BLEU %s, Duration %ss", np.mean(scores) if scores else 0.0, bleu, time.time() - t0)
     evalu.dump_tanslation(tranes, params.test_output, indices=indices)
@@ -841,11 +853,12 @@ def ensemble(total_params):
                       default_params.src_vocab, default_params.eval_max_len, batch_or_token='batch',
                       data_leak_ratio=default_params.data_leak_ratio)
     total_graphs = [model_registry.get_model(p.model_name) for p in total_params]
+    prefixes = _load_prefixes(default_params)      # member 0's tgt_prefix_file, like its test set
     for midx, p in enumerate(total_params):
         restore_ensemble_member(p, midx)
     t0 = time.time()
     tranes, scores, indices = evalu.decoding(
-        total_graphs[0], dataset, default_params, streams=1,
+        total_graphs[0], dataset, default_params, streams=1, prefixes=prefixes,
         infer=lambda features, graph, params: tower_ensemble_graph(features, total_graphs, total_params))
     bleu = evalu.eval_metric(tranes, default_params.tgt_test_file, indices=indices)
     log.info("Scores %s, BLEU %s, Duration %ss", np.mean(scores) if scores else 0.0, bleu, time.time() - t0)

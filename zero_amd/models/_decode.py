@@ -84,6 +84,8 @@ def _graph_pointers(state, book):
     own = getattr(state, "graph_pointers", None)      # a state that is not a Transformer layer stack names its own
     if state.get("ngram_hist") is not None:           # the history the n-gram ban reads (the book's seq, or ngram_history)
         book = (tuple(book) if book is not None else ()) + tuple(state["ngram_hist"])
+    if state.get("prefix") is not None:               # the table of forced target prefixes (prefix_table) and its row stride
+        book = (tuple(book) if book is not None else ()) + tuple(state["prefix"])
     if own is not None:
         return tuple(own()) + (tuple(book) if book is not None else ())
     core = state["_core"]
@@ -119,7 +121,7 @@ def _f32_bits(x):
 def graph_key(state, book, temperature, forbid_value, noise, dec_group, ngram=0, sample=None, diverse=None):
     """What tells the step graphs of one batch from those of another: the shape, the search's constants and the option set
     (ngram: the n-gram size of the step's ban node, 0 = none; sample: sampling_opts' pair when the step truncates; diverse:
-    diverse_opts' pair when the step selects per beam group)."""
+    diverse_opts' pair when the step selects per beam group; state["prefix"], prefix_table's: the step forces a prefix)."""
     key = (state["B"], state["K"], state["Ls"], state["Tmax"], book is not None, float(temperature),
            float(forbid_value), bool(noise), int(dec_group), bool(state.get("f32")))
     if state.get("shortlist") is not None:      # the size of the output vocabulary is part of a step's shape
@@ -130,6 +132,8 @@ def graph_key(state, book, temperature, forbid_value, noise, dec_group, ngram=0,
         key += (("sample", int(sample[0]), _f32_bits(sample[1])),)
     if diverse_on(diverse):                     # and one with the group selection, per (G, lambda): launch arguments too
         key += (("diverse", int(diverse[0]), _f32_bits(diverse[1])),)
+    if state.get("prefix") is not None:         # and one with the forced-prefix node (a batch of empty prefixes has none)
+        key += (("prefix",),)
     return key
 
 
@@ -384,6 +388,118 @@ def sample_truncate(e, logits, rows, V, topk, topp, min_keep, forbid_value):
                -float(forbid_value), e.stream)
 
 
+def prefix_file(hp):
+    """hp.tgt_prefix_file as a string: "" = off."""
+    return getattr(hp, "tgt_prefix_file", "") or ""
+
+
+def check_prefix_opts(hp):
+    """What tgt_prefix_file does not go together with; nothing here depends on the data, so infer_fn refuses before a core is
+    built."""
+    if prefix_file(hp) and _shortlist.wanted(hp):
+        raise NotImplementedError("tgt_prefix_file=%s with shortlist_file=%s: a forced token must be a candidate of its batch, "
+                                  "i.e. the prefix ids would have to be forced into the batch's shortlist inside "
+                                  "zk_shortlist_build, which is not built" % (hp.tgt_prefix_file, hp.shortlist_file))
+
+
+def check_prefix(prefix, B, V, eos_id, src_len, decode_length):
+    """features["prefix"] of a batch of B sentences -> (int32 [B, P] right-padded with 0, the lengths n_b [B]), or (None,
+    None) for None.  ValueError, naming the sentence and the numbers: a row count other than B; an id outside [1, V); EOS; a
+    0 followed by a non-zero; n_b >= src_len_b + decode_length (the search stops a sentence at that length: the hypothesis
+    could not end).  Nothing here touches the device: the search calls it before the encoder pass."""
+    if prefix is None:
+        return None, None
+    p = np.asarray(prefix.cpu() if torch.is_tensor(prefix) else prefix)
+    if p.ndim != 2 or p.shape[0] != int(B):
+        raise ValueError("features['prefix'] has shape %s: one row of target ids per sentence of the batch, [%d, P], is "
+                         "expected" % (tuple(p.shape), B))
+    if p.dtype.kind not in "iu":
+        raise ValueError("features['prefix'] holds %s values: target ids are integers" % p.dtype)
+    p = p.astype(np.int64)
+    n = (p != 0).sum(1)
+    for b in range(int(B)):
+        row = p[b]
+        if (row[:n[b]] == 0).any():
+            t = int(np.argmax(row == 0))
+            raise ValueError("prefix of sentence %d: position %d is 0 (padding) and position %d holds id %d; a prefix is "
+                             "right-padded" % (b, t, int(np.nonzero(row)[0][-1]), int(row[np.nonzero(row)[0][-1]])))
+        bad = np.nonzero((row[:n[b]] < 1) | (row[:n[b]] >= int(V)))[0]
+        if bad.size:
+            raise ValueError("prefix of sentence %d: id %d at position %d is outside [1, %d), the target vocabulary"
+                             % (b, int(row[bad[0]]), int(bad[0]), V))
+        if (row[:n[b]] == int(eos_id)).any():
+            raise ValueError("prefix of sentence %d: position %d holds the end-of-sentence id %d; a hypothesis cannot go on "
+                             "behind it" % (b, int(np.argmax(row == int(eos_id))), eos_id))
+        limit = int(src_len[b]) + int(decode_length)
+        if n[b] >= limit:
+            raise ValueError("prefix of sentence %d: %d tokens, but the search ends a hypothesis of this sentence at source "
+                             "length + decode_length = %d + %d = %d tokens: it could not end" %
+                             (b, int(n[b]), int(src_len[b]), int(decode_length), limit))
+    return np.ascontiguousarray(p[:, :max(1, int(n.max()) if n.size else 1)].astype(np.int32)), n.astype(np.int64)
+
+
+def check_prefix_ngram(prefix, n):
+    """tgt_prefix_file with no_repeat_ngram_size = n: a prefix that holds an n-gram twice is refused (ValueError naming the
+    sentence, the position and the n-gram).  The ban runs ahead of the force and the force leaves the forced entry as it
+    finds it, so where the ban has taken the forced token itself -- the second occurrence of the n-gram -- that entry holds
+    the same forbid value as the fillers around it, ties with them, and the lowest index wins: the hypothesis would leave its
+    prefix.  During a prefix the row's history IS the prefix, so this is the only case in which a ban meets a forced token,
+    and it is known before the encoder pass."""
+    if prefix is None or n <= 0:
+        return
+    for b, row in enumerate(np.asarray(prefix)):
+        toks = [int(v) for v in row if int(v) != 0]
+        seen = {}
+        for i in range(len(toks) - n + 1):
+            g = tuple(toks[i:i + n])
+            if g in seen:
+                raise ValueError("prefix of sentence %d with no_repeat_ngram_size=%d: the %d-gram %s at position %d is already "
+                                 "at position %d; the ban would take the forced token %d and the hypothesis would leave its "
+                                 "prefix" % (b, n, n, g, i, seen[g], g[-1]))
+            seen[g] = i
+
+
+def prefix_table(state, prefix, eos_id):
+    """Upload a batch's checked prefixes (check_prefix's array, or None) for the step's force node: a persistent int32 [B,
+    Tmax] device buffer under the decode mode's prefix -- the same address for every batch of a shape, so a later batch can
+    adopt the captured step graphs -- filled through a pinned staging copy on the current stream.  state["prefix"] = (device
+    address, row stride) is what search_tail launches with and what graph_key / _graph_pointers see; None, and no buffer is
+    touched, when every prefix of the batch is empty: such a batch issues no launch.  -> state["prefix"]"""
+    state["prefix"] = None
+    if prefix is None or not np.asarray(prefix).any():
+        return None
+    core = state["_core"]
+    st = getattr(state, "storage", BF16_CACHES)
+    own = getattr(state, "graph_pointers", None)
+    B, cols = int(state["B"]), int(state["Tmax"])
+    prefix = np.asarray(prefix)
+    if prefix.shape[0] != B or prefix.shape[1] > cols:
+        raise ValueError("prefix table of shape %s for a batch of %d sentences and %d cache positions" %
+                         (tuple(prefix.shape), B, cols))
+    dev = core.eng.buf(st.prefix + ("rn." if own is not None else "") + "prefix.tbl", (B, cols), torch.int32)
+    pins = core.__dict__.setdefault("_decode_pins", {})
+    n = B * cols
+    host = pins.get("prefix")
+    if host is None or host.numel() < n:
+        host = pins["prefix"] = torch.zeros(n + n // 4, dtype=torch.int32).pin_memory()
+    host = host[:n].view(B, cols)
+    host.zero_()
+    host.numpy()[:, :prefix.shape[1]] = prefix
+    dev.copy_(host, non_blocking=True)
+    state["prefix"] = (dev.data_ptr(), cols)
+    state["prefix_eos"] = int(eos_id)
+    return state["prefix"]
+
+
+def prefix_force(e, logits, rows, V, table, K, eos_id, forbid_value, time=0, time_dev=None):
+    """zk_prefix_force on the step's logits Mat; table = (device address of the int32 prefix table, its row stride), K = the
+    beam rows per sentence (the model's beam_size: the groups of a diverse beam share the sentence's prefix).  forbid_value is
+    the search tail's, dtype.inf() = +1e8: a forced row holds -forbid_value everywhere but at its token, -2 * forbid_value
+    at eos_id."""
+    e.lib.call("zk_prefix_force", logits.ptr, logits.ld, rows, V, table[0], table[1], int(K), int(time),
+               time_dev.data_ptr() if time_dev is not None else None, int(eos_id), -float(forbid_value), e.stream)
+
+
 DIVERSE_DEPTH_MAX = 16      # the deepest candidate list zk_beam_topk returns per row (TOPK_MAX of zk_decode.hip)
 
 
@@ -423,7 +539,8 @@ def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0, 
     is n-gram ban, truncation, noise, tail: the noise then draws from the truncated distribution, and banned tokens -- at the
     forbid value, with mass 0 and the lowest rank -- stay out of the counts and the mass.  With diverse = (G, lambda, eos_id),
     G > 1 (diverse_opts + the EOS id: diverse_beam_groups / diverse_beam_strength), the fused tail is replaced by the per-row
-    top-k, zk_diverse_select and the bookkeeping on B*G pseudo-sentences (below).  Launches on the current stream with
+    top-k, zk_diverse_select and the bookkeeping on B*G pseudo-sentences (below).  With state["prefix"] set (prefix_table:
+    tgt_prefix_file) zk_prefix_force runs directly ahead of either tail, and ahead of the truncation where there is one.  Launches on the current stream with
     the scratch of ``core``'s engine; shared by the single-model step and the ensemble step (models/_ensemble.py)."""
     e = core.eng
     book = state.get("book")
@@ -433,6 +550,13 @@ def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0, 
         if ngram > 0:
             ngram_ban(e, logits, state["BK"], V, state["ngram_hist"], ngram, forbid_value, time_dev=sb[0:1])
             ngram = 0
+        if state.get("prefix") is not None:
+            # a forced token outside the kept set would be truncated to the forbid value, which the force below -- it leaves
+            # the forced entry as it finds it -- could not undo: force ahead of the truncation too.  The forced entry is then
+            # the row's only real one and survives; the truncation lifts EOS from twice the forbid value back to it, which
+            # the force ahead of the tail puts right again.  (This combination has two force launches per step.)
+            prefix_force(e, logits, state["BK"], V, state["prefix"], state["K"], state["prefix_eos"], forbid_value,
+                         time_dev=sb[0:1])
         sample_truncate(e, logits, state["BK"], V, sample[0], sample[1], sampling_min_keep(state["K"]), forbid_value)
     if noise:      # search.py:143-145; a fresh stream position every step
         e.lib.call("zk_add_gumbel", logits.ptr, state["BK"], V, logits.ld, float(zdtype.epsilon()),
@@ -443,6 +567,11 @@ def search_tail(state, core, logits, noise, temperature, forbid_value, ngram=0, 
         # (the previous step's advance wrote the alive rows in the order flat_idx reorders the caches to), or the buffer
         # the host refreshes (ngram_history); the step's time word is read on the device
         ngram_ban(e, logits, state["BK"], V, state["ngram_hist"], ngram, forbid_value, time_dev=sb[0:1])
+    if state.get("prefix") is not None:
+        # tgt_prefix_file: the last launch ahead of the tail, so a forced token wins over a ban, a truncation and the noise;
+        # the rows of a sentence are the model's beam (all groups of a diverse beam), the time word is read on the device
+        prefix_force(e, logits, state["BK"], V, state["prefix"], state["K"], state["prefix_eos"], forbid_value,
+                     time_dev=sb[0:1])
     if diverse_on(diverse):
         # Diverse beam search: three launches instead of the fused tail.  (1) zk_beam_topk with B*K "sentences" of beam 1:
         # every row's k2 = K + K/G best (score, token).  That depth is exact: a kept candidate with an unpenalised token has
@@ -852,6 +981,7 @@ def make_infer_fns(params, model_name):
     ngram_size(hp)
     sampling_opts(hp)
     diverse_opts(hp)
+    check_prefix_opts(hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)

@@ -360,6 +360,7 @@ def make_infer_fns(params, model_name):
     _dec.ngram_size(hp)
     _dec.sampling_opts(hp)
     _dec.diverse_opts(hp)
+    _dec.check_prefix_opts(hp)
 
     def encoding_fn(source, beam_size=None, max_steps=None):
         core = get_core(hp, model_name)

@@ -97,6 +97,15 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
     src_len = (src_np != 0).sum(-1).astype(f32)
     max_target_length = src_len + f32(params.decode_length)
     cache_mode = params.search_mode == "cache"
+    # tgt_prefix_file: features["prefix"], optional, int [B, P] right-padded with 0 -- the target ids every hypothesis of a
+    # sentence starts with (the rule is stated in tests/prefix_ref.py); refused here, before the encoder pass
+    prefix, _ = _dec.check_prefix(features.get("prefix"), B, V, eos_id, src_len, params.decode_length)
+    if prefix is not None:
+        _dec.check_prefix_ngram(prefix, _dec.ngram_size(params))
+        from zero_amd import shortlist as _sl
+        if _sl.wanted(params):
+            raise NotImplementedError("features['prefix'] with shortlist_file=%s: the prefix ids would have to be forced into "
+                                      "the batch's shortlist, which is not built" % params.shortlist_file)
     if cache_mode:
         # start-up (allocations, pinned staging, the two graph captures) is serialised between concurrent batches
         # (models/_decode.py STARTUP_LOCK); step_static releases it once both step graphs exist, _beam_search at the end
@@ -104,6 +113,7 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
         try:
             state = encoding_fn(source, beam_size=K,
                                 max_steps=int(max_target_length.max()) + 2)
+            _dec.prefix_table(state, prefix, eos_id)      # state["prefix"]: the step's force node reads it (search_tail)
         except BaseException:
             _dec.STARTUP_LOCK.release()
             raise
@@ -117,6 +127,14 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
         state = np.repeat(src_np, K, axis=0)      # expand_tile_dims of the raw source
     e = core.eng
     dev = e.device
+    if cache_mode:
+        prefix_tab = state.get("prefix")
+    elif prefix is not None and prefix.any():       # search_mode=dev keeps no state: the eager steps' table
+        d_prefix = e.buf("bs.prefix", prefix.shape, torch.int32)
+        d_prefix.copy_(torch.from_numpy(prefix))
+        prefix_tab = (d_prefix.data_ptr(), prefix.shape[1])
+    else:
+        prefix_tab = None
     Kall = K
     if G > 1:
         # Diverse beam search: every group is a beam search of its own, so from here on the bookkeeping sees B * G
@@ -217,6 +235,8 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
                     _dec.ngram_ban(e, logits, B * K, V, (hist_dev.data_ptr(), hist_np.shape[1]), ngram, zdtype.inf(),
                                    time=time)
                     ban_left = 0
+                if prefix_tab is not None:      # ahead of the truncation too, which would take a forced token outside its set
+                    _dec.prefix_force(e, logits, B * K, V, prefix_tab, Kall, eos_id, zdtype.inf(), time=time)
                 # (min_keep from the sentence's whole beam, as the captured step's: with groups K here is K / G, and the
                 # per-row lists of depth K + K/G need that many real candidates)
                 _dec.sample_truncate(e, logits, B * K, V, sample[0], sample[1], _dec.sampling_min_keep(Kall), zdtype.inf())
@@ -226,6 +246,8 @@ def _beam_search_body(features, encoding_fn, decoding_fn, params, box):
                 e.lib.call("zk_seed_advance", e.seed.data_ptr(), 1, e.stream)
             if ban_left > 0:
                 _dec.ngram_ban(e, logits, B * K, V, (hist_dev.data_ptr(), hist_np.shape[1]), ngram, zdtype.inf(), time=time)
+            if prefix_tab is not None:      # the last launch ahead of the tail; a sentence's rows are the model's whole beam
+                _dec.prefix_force(e, logits, B * K, V, prefix_tab, Kall, eos_id, zdtype.inf(), time=time)
             d_prev.copy_(torch.from_numpy(log_probs.reshape(-1)))
             if G > 1:
                 # per-row candidates, the group selection (models/_decode.py search_tail), then the bookkeeping below
