@@ -938,6 +938,35 @@ int zk_f32_rnn_lrn_scan(const float* h_prev, int ldh, int n_prev, const int* idx
                         const float* hi, long hi_ps, long hi_rs, const float* mask, long m_ps, long m_rs, float* out, int ldo,
                         float* seq, long seq_ps, long seq_rs, int R, int H, int T, int reverse, int gated, zk_stream_t stream);
 
+/* Word alignment from one decoder layer's cross-attention (hp.alignment_file; zero_amd/models/_align.py, zk_align.hip): the
+ * head-averaged attention weights of func.py:218-256 (additive mask of func.py:372-400) and their arg-max, from the layer's q
+ * and k projections alone -- no value product, no context.  For sentence b, decoder row t, source position j:
+ *   P[b, t, j] = (1 / nh) * sum_h softmax_j(scale * q[b, t, h] . k[b, j, h] + (1 - kmask[b, j]) * -mask_inf)   heads ascending
+ *   best[b, t] = argmax_j P[b, t, j] over the ELIGIBLE positions (amask[b, j] != 0); the lowest j wins on equal values;
+ *                -1 for a row without an eligible position.
+ *   q, ldq, bsq   [B, Lq, >= nh * d] of the storage type; row stride ldq and sentence stride bsq in elements (a qkv-style
+ *                 column slice passes: ldq = 3 H); head h in the columns h d .. h d + d - 1.
+ *   k, ldk, bsk   [B, Lk, >= nh * d] likewise (the first H columns of a [., 2 H] kv buffer: ldk = 2 H).
+ *   kmask, ldmask fp32 [B, ldmask >= Lk], 1 = valid key, or NULL (all valid).  A masked key's weight is exactly 0 in every row
+ *                 that has a valid key.
+ *   amask         fp32 [B, ldmask] (the same row stride), the positions the arg-max may return, or NULL (= kmask).
+ *   probs, ldp, bsp   fp32 [B, Lq, ldp >= Lk], sentence stride bsp; only the Lk columns of a row are written.  May be NULL.
+ *   best          int32 [B, Lq].  May be NULL; at least one of probs / best is given.
+ *   scale, mask_inf   those of the layer (d^-0.5, dtype_inf).
+ * All softmax arithmetic and the head average are fp32; no atomics, one fixed order: two runs are bit-identical.
+ * zk_align_probs: bf16 q / k, scores by v_mfma_f32_16x16x32_bf16, d a multiple of 32 up to 128, q and k rows 16-byte aligned
+ * (pointer, ld and bs multiples of 8).  zk_f32_align_probs: fp32 q / k, fused multiply-adds with the channels ascending, d a
+ * multiple of 4 up to 128, k rows 16-byte aligned.  Lk <= zk_align_max_lk() = 1024 (two [16][Lk] fp32 images of a block of 16
+ * decoder rows in LDS).  Anything else -- a longer source, a short stride, an unaligned row, another d, both outputs NULL --
+ * is refused by name: nothing is launched and the buffers stay untouched. */
+int zk_align_probs(const void* q, int ldq, long bsq, const void* k, int ldk, long bsk, const float* kmask, int ldmask,
+                   const float* amask, float* probs, int ldp, long bsp, int* best, int B, int nh, int Lq, int Lk, int d,
+                   float scale, float mask_inf, zk_stream_t stream);
+int zk_f32_align_probs(const float* q, int ldq, long bsq, const float* k, int ldk, long bsk, const float* kmask, int ldmask,
+                       const float* amask, float* probs, int ldp, long bsp, int* best, int B, int nh, int Lq, int Lk, int d,
+                       float scale, float mask_inf, zk_stream_t stream);
+int zk_align_max_lk(void);
+
 /* hipGraph plumbing: capture a sequence of the calls above once, replay per step */
 int zk_graph_begin(zk_stream_t stream);
 int zk_graph_end(zk_stream_t stream, void** exec_out);

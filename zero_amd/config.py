@@ -92,6 +92,16 @@ _DEFAULTS = [
     # overwritten with the forbid value BEFORE the log-softmax, so a forced token scores exactly 0 and a hypothesis' score
     # is log P(continuation | prefix); "" = off.  Not together with shortlist_file
     ("tgt_prefix_file", ""),
+    # build-specific: word alignments from the decoder's cross-attention (zero_amd/align.py, models/_align.py, zk_align_probs;
+    # the rule is stated in tests/align_ref.py).  alignment_file: --mode test writes one line per source line there, the
+    # space-separated 0-based pairs s-t of the best hypothesis (t ascending); --mode score aligns the given (source, target)
+    # pairs.  The alignment is read off ONE teacher-forced pass behind the search (the head-averaged weights of one decoder
+    # layer, arg-max over the source words), so every search option keeps working unchanged; "" = off
+    ("alignment_file", ""),
+    # the decoder layer whose cross-attention is read, a Python-style index (-1 = the last layer)
+    ("alignment_layer", -1),
+    # every <unk> of a hypothesis becomes the raw source word it is aligned to (needs alignment_file)
+    ("replace_unk", False),
 ]
 
 

@@ -238,6 +238,41 @@ def scoring(graph, dataset, params, score=None):
     return scores, ppl
 
 
+def aligning(graph, pairs, params, align=None):
+    """alignment_file: ``pairs`` = [(source ids with EOS, target ids with EOS)] in file order -> [[(s, t)]] in the same
+    order (zero_amd.align.hard_pairs per sentence; an empty target gives no pairs).  Batched by eval_batch_size in file
+    order, one batch at a time on the default core, like ``scoring``.  ``align(features, graph, params) -> int [B, Lt]``
+    defaults to zero_amd.main.tower_align_graph."""
+    from zero_amd.align import hard_pairs
+    if align is None:
+        from zero_amd.main import tower_align_graph as align
+    out = []
+    size = max(1, int(params.eval_batch_size))
+    for i in range(0, len(pairs), size):
+        chunk = pairs[i:i + size]
+        live = [j for j, (s, t) in enumerate(chunk) if len(s) > 1 and len(t) > 1]       # (more than the EOS on both sides)
+        rows = {}
+        if live:
+            src = np.zeros((len(live), max(len(chunk[j][0]) for j in live)), dtype=np.int32)
+            tgt = np.zeros((len(live), max(len(chunk[j][1]) for j in live)), dtype=np.int32)
+            for r, j in enumerate(live):
+                src[r, :len(chunk[j][0])] = chunk[j][0]
+                tgt[r, :len(chunk[j][1])] = chunk[j][1]
+            best = _to_numpy(align({"source": src, "target": tgt}, graph, params))
+            rows = {j: best[r] for r, j in enumerate(live)}
+        for j, (s, t) in enumerate(chunk):
+            out.append(hard_pairs(rows[j], len(s) - 1, len(t) - 1) if j in rows else [])
+    return out
+
+
+def dump_alignments(lines, output):
+    os.makedirs(os.path.dirname(os.path.abspath(output)), exist_ok=True)
+    with open(output, 'w') as writer:
+        for line in lines:
+            writer.write(line + "\n")
+    log.info("Saving alignments into %s", output)
+
+
 def _to_numpy(x):
     if hasattr(x, "detach"):
         return x.detach().float().cpu().numpy()

@@ -650,6 +650,20 @@ class Engine(object):
         name = "zk_f32_fixup_relu_shift" if h.t.dtype == torch.float32 else "zk_fixup_relu_shift"
         self.lib.call(name, h.ptr, h.ld, hip.ptr(offset), out.ptr, out.ld, h.rows, h.cols, self.stream)
 
+    def align_probs(self, q, k, B, nh, Lq, Lk, d, kmask=None, ldmask=0, amask=None, probs=None, best=None, bsq=0, bsk=0,
+                    mask_inf=None):
+        """The head-averaged cross-attention weights and their arg-max from a layer's q / k projections (zk_align_probs /
+        zk_f32_align_probs by q's dtype; include/zero_hip.h).  q: Mat [B * Lq, >= nh * d], k: Mat [B * Lk, >= nh * d] of the
+        storage type (bs* = sentence strides in elements, 0: Lq or Lk rows); kmask / amask: fp32 [B, ldmask] or None;
+        probs: fp32 tensor [B, Lq, ldp >= Lk] or None; best: int32 [B, Lq] or None; mask_inf: the additive mask's magnitude
+        (default: dtype_inf, as every attention launch)."""
+        name = "zk_f32_align_probs" if q.t.dtype == torch.float32 else "zk_align_probs"
+        ldp = int(probs.stride(1)) if probs is not None else 0
+        bsp = int(probs.stride(0)) if probs is not None else 0
+        self.lib.call(name, q.ptr, q.ld, int(bsq or Lq * q.ld), k.ptr, k.ld, int(bsk or Lk * k.ld), hip.ptr(kmask),
+                      int(ldmask or Lk), hip.ptr(amask), hip.ptr(probs), ldp, bsp, hip.ptr(best), B, nh, Lq, Lk, d,
+                      float(d) ** -0.5, float(zdtype.inf() if mask_inf is None else mask_inf), self.stream)
+
     # ---- rnnsearch (zk_rnn.hip); the bf16 or the fp32 form by the dtype of the storage-type operand
     def rnn_atr_step(self, h_prev, U, b, p, out, out_copy=None, idx=None, mask=None):
         """rnns/atr.py:32-60 + the carry of rnns/rnn.py:41-49, one time step of one cell: out = carry(mask,

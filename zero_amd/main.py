@@ -49,6 +49,12 @@ def tower_infer_graph(eval_features, graph, params):
     return out["seq"], out["score"]
 
 
+def tower_align_graph(eval_features, graph, params):
+    """alignment_file: the hard alignment int32 [B, Lt] of a {"source", "target"} batch (zero_amd/align.py align_fn)."""
+    from zero_amd.align import align_fn
+    return align_fn(eval_features, params, params.model_name)["best"]
+
+
 def tower_ensemble_graph(eval_features, total_graphs, total_params):
     """main.py:65-115: several models per beam step, combined on the device (zero_amd/models/_ensemble.py)."""
     from zero_amd.models._ensemble import tower_ensemble_graph as impl
@@ -788,17 +794,51 @@ def _load_prefixes(params):
     return evalu.load_prefixes(params.src_test_file, params.tgt_prefix_file, params.tgt_vocab, params.eval_max_len)
 
 
+def _read_pairs(params, with_target):
+    """The test set as evalu's batches number it (data.Dataset.load_data: lines that are empty on a side it reads are
+    dropped): -> [(raw source tokens, source ids with EOS, target ids with EOS or None)] in file order."""
+    out = []
+    tgt_file = params.tgt_test_file if with_target else params.src_test_file
+    with open(params.src_test_file, 'r') as sr, open(tgt_file, 'r') as tr:
+        for s, t in zip(sr, tr):
+            s, t = s.strip(), t.strip()
+            if s == "" or t == "":
+                continue
+            out.append((s.split(), params.src_vocab.to_id(s.split()[:params.eval_max_len]),
+                        params.tgt_vocab.to_id(t.split()[:params.eval_max_len]) if with_target else None))
+    return out
+
+
+def _align_and_dump(graph, params, lines, targets):
+    """alignment_file: align ``targets`` (token ids with EOS, one per entry of ``lines``), write the file -> [[(s, t)]]."""
+    from zero_amd import evalu
+    from zero_amd.align import format_pairs
+    pairs = evalu.aligning(graph, [(src, tgt) for (_, src, _), tgt in zip(lines, targets)], params)
+    evalu.dump_alignments([format_pairs(p) for p in pairs], params.alignment_file)
+    return pairs
+
+
 def evaluate(params):
     """main.py:469-535: translate the test set, BLEU against ``tgt_test_file``, dump to
-    ``test_output``."""
+    ``test_output``.  With alignment_file the best hypothesis of every line is aligned behind the search (and, with
+    replace_unk, its <unk> tokens replaced before BLEU and the dump)."""
     from zero_amd import evalu
     from zero_amd.data import Dataset
+    from zero_amd import align as zalign
+    aligned = zalign.check_opts(params, "test")      # refusals come before the checkpoint is read
     dataset = Dataset(params.src_test_file, params.src_test_file, params.src_vocab, params.src_vocab,
                       params.eval_max_len, batch_or_token='batch', data_leak_ratio=params.data_leak_ratio)
     prefixes = _load_prefixes(params)      # tgt_prefix_file; a bad file is refused before the checkpoint is read
     trainer = _eval_trainer(params)
     t0 = time.time()
     tranes, scores, indices = evalu.decoding(trainer.graph, dataset, params, prefixes=prefixes)
+    if aligned:
+        tranes, indices = [d[1] for d in sorted(zip(indices, tranes), key=lambda x: x[0])], None      # file order
+        lines = _read_pairs(params, False)
+        pairs = _align_and_dump(trainer.graph, params, lines, [params.tgt_vocab.to_id(h) for h in tranes])
+        if params.replace_unk:
+            tranes = [zalign.replace_unk_tokens(h, p, raw, params.tgt_vocab.unk_sym)
+                      for h, p, (raw, _, _) in zip(tranes, pairs, lines)]
     bleu = evalu.eval_metric(tranes, params.tgt_test_file, indices=indices)
     log.info("Scores %s, BLEU %s, Duration %ss", np.mean(scores) if scores else 0.0, bleu, time.time() - t0)
     evalu.dump_tanslation(tranes, params.test_output, indices=indices)
@@ -809,11 +849,16 @@ def scorer(params):
     """main.py:538-607: per-sentence scores of (src_test_file, tgt_test_file) + perplexity."""
     from zero_amd import evalu
     from zero_amd.data import Dataset
+    from zero_amd import align as zalign
+    aligned = zalign.check_opts(params, "score")     # refusals come before the checkpoint is read
     dataset = Dataset(params.src_test_file, params.tgt_test_file, params.src_vocab, params.tgt_vocab,
                       params.eval_max_len, batch_or_token='batch', data_leak_ratio=params.data_leak_ratio)
     trainer = _eval_trainer(params)
     t0 = time.time()
     scores, ppl = evalu.scoring(trainer.graph, dataset, params)
+    if aligned:      # the given (source, target) pairs, next to their scores
+        lines = _read_pairs(params, True)
+        _align_and_dump(trainer.graph, params, lines, [tgt for _, _, tgt in lines])
     log.info("Scores %s, PPL %s, Duration %ss", np.mean(scores), ppl, time.time() - t0)
     evalu.dump_tanslation(scores, params.test_output)
     return float(np.mean(scores))
@@ -846,6 +891,9 @@ def ensemble(total_params):
     from zero_amd.data import Dataset
     from zero_amd.models._ensemble import check_members
     load_all()
+    from zero_amd import align as zalign
+    for p in total_params:
+        zalign.check_opts(p, "ensemble")       # alignment_file / replace_unk: refused here, by name
     check_members(total_params)
     default_params = total_params[0]
     # (different members are assumed to use the same test file and to share both vocabularies, main.py:627-629)

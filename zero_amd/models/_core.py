@@ -379,7 +379,9 @@ class TransformerCore(object):
         e.gemm_grouped(probs, 0, 0)
 
     def _cross_attn_fwd(self, x, mem, B, Lq, Lk, scope, tag, kmask, save, sid0, train, kv_ready=False,
-                        fuse_tmask=None):
+                        fuse_tmask=None, align=None):
+        """align: the hook of the alignment pass (models/_align.py), called right behind the attention launch as
+        align(x, q, kv, p) -- q is None where the launch formed it itself (fuse_proj); None: nothing differs."""
         e, H = self.eng, self.H
         hp = self.hp
         p = scope + "/dot_attention/"
@@ -406,10 +408,14 @@ class TransformerCore(object):
                                         hp.attention_dropout if train else 0.0, sid0, p + "o_map", x, scope, tag, save,
                                         hp.residual_dropout if train else 0.0, sid0 + 1, proj=pj)
                 if out is not None:
+                    if align is not None:
+                        align(x, None if pj is not None else q, kv, p)
                     return out
         e.attn_fwd(q, kv.cols_slice(0, H), kv.cols_slice(H, 2 * H), att, lse, B, self.nh, Lq, Lk, self.d,
                    kmask=kmask, causal=False, rpr_k=rk, rpr_v=rv, max_rel=hp.max_relative_position,
                    drop_p=hp.attention_dropout if train else 0.0, sid=sid0)
+        if align is not None:
+            align(x, q, kv, p)
         if fuse_tmask is not None:
             # func.py:258-275: o += average over valid positions j <= i of v_map(query)
             vq = e.mat("tmp.vq%d" % x.rows, x.rows, H)
@@ -704,8 +710,9 @@ class TransformerCore(object):
             x = self._ffn_fwd(x, pre + "/feed_forward", "e%d.ff" % l, save, 100 * l + 11, train)
         return x, smask
 
-    def decode_train(self, batch, enc, smask, train, save):
-        """transformer.py:87-181 (training path: shifted inputs, causal self-attention)."""
+    def decode_train(self, batch, enc, smask, train, save, align=None):
+        """transformer.py:87-181 (training path: shifted inputs, causal self-attention).  align = (layer, hook): the
+        alignment pass (models/_align.py) -- the hook runs behind that layer's cross-attention and the layers end there."""
         e, hp, H = self.eng, self.hp, self.H
         B, Ls, Lt = batch["B"], batch["Ls"], batch["Lt"]
         Tt = B * Lt
@@ -734,8 +741,11 @@ class TransformerCore(object):
             elif not self.fuse:
                 x = self._self_attn_fwd(x, B, Lt, pre + "/self_attention", "d%d.sa" % l, None, True, save,
                                         sid + 1, train)
+            tap = align[1] if align is not None and l == align[0] else None
             x = self._cross_attn_fwd(x, enc, B, Lt, Ls, pre + "/" + self.cross, "d%d.ca" % l, smask, save,
-                                     sid + 11, train, kv_ready=group_kv, fuse_tmask=tmask if self.fuse else None)
+                                     sid + 11, train, kv_ready=group_kv, fuse_tmask=tmask if self.fuse else None, align=tap)
+            if tap is not None:
+                return x, tmask, w
             x = self._ffn_fwd(x, pre + "/feed_forward", "d%d.ff" % l, save, sid + 21, train)
         return x, tmask, w
 
@@ -769,7 +779,7 @@ class TransformerCore(object):
             e.loss_reduce(ce, batch["tgt"], per_sample, loss, B, Lt)
         return loss, per_sample, logits, dlogits
 
-    def forward(self, batch, train=False, save=False, label_smooth=None):
+    def forward(self, batch, train=False, save=False, label_smooth=None, align=None):
         if self.fixup and (train or save):
             raise NotImplementedError("transformer_fixup has no training path: dropout and the saved activations of a "
                                       "backward are not built")
@@ -792,9 +802,12 @@ class TransformerCore(object):
             self._embeds_done = True
         try:
             enc, smask = self.encode(batch, train, save)
-            feat, tmask, w = self.decode_train(batch, enc, smask, train, save)
+            feat, tmask, w = self.decode_train(batch, enc, smask, train, save, align=align)
         finally:
             self._embeds_done = False
+        if align is not None:     # (models/_align.py: the pass ends behind the aligned layer; no logits, no loss)
+            self._sync_ln = False
+            return None
         loss, per_sample, logits, dlogits = self.loss_head(batch, feat, w, ls, save)
         self._sync_ln = False     # (encode() / decode_train() are also called directly by the decode path)
         self._ctx = (batch, enc, smask, feat, tmask, dlogits)

@@ -44,9 +44,10 @@ def check_model(core):
                            "zk_f32_attn_seq reads keys 16 bytes at a time and holds two channels per lane" % core.d)
 
 
-def decode_train(core, hp, batch, enc, smask, o):
+def decode_train(core, hp, batch, enc, smask, o, align=None):
     """transformer.py:87-181 / transformer_aan.py:120-192 / transformer_fuse.py:131-160, training path, in fp32:
-    -> decoder output Mat [B*Lt, H]."""
+    -> decoder output Mat [B*Lt, H].  align = (layer, hook): the alignment pass (models/_align.py) -- hook(q, k) runs
+    behind that layer's cross-attention and the layers end there (-> None)."""
     e, H = core.eng, core.H
     B, Ls, Lt = batch["B"], batch["Ls"], batch["Lt"]
     T = B * Lt
@@ -89,6 +90,9 @@ def decode_train(core, hp, batch, enc, smask, o):
         o.linear(enc, p + "v_map", mv)
         att = o.mat("att", T, H)
         o.attn_seq(qm, mk, mv, att, B, Lt, Ls, Lt * H, Ls * H, Ls * H, kmask=smask, ldmask=Ls, rpr=p if core.rpr else None)
+        if align is not None and l == align[0]:
+            align[1](qm, mk)
+            return None
         if core.fuse:
             # func.py:258-275: v_q = v_map(query); o += aan_weights x v_q (the masked cumulative average)
             vq = o.mat("vq", T, H)
